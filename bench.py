@@ -23,6 +23,9 @@ broadcasts the training set + cached posterior (alpha, U^-1) ONCE over RCCL; no 
 
 Prints ONE JSON line (rank 0) with `roofline` (dominant kernel sr_var_kernel, fp64 MFMA bound, timed
 live with hipEvents on the launch stream) and `cpu_baseline` (oracle on the host cores, bounded sample).
+`ms_per_step` is the wall time of one of the --steps timed steps.  With --dump-outputs DIR, rank 0 also writes what the
+timed path returned in its last step (DIR/<name>.npy, float64); the inputs are seeded, so two builds run with the same
+arguments can be compared output for output.
 """
 import argparse
 import json
@@ -188,7 +191,13 @@ def parse_args(argv=None):
                     "(parallel.fit_outputs_sharded: strong scaling, every factor broadcast once from its owner)")
     ap.add_argument("--dump-shards", default="", help="directory: every rank stores its query seed and the head of its "
                     "outputs of the last step there (shard_rank<r>.npz) -- for tests of the sharded path")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="directory: rank 0 writes what the timed path handed "
+                    "its caller in the last timed step as DIR/<name>.npy (float64, at most 64 MB in all: beyond that a fixed, "
+                    "seeded sample of rows) -- for output-for-output comparisons of two builds")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def dist_backend():
@@ -231,6 +240,45 @@ def main(argv=None):
                  nprocs=args.gpus, join=True)
         return
     run(args)
+
+
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SAMPLE_SEED = 0
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: every array (device tensor or ndarray) as DIR/<name>.npy in float64.  If they hold more than
+    DUMP_MAX_BYTES together, the arrays whose first axis is the longest are cut to the same fixed, seeded sample of rows
+    (ascending, drawn from DUMP_SAMPLE_SEED, the row count and the length alone, so equal runs write equal files).
+    Returns the description the JSON line carries."""
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    nbytes = {k: 8 * int(np.prod(v.shape)) for k, v in arrays.items()}
+    rows = max(v.shape[0] for v in arrays.values())
+    kept, info = rows, {"dir": os.path.abspath(dirname), "files": sorted(k + ".npy" for k in arrays)}
+    if sum(nbytes.values()) > DUMP_MAX_BYTES:
+        cut = [k for k, v in arrays.items() if v.shape[0] == rows]
+        rest = sum(nbytes[k] for k in arrays if k not in cut)
+        per_row = sum(nbytes[k] for k in cut) // rows
+        kept = max(1, (DUMP_MAX_BYTES - rest) // per_row)
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(rows, kept, replace=False))
+        info["sample"] = {"arrays": sorted(cut), "rows_kept": int(kept), "rows_total": int(rows),
+                          "seed": DUMP_SAMPLE_SEED, "rule": "np.sort(np.random.default_rng(seed).choice(rows_total, "
+                                                            "rows_kept, replace=False))"}
+    for k, v in arrays.items():
+        if kept < rows and v.shape[0] == rows:
+            v = v[torch.as_tensor(idx, device=v.device)] if torch.is_tensor(v) else v[idx]
+        a = v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)
+        np.save(os.path.join(dirname, k + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+    return info
+
+
+def dump_update_outputs(args, gp, idx, mu, var):
+    """--dump-outputs of --workload c4: the updated model a caller receives -- alpha = K_y^-1 y (N, n_out) -- and its
+    posterior mean and variance at the fixed sample of training inputs the identity check uses."""
+    if not args.dump_outputs:
+        return None
+    return dump_outputs(args.dump_outputs, {"alpha": gp.beta, "mu_at_sample": mu, "var_at_sample": var})
 
 
 def gather_rank_stats(vals, dev, world):
@@ -287,10 +335,11 @@ def run_model_update_sharded(args, dev, world, rank):
     elapsed = float(stats[:, 1].max())
     idx = np.random.default_rng(0).choice(N, min(N, 1024), replace=False)
     s2n = prob["noise_var"] + 1e-5 + 1e-8
-    mu, _ = gp.predict(prob["Z"][idx])
+    mu, var = gp.predict(prob["Z"][idx])
     res_mu = float(np.abs(mu + s2n[None, :] * gp.beta[idx] - prob["Y"][idx]).max())
     assert res_mu < 1e-7, "posterior identity violated on rank %d: %g" % (rank, res_mu)
     if rank == 0:
+        dumped = dump_update_outputs(args, gp, idx, mu, var)
         flops = n_s * (2.0 / 3.0) * float(N) ** 3
         per = elapsed / args.steps
         owners = min(world, n_s)
@@ -313,6 +362,8 @@ def run_model_update_sharded(args, dev, world, rank):
                          "frac": flops / per / 1e12 / owners / FP64_MFMA_PEAK_TFLOPS, "traffic": None,
                          "note": "per factorising GPU (%d of the %d ranks own an output), the broadcast inside the time" % (owners, world)},
         }
+        if dumped is not None:
+            line["dump_outputs"] = dumped
         print(json.dumps(line), flush=True)
     dist.barrier()
     dist.destroy_process_group()
@@ -363,6 +414,7 @@ def run_model_update(args, dev, world, rank):
     res_mu = float(np.abs(mu + s2n[None, :] * gp.beta[idx] - prob["Y"][idx]).max())
     assert res_mu < 1e-7, "posterior identity violated: %g" % res_mu
     if rank == 0:
+        dumped = dump_update_outputs(args, gp, idx, mu, var)
         flops = n_s * (2.0 / 3.0) * float(N) ** 3
         per = elapsed / args.steps
         ms = {k: gp.prof_get(i) for k, i in (("sr_gram_kernel", _lib.K_GRAM), ("sr_potrf_diag_kernel", _lib.K_POTRF),
@@ -390,6 +442,8 @@ def run_model_update(args, dev, world, rank):
             "kernel_launches_per_step": {k: v[1] / prof_steps for k, v in ms.items()},
             "gemm_TFLOPs_over_gemm_ms": flops / max(gemm_ms / prof_steps, 1e-9) / 1e9,
         }
+        if dumped is not None:
+            line["dump_outputs"] = dumped
         if world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline_update(n_s, n_u, N)
         print(json.dumps(line), flush=True)
@@ -540,6 +594,10 @@ def run(args):
         assert bool(torch.isfinite(out[1][:, :8]).all()), "non-finite result before the chain can overflow"
     else:
         assert bool(torch.isfinite(out[1]).all()), "non-finite result in the timed region"
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # what the batched entry point returned in the last timed step: p_new / q_new (one step), p_all / q_all (H steps)
+        dumped = dump_outputs(args.dump_outputs, dict(zip(("p_new", "q_new") if H == 1 else ("p_all", "q_all"), out)))
     if args.dump_shards:
         os.makedirs(args.dump_shards, exist_ok=True)
         head = min(T, 4096)
@@ -623,6 +681,8 @@ def run(args):
         }
         if dry is not None:
             line["config"]["dry_nccl"] = dry
+        if dumped is not None:
+            line["dump_outputs"] = dumped
         if overflow is not None:
             line["config"]["first_nonfinite_step"] = {"min": overflow[0], "median": overflow[1], "max": overflow[2],
                                                       "note": "0-based step of the chain at which a rollout's shape matrix first "

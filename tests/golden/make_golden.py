@@ -571,5 +571,34 @@ def main():
           d_safety=dd, dist=ue.distance_to_center(np.array([[0.2, 0.0]]), pe, np.real(qe)))
 
 
+def casadi_evaluator():
+    """9. The reference's own CasadiSSMEvaluator (state_space_models.py:214-566) driven over this package's
+    StateSpaceModel surface (the closed-form model of tests/test_host_logic.py) with the stand-in casadi module of
+    tests/standin, through JacFun.eval and BackFun.eval (:384-417, :534-562).  Runs in a process of its own
+    (``python tests/golden/make_golden.py casadi_evaluator``): it needs the stand-in, not the numeric shim of main()."""
+    sys.path[:0] = [os.path.join(ROOT, "tests", "standin"), os.path.join(ROOT, "tests"), REF, ROOT]
+    warnings.simplefilter("ignore")
+    import casadi
+    import test_host_logic as th
+    from safe_exploration.state_space_models import CasadiSSMEvaluator as RefEvaluator
+    Linear = th._linear_ssm()
+    ssm = Linear(2, 1, has_jacobian=True, has_reverse=True)
+    ev = RefEvaluator(ssm, True, ssm.has_jacobian, ssm.has_reverse)
+    bfun, stacked, (x, u, mu, var, jac) = th._drive_evaluator(ev, Linear, True)
+    # a reverse seed whose row- and column-major flattenings of the jac_mean part coincide (first column only): the
+    # reference flattens it column-major (:555-556) while its GPyTorchSSM caches jac_mean row-major
+    s_mu, s_var = np.array([[0.3], [-0.7]]), np.array([[1.1], [0.2]])
+    s_jac = np.zeros((2, 3))
+    ssm.linearize_predict(x.T, u.T, True)
+    adj_x, adj_u = bfun.eval([casadi.DM(a) for a in (x, u, mu, var, jac, s_mu, s_var, s_jac)])
+    _save("casadi_evaluator.npz", x=x, u=u, mu=np.array(mu), var=np.array(var), jac=np.array(jac), stacked=stacked,
+          s_mu=s_mu, s_var=s_var, s_jac=s_jac, adj_x=np.array(adj_x), adj_u=np.array(adj_u))
+
+
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["casadi_evaluator"]:
+        casadi_evaluator()
+    else:
+        main()
+        import subprocess
+        subprocess.run([sys.executable, os.path.abspath(__file__), "casadi_evaluator"], check=True)

@@ -4,7 +4,7 @@ the HIP model.
   * C5 per-GPU share at the HEADLINE model: N = 5000, 1 048 576 query states through 16 chunks of the bounded
     workspace (oracle sample + chunk-boundary identities),
   * C4: N = 50000 training points, the model update itself (posterior identities; no CPU oracle reaches it),
-  * two-rank RCCL: replicate_model over backend "nccl" + sharded one-step == single process (needs 2 GPUs),
+  * RCCL ranks: replicate_model over backend "nccl" + sharded one-step == single process (one rank per GPU, at most 4),
   * CasadiSSMEvaluator (forward / Jacobian / reverse callbacks) on the HIP SimpleGPModel against the oracle and
     finite differences.
 """
@@ -160,6 +160,7 @@ def _nccl_worker(rank, world, port, ret):
             ret["dq"] = float(np.abs(full_q - rq).max() / np.abs(rq).max())
             ret["backend"] = dist.get_backend()
             ret["world"] = dist.get_world_size()
+            ret["factor_bytes"] = parallel.LAST_REPLICATION["factor_bytes"]
         else:
             # the receiver holds a complete model: a later append works on consistent targets / noise
             gp.update_model(prob["Z"][:3] + 0.01, prob["Y"][:3], opt_hyp=False, replace_old=False, noise_diag=2e-5)
@@ -170,20 +171,23 @@ def _nccl_worker(rank, world, port, ret):
 
 
 def test_ranks_over_rccl():
-    """One rank per visible GPU (at most 8) over backend "nccl" (RCCL): rank 0 factorises on cuda:0, the others adopt
-    the model through the packed-triangle broadcast on their own device; the sharded one-step result equals the
-    single-process one.  Skipped on a one-GPU box (RCCL refuses two ranks on one device; the same code path runs
-    there over gloo: tests/test_gpu_distributed.py)."""
+    """One rank per visible GPU (at most 4, so that the ranks and this process stay within six processes with a GPU
+    open) over backend "nccl" (RCCL): rank 0 factorises on cuda:0, the others adopt the model through the packed-triangle
+    broadcast on their own device; the sharded one-step result equals the single-process one.  On a one-GPU box the group
+    has ONE rank (RCCL refuses two ranks on one device): the sender's half of the replication -- object and tensor
+    broadcasts, the packed triangle in pieces -- and the gather still go through RCCL; the receiver's half runs on one
+    device over gloo in tests/test_gpu_distributed.py."""
     import torch
     import torch.multiprocessing as mp
-    world = min(torch.cuda.device_count(), 8)
-    if world < 2:
-        pytest.skip("needs two GPUs (RCCL refuses two ranks on one device)")
+    world = min(torch.cuda.device_count(), 4)
+    assert world >= 1
     with mp.Manager() as mgr:
         ret = mgr.dict()
         mp.spawn(_nccl_worker, args=(world, _free_port(), ret), nprocs=world, join=True)
         assert ret["backend"] == "nccl" and ret["world"] == world
         assert ret["dp"] < 1e-13 and ret["dq"] < 1e-12
+        N, n_out = 1000, 2
+        assert ret["factor_bytes"] == n_out * N * (N + 1) // 2 * 8
 
 
 @pytest.mark.parametrize("kt,N,n_s,n_u", [("rbf", 200, 2, 1), ("rbf", 900, 4, 1), ("mat52", 700, 2, 1), ("lin_mat52", 150, 2, 1)])
@@ -194,7 +198,8 @@ def test_casadi_evaluator_callbacks_on_the_hip_model(kt, N, n_s, n_u, monkeypatc
     oracle's closed forms and with central differences of the forward callback; the reverse callback with seed^T J."""
     from safe_exploration_amd import SimpleGPModel
     monkeypatch.syspath_prepend(STANDIN)
-    monkeypatch.delitem(sys.modules, "casadi", raising=False)
+    monkeypatch.setitem(sys.modules, "casadi", None)      # what sys.modules held for casadi comes back after the
+    del sys.modules["casadi"]                            # test: the stand-in imported below does not outlive it
     import casadi  # noqa: F401  (the stand-in must be the module the evaluator finds)
     rng = np.random.default_rng(N + n_s)
     D = n_s + n_u
@@ -566,6 +571,27 @@ def test_bench_lines_are_self_consistent(argv, N, T, H, n_s):
     rk = line["roofline_kstar"]
     assert rk["bound"] == "hbm-write" and 0.2 < rk["frac"] < 1.0
     assert abs(rk["achieved"] * 1e9 * rk["avg_launch_ms"] * 1e-3 - rk["bytes_per_launch"]) <= 1e-6 * rk["bytes_per_launch"]
+
+
+def test_bench_dump_outputs_are_what_the_timed_path_returns(tmp_path):
+    """`bench.py --workload c2 --queries 8192 --steps 2 --dump-outputs DIR`: the line says how many steps were timed, and
+    DIR holds p_new / q_new of the last one in float64 -- the one-step result of the same seeded model and queries
+    evaluated here."""
+    line = _bench_line(["--workload", "c2", "--queries", "8192", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
+                        "--dump-outputs", str(tmp_path)])
+    assert line["steps"] == 2 and line["ms_per_step"] > 0
+    assert line["dump_outputs"]["files"] == ["p_new.npy", "q_new.npy"] and "sample" not in line["dump_outputs"]
+    p_new, q_new = np.load(str(tmp_path / "p_new.npy")), np.load(str(tmp_path / "q_new.npy"))
+    assert p_new.dtype == q_new.dtype == np.float64 and p_new.shape == (8192, 2) and q_new.shape == (8192, 2, 2)
+    from safe_exploration_amd import SimpleGPModel, gp_reachability as reach, workload
+    prob = workload.make_problem(2, 2000, 2, 1, 8192)
+    gp = SimpleGPModel(2, 2, 1, kern_types=["rbf"] * 2, hyp=workload.hyp_list(prob))
+    gp.train(prob["Z"], prob["Y"], opt_hyp=False)
+    l = np.array([0.05, 0.02])
+    rp, rq = reach.onestep_reachability_batch(prob["p"], gp, prob["k_ff"], l, l, prob["Q"], prob["k_fb"], 2.0,
+                                              np.eye(2), np.zeros((2, 1)))
+    np.testing.assert_allclose(p_new, rp, rtol=0, atol=1e-13)
+    np.testing.assert_allclose(q_new, rq, rtol=1e-12, atol=1e-16)
 
 
 def test_bench_model_update_line_is_self_consistent():

@@ -109,8 +109,16 @@ def test_simple_gp_model_surface(lib_built):
     kp = g._pack_kernel_params()
     assert kp.shape == (2, 12) and kp[0, 0] == 1.0 and kp[0, 2] == 1.0 and kp[1, 2] == 0.0
     assert kp[1, 3 + 1] == 1.0 and kp[1, 3 + 0] == 0.0 and kp[1, 3 + 3 + 1] == 1.0     # product part on dim 1
-    with pytest.raises(RuntimeError, match="no CPU fallback"):  # opt_hyp=True evaluates the likelihood on the GPU
-        gp.train(np.zeros((4, 3)), np.zeros((4, 2)))
+    import torch
+    if torch.cuda.is_available():
+        # opt_hyp=True evaluates the likelihood on the GPU: with one, the model trains (a model of its own: `gp` stays
+        # untrained for the checks below)
+        g_opt = SimpleGPModel(2, 2, 1)
+        g_opt.train(np.zeros((4, 3)), np.zeros((4, 2)))
+        assert g_opt.gp_trained
+    else:
+        with pytest.raises(RuntimeError, match="no CPU fallback"):  # ... and without one there is no CPU fallback
+            gp.train(np.zeros((4, 3)), np.zeros((4, 2)))
     assert gp._free_hyp(0) == [("lengthscale", 3), ("variance", 1), ("noise_variance", 1)]
     fixed = SimpleGPModel(2, 2, 1, hyp=[{"lengthscale": np.ones(3), "noise_variance": 0.1}] * 2)
     assert fixed._free_hyp(1) == [("variance", 1)]
@@ -316,7 +324,8 @@ def test_casadi_evaluator_contract_forward_jacobian_reverse(monkeypatch):
     of the model like state_space_models.py:166."""
     import sys
     monkeypatch.syspath_prepend(STANDIN)
-    monkeypatch.delitem(sys.modules, "casadi", raising=False)
+    monkeypatch.setitem(sys.modules, "casadi", None)      # what sys.modules held for casadi comes back after the
+    del sys.modules["casadi"]                            # test: the stand-in imported below does not outlive it
     import casadi
     Linear = _linear_ssm()
     ssm = Linear(2, 1, has_jacobian=True, has_reverse=True)
@@ -345,37 +354,35 @@ def test_casadi_evaluator_contract_forward_jacobian_reverse(monkeypatch):
     assert ssm_mod.CasadiSSMEvaluator is type(ev)
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/safe_exploration"),
-                    reason="needs the reference checkout (build container only)")
 def test_reference_casadi_evaluator_runs_on_this_surface(monkeypatch):
     """The REFERENCE's own CasadiSSMEvaluator (state_space_models.py:214-566) driven over this package's
     StateSpaceModel surface with the same stand-in casadi module, through JacFun.eval and BackFun.eval
-    (:384-417, :534-562): it must accept the surface unchanged and produce what this package's evaluator does."""
+    (:384-417, :534-562): it accepted the surface unchanged, and what it produced (tests/golden/casadi_evaluator.npz,
+    written by make_golden.py from the reference itself) is what this package's evaluator produces."""
     import sys
     monkeypatch.syspath_prepend(STANDIN)
-    monkeypatch.syspath_prepend("/root/reference")
-    for m in [k for k in sys.modules if k == "casadi" or k.startswith("safe_exploration.") or k == "safe_exploration"]:
-        monkeypatch.delitem(sys.modules, m)
+    monkeypatch.setitem(sys.modules, "casadi", None)      # what sys.modules held for casadi comes back after the
+    del sys.modules["casadi"]                            # test: the stand-in imported below does not outlive it
     import casadi
-    from safe_exploration.state_space_models import CasadiSSMEvaluator as RefEvaluator
+    g = load_golden("casadi_evaluator.npz")
+    x, u, mu, var, jac = (g[k] for k in ("x", "u", "mu", "var", "jac"))
     Linear = _linear_ssm()
     ssm = Linear(2, 1, has_jacobian=True, has_reverse=True)
-    ev = RefEvaluator(ssm, True, ssm.has_jacobian, ssm.has_reverse)
-    bfun, stacked, (x, u, mu, var, jac) = _drive_evaluator(ev, Linear, True)
     mine = ssm.get_forward_model_casadi(True)
+    for a, b in zip((mu, var, jac), mine.eval([x, u])):
+        np.testing.assert_allclose(np.array(b), a, rtol=1e-15, atol=0)
     mine.jac_mu_order = "C"                      # the reference helper's row order
     (stacked_mine,) = mine.get_jacobian("jac", [], [], {}).eval([x, u, mu, var, jac])
-    np.testing.assert_array_equal(stacked, np.array(stacked_mine))
+    np.testing.assert_array_equal(g["stacked"], np.array(stacked_mine))
     # reverse: the reference flattens the jac_mean seed with casadi's column-major reshape (:555-556) while its own
     # GPyTorchSSM caches jac_mean row-major (ssm_pytorch/gaussian_process.py:372); the two agree for a seed whose
-    # two flattenings coincide, e.g. one that only touches the first column
-    s_mu, s_var = np.array([[0.3], [-0.7]]), np.array([[1.1], [0.2]])
-    s_jac = np.zeros((2, 3))
+    # two flattenings coincide, e.g. one that only touches the first column (the stored s_jac)
+    s_mu, s_var, s_jac = g["s_mu"], g["s_var"], g["s_jac"]
+    assert not s_jac[:, 1:].any()
     ssm.linearize_predict(x.T, u.T, True)
-    adj_ref = bfun.eval([casadi.DM(a) for a in (x, u, mu, var, jac, s_mu, s_var, s_jac)])
     adj_mine = mine.get_reverse(1, "rev", [], [], {}).eval([casadi.DM(a) for a in (x, u, mu, var, jac, s_mu, s_var, s_jac)])
-    for a, b in zip(adj_ref, adj_mine):
-        np.testing.assert_allclose(np.array(a), np.array(b), rtol=1e-6)      # the reference casts its seed to float32
+    for a, b in zip((g["adj_x"], g["adj_u"]), adj_mine):
+        np.testing.assert_allclose(a, np.array(b), rtol=1e-6)      # the reference casts its seed to float32
 
 
 def test_dlqr_and_name_aliases_vs_reference_golden():
@@ -462,6 +469,42 @@ def test_bench_rank_section_and_single_rank_gather():
     assert bench.XGMI_LINK_GBS == 153.0
     args = bench.parse_args(["--workload", "c4", "--gpus", "2"])
     assert args.c4_replicas is False and bench.parse_args(["--c4-replicas"]).c4_replicas is True
+
+
+def test_bench_dump_outputs_writes_float64_within_the_cap(tmp_path, monkeypatch):
+    """bench.py --dump-outputs, host side: one float64 .npy per array; past the byte cap the arrays of the longest first
+    axis are cut to one fixed, seeded, ascending sample of rows (the same rows in every array and in every run), the
+    others stay whole; --steps below 1 is refused."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("_bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    assert bench.DUMP_MAX_BYTES == 64 << 20
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--steps", "0"])
+    assert bench.parse_args(["--dump-outputs", "d", "--steps", "3"]).dump_outputs == "d"
+    rng = np.random.default_rng(1)
+    p, q, small = rng.standard_normal((1000, 2)), rng.standard_normal((1000, 2, 2)), rng.standard_normal((7, 3))
+    info = bench.dump_outputs(str(tmp_path / "all"), {"p_new": p, "q_new": q.astype(np.float32), "small": small})
+    assert info["files"] == ["p_new.npy", "q_new.npy", "small.npy"] and "sample" not in info
+    for name, ref in (("p_new", p), ("q_new", q.astype(np.float32)), ("small", small)):
+        got = np.load(str(tmp_path / "all" / (name + ".npy")))
+        assert got.dtype == np.float64
+        np.testing.assert_array_equal(got, ref)
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 8 * (6 * 100 + 21))
+    cut = []
+    for run in ("a", "b"):
+        info = bench.dump_outputs(str(tmp_path / run), {"p_new": p, "q_new": q, "small": small})
+        assert info["sample"]["rows_kept"] == 100 and info["sample"]["rows_total"] == 1000
+        assert info["sample"]["arrays"] == ["p_new", "q_new"]
+        cut.append([np.load(str(tmp_path / run / (n + ".npy"))) for n in ("p_new", "q_new", "small")])
+        assert sum(a.nbytes for a in cut[-1]) <= bench.DUMP_MAX_BYTES
+    for a, b in zip(*cut):
+        np.testing.assert_array_equal(a, b)
+    rows = np.sort(np.random.default_rng(bench.DUMP_SAMPLE_SEED).choice(1000, 100, replace=False))
+    np.testing.assert_array_equal(cut[0][0], p[rows])
+    np.testing.assert_array_equal(cut[0][1], q[rows])
+    np.testing.assert_array_equal(cut[0][2], small)
 
 
 def _flow_tasks(nb, band, P, segs):
