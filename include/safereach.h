@@ -134,6 +134,19 @@ int sr_gp_inv_k(sr_gp_t h, int d, double* inv_k, void* stream);
 int sr_gp_predict(sr_gp_t h, const double* Xq, long T, double* mu, double* var, double* jac,
                   void* stream);
 
+/* ---- batched posterior with the gradient of the variance -----------------------------------------
+ * replaces: predict(states, actions, jacobians=True) for N > 1  state_space_models.py:74-104 (the reference's
+ *           backends loop or autograd per batch, ssm_pytorch/gaussian_process.py:280-292), and GPy's
+ *           predictive_gradients(x, grad_sigma=True)  (ssm_gpy/gaussian_process.py:570-596 raises there).
+ * Xq T x D -> mu T x n_out, var T x n_out (as sr_gp_predict), jac_mu T x n_out x D (may be NULL),
+ * jac_var T x n_out x D (d var/dx).  One tiled pass per chunk of sr_gp_set_chunk queries: the variance contraction
+ * also stores V = U^-T K*, a second triangular product G = U^-1 V = K_y^-1 K* is reduced on the fly against dk(Z, x)/dx.
+ * About twice the matrix-core work of sr_gp_predict.  All kernel identifiers, any n_out, D <= 8 (SR_EUNSUPPORTED beyond).
+ * Memory: a grow-only workspace of n_out x Np x chunk doubles (V, the size of the K* slab) and
+ * n_out x Np/128 x D x chunk doubles, owned by the handle and freed by sr_gp_release_scratch. */
+int sr_gp_predict_grad(sr_gp_t h, const double* Xq, long T, double* mu, double* var, double* jac_mu,
+                       double* jac_var, void* stream);
+
 /* ---- single query with second-order outputs (the CasADi Jacobian callback) ------------------------
  * replaces: linearize_predict(states 1xn, actions 1xm, jacobians=True)  state_space_models.py:106-138,
  *           consumed at :402-415; reference implementation ssm_pytorch/gaussian_process.py:333-385.

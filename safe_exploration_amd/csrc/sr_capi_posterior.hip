@@ -235,7 +235,7 @@ static int stream_linearize(sr_gp* h, const double* x, double* mu, double* var, 
 // and the model goes back to plain buffers first (unslide: a copy of the factor and a device-wide wait -- this call then
 // BLOCKS).  So that a loop of "one append, one big batch" does not pay that every step, the in-place route of the append
 // is held off for the next 64 one-point appends, twice as many after every further forced unslide (reset by a refit).
-static int tile_route_alignment(sr_gp* h) {
+int srh::tile_route_alignment(sr_gp* h) {
     if (!(h->slide & 1)) return SR_OK;
     SR_TRY(unslide(h));
     const int shift = std::min(h->slide_forced, 14);

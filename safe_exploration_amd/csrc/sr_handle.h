@@ -66,6 +66,9 @@ struct sr_gp {
     int* stream_tab = nullptr; long stream_tab_cap = 0; long stream_tab_key = -1; int stream_tab_kr = 0, stream_tab_n = 0, stream_tab_nwg = 0;   // work items of the run kernel (+ workgroups they are dealt to)
     double* stream_slots = nullptr; long stream_slots_cap = 0;    // self-validating hand-over slots of the T = 1 kernel's polling finaliser
     double* splitk_vt = nullptr; long splitk_cap = 0;   // partial products of the balanced few-query-tile route (grow-only)
+    // sr_gp_predict_grad (grow-only): V = U^-T K* of a chunk (n_out x Np x Tp) and the row blocks' partial sums of
+    // d var/dx (n_out x Np/128 x D x Tp); capacities in doubles
+    double* grad_v = nullptr; long grad_v_cap = 0; double* grad_part = nullptr; long grad_part_cap = 0;
     // log det(K + noise) per output as of the last <= 16-row append (read back with its status words): the blocking read of
     // sr_gp_logdet costs the exploration loop 30 us per step
     std::vector<double> logdet_host; int logdet_valid = 0;
@@ -203,6 +206,8 @@ struct sr_ws_lock {
 };
 int gp_pass(sr_gp* h, long Tc, const double* xa, long lda, int na, const double* xb, long ldb,
             int nb, double* mu, double* var, double* jac, hipStream_t s);
+// a tile route meets an odd slide of U^-1: back to plain buffers first (see sr_capi_posterior.hip)
+int tile_route_alignment(sr_gp* h);
 int gp_pass_states(sr_gp* h, long Tc, const double* p, long ldp, int n_s, const double* kff, long ldkff, int n_u,
                    double* mu, double* var, const double** jac_out, hipStream_t s);
 

@@ -283,6 +283,83 @@ __device__ __forceinline__ void mainloop_tn_pipe(const double* __restrict__ A, l
 #undef SRT_TILE
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// "NT" form: the A operand is read along its ROWS,
+//   acc[m][n] += sum_{k in [k_beg, k_end)} A[m][k] * B[k][n]      (A row-major: row m holds contiguous k; B k-major)
+// for the second triangular product of the predictive-variance gradient, G = U^-1 V, which contracts over the column
+// index of the stored U^-1 (sr_predict_grad.hip) -- without a transposed copy of the factor.
+// A k-tile of A is 128 rows x 16 doubles (128 B each): one LDS-DMA instruction moves 8 of them (lane l: row l >> 3,
+// 16-byte slot l & 7), wavefront w the 8-row groups w, w + 4, w + 8, w + 12.  The rows are 32 dwords apart in LDS, so a
+// plain layout puts the A fragment of a 16 x 16 x 4 step (lane l: row l & 15, k = 4 kk + (l >> 4)) on the same two banks
+// for every other row.  The DMA therefore SWIZZLES the slots: LDS slot s of row m holds the k-pair s ^ ((m >> 1) & 7)
+// (the permutation is applied to the global addresses each lane fetches; the 8 lanes of a row still read one contiguous
+// 128-byte segment).  In a 32-lane group of the fragment read (ds_read_b64: bank = (byte address / 4) % 64) the rows m
+// and m + 1 differ in bank half (32 m mod 64), the eight rows of one parity in slot (c ^ (m >> 1) & 7 for the common
+// k-pair c), the two k of a pair in the dword inside the slot: 32 distinct bank pairs, conflict-free.  B as in the TN
+// loops (BK rows of 128 doubles, padded to LDT).  Two stages, LDS-DMA for both operands, barrier on top of the k-tile
+// (the form of mainloop_tn_glds).  Contract as above: A points at A[m0][0], B at B[0][n0]; k range multiples of BK.
+// ------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ void mainloop_nt_glds(const double* __restrict__ A, long lda, const double* __restrict__ B,
+                                                 long ldb, int k_beg, int k_end, double* smem, Acc& acc) {
+    constexpr int STG = BK * LDT;              // doubles per operand per stage (A uses 128 x 16 = 2048 of them)
+    static_assert(BM * BK <= STG, "A tile must fit a stage");
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wm = wave >> 1, wn = wave & 1;
+    double* As = smem;
+    double* Bs = smem + 2 * STG;
+    if (k_beg >= k_end) return;
+    // DMA of A: lane -> (row r of its 8-row group, LDS slot s); the group's first row is a multiple of 8, so the swizzle of
+    // row 8 g + r is (4 g + (r >> 1)) & 7 = (4 wave + (r >> 1)) & 7 for all four groups of this wavefront
+    const int dr = lane >> 3, ds = lane & 7;
+    const int dsw = (4 * wave + (dr >> 1)) & 7;
+    const double* ga = A + (long)(8 * wave + dr) * lda + 2 * (ds ^ dsw);
+    const double* gb = B + (long)wave * ldb + 2 * lane;
+#define SRT_NT_DMA(k0, buf)                                                                          \
+    do {                                                                                             \
+        _Pragma("unroll") for (int j_ = 0; j_ < 4; ++j_) {                                           \
+            __builtin_amdgcn_global_load_lds(SRT_AS1(ga + (long)32 * j_ * lda + (k0)),               \
+                                             SRT_AS3(As + (buf) * STG + (wave + 4 * j_) * 128), 16, 0, 0); \
+            __builtin_amdgcn_global_load_lds(SRT_AS1(gb + (long)((k0) + 4 * j_) * ldb),              \
+                                             SRT_AS3(Bs + (buf) * STG + (wave + 4 * j_) * LDT), 16, 0, 0); \
+        }                                                                                            \
+    } while (0)
+    // A fragment of k-step kk: row wm*64 + i*16 + (lane & 15), k = 4 kk + lk -> slot (2 kk + (lk >> 1)) ^ swizzle(row)
+    const int lk = lane >> 4, ln = lane & 15;
+    const int fsw = ln >> 1;                   // (row >> 1) & 7: row tiles start at multiples of 16
+    int fa[4];
+#pragma unroll
+    for (int kk = 0; kk < 4; ++kk) fa[kk] = (wm * 64 + ln) * 16 + 2 * ((2 * kk + (lk >> 1)) ^ fsw) + (lk & 1);
+    const int fb = lk * LDT + wn * 64 + ln;
+
+    SRT_NT_DMA(k_beg, 0);
+    int buf = 0;
+    for (int k0 = k_beg; k0 < k_end; k0 += BK) {
+        __syncthreads();                       // vmcnt(0) + s_barrier: tile k0 landed, other stage is free
+        if (k0 + BK < k_end) SRT_NT_DMA(k0 + BK, buf ^ 1);
+        const double* as = As + buf * STG;
+        const double* bs = Bs + buf * STG + fb;
+#pragma unroll
+        for (int kk = 0; kk < BK / 4; ++kk) {
+            double af[4], bf[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                af[i] = as[fa[kk] + i * 16 * 16];
+                bf[i] = bs[kk * 4 * LDT + i * 16];
+            }
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    acc.v[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[i], bf[j], acc.v[i][j], 0, 0, 0);
+        }
+        buf ^= 1;
+    }
+    __syncthreads();                           // callers reuse smem after the main loop
+#undef SRT_NT_DMA
+}
+
 // Round 3, measured and NOT kept (scripts/mfma_lds_tile.hip, profiles/archive/r03_mfma_lds_tile.txt): where the 9 % between this
 // loop (70.5 TF inside sr_var_kernel) and the matrix pipe (77.5 TF) go.  An LDS-fed loop of the same fragment reads and
 // MFMAs runs at 77.0 - 77.7 TF for EVERY wavefront tile from 32 x 32 to 96 x 64 at two wavefronts per SIMD: the LDS -> VGPR

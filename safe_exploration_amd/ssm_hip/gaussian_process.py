@@ -844,11 +844,49 @@ class SimpleGPModel(StateSpaceModel):
         return self.predict_device(x_new, bool(compute_gradients))
 
     def predictive_gradients(self, x_new, grad_sigma=False):
-        """(T, n_s, D) gradients of the predictive mean (gaussian_process.py:570-596)."""
+        """(T, n_s, D) gradients of the predictive mean (gaussian_process.py:570-596).  With ``grad_sigma=True``
+        (the reference raises there; GPy returns it) the pair (grad_mu, grad_var), each (T, n_s, D), through the
+        batched gradient pass.  NumPy or tensors like the input."""
         if grad_sigma:
-            raise NotImplementedError("Gradient of sigma not implemented")
+            if B.is_tensor(x_new):
+                return self.predict_device_grad(x_new)[2:]
+            return self._predict_grad_host(x_new)[2:]
         out = self.predict_device(x_new, True)[2]
         return out if B.is_tensor(x_new) else B.to_numpy(out)
+
+    def predict_device_grad(self, x_new):
+        """Batched posterior with both gradients on device tensors, no host synchronisation (sr_gp_predict_grad):
+        x_new (T, D) -> mu (T,n), var (T,n), jac_mu (T,n,D), jac_var (T,n,D) = d var / dx."""
+        self._need_trained()
+        hd = self._handle
+        x = B.as_dev(x_new, hd.device)
+        if x.dim() != 2 or x.shape[1] != hd.D:
+            raise ValueError("x_new must be (T, {})".format(hd.D))
+        T = x.shape[0]
+        mu, var = B.empty((T, hd.n_out), hd.device), B.empty((T, hd.n_out), hd.device)
+        jm, jv = B.empty((T, hd.n_out, hd.D), hd.device), B.empty((T, hd.n_out, hd.D), hd.device)
+        check(lib.sr_gp_predict_grad(hd.h, B.ptr(x), T, B.ptr(mu), B.ptr(var), B.ptr(jm), B.ptr(jv),
+                                     B.stream_ptr(hd.device)))
+        return mu, var, jm, jv
+
+    def _predict_grad_host(self, x_new):
+        """predict_device_grad for a NumPy batch through one staging round trip (as _predict_host)."""
+        self._need_trained()
+        hd = self._handle
+        x = np.ascontiguousarray(np.asarray(x_new, dtype=np.float64))
+        if x.ndim != 2 or x.shape[1] != hd.D:
+            raise ValueError("x_new must be (T, {})".format(hd.D))
+        T = x.shape[0]
+        if T == 0 or T * hd.n_out * (2 + 2 * hd.D) > B.STAGING_MAX_DOUBLES:
+            return tuple(B.to_numpy(o) for o in self.predict_device_grad(x))
+        st = getattr(hd, "_staging", None)
+        if st is None:
+            st = hd._staging = B.Staging(hd.device)
+        shapes = [(T, hd.n_out), (T, hd.n_out), (T, hd.n_out, hd.D), (T, hd.n_out, hd.D)]
+        (dx,), outs = st.stage([x], shapes, zero_copy=True)
+        check(lib.sr_gp_predict_grad(hd.h, B.ptr(dx), T, B.ptr(outs[0]), B.ptr(outs[1]), B.ptr(outs[2]),
+                                     B.ptr(outs[3]), B.stream_ptr(hd.device)))
+        return tuple(st.fetch())
 
     def __call__(self, states, actions):
         """Single-query evaluation used by onestep_reachability (gaussian_process.py:135-144):
@@ -939,20 +977,39 @@ class SimpleGPModel(StateSpaceModel):
         o = hd.fetch(io["d_out"].numel(), stream)
         return o[:n], o[n:a], o[a:b].reshape(n, D), o[b:c].reshape(n, D), o[c:].reshape(n, D, D)
 
+    # from this many queries on predict(states, actions, jacobians=True) takes the batched gradient pass instead of the
+    # single-query linearisation per row (inputs of up to GRAD_MAX_D dimensions: the pass's compiled range)
+    GRAD_BATCH_MIN = 2
+    GRAD_MAX_D = 8
+
     def predict_with_jacobians(self, states, actions):
         """Base-class ``predict(states, actions, jacobians=True)`` (state_space_models.py:74-104):
-        (mean (N,n), var (N,n), jac_mean (N,n,D), jac_var (N,n,D)).  d var/dx needs K_y^-1 k* per
-        query, so this is the latency path looped over the N queries."""
-        x = np.hstack((np.asarray(states, dtype=np.float64), np.asarray(actions, dtype=np.float64)))
+        (mean (N,n), var (N,n), jac_mean (N,n,D), jac_var (N,n,D)).  One query: the single-query latency path
+        (cached for ``get_reverse``); a batch: one batched gradient pass (sr_gp_predict_grad).  Torch device tensors
+        in give device tensors out."""
+        batched = self._handle is not None and self._handle.D <= self.GRAD_MAX_D
+        if B.is_tensor(states):
+            x = torch.cat((states, actions), dim=1)
+            if batched and x.shape[0] >= self.GRAD_BATCH_MIN:
+                return self.predict_device_grad(x)
+            x = x.detach().cpu().numpy()
+            as_t = True
+        else:
+            x = np.hstack((np.asarray(states, dtype=np.float64), np.asarray(actions, dtype=np.float64)))
+            as_t = False
         N = x.shape[0]
         hd = self._handle
         self._need_trained()
+        if batched and N >= self.GRAD_BATCH_MIN:
+            return self._predict_grad_host(x)
         mean, var = np.empty((N, hd.n_out)), np.empty((N, hd.n_out))
         jm, jv = np.empty((N, hd.n_out, hd.D)), np.empty((N, hd.n_out, hd.D))
         for t in range(N):
             mean[t], var[t], jm[t], jv[t], _ = self._linearize_host(x[t])
         if N == 1:
             self._forward_cache = (jm[0], jv[0])
+        if as_t:
+            return tuple(B.as_dev(o, hd.device) for o in (mean, var, jm, jv))
         return mean, var, jm, jv
 
     def get_reverse(self, seed):
