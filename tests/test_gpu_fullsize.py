@@ -612,13 +612,15 @@ def test_no_access_past_a_buffer_under_guard_allocation():
     past a buffer leaves the mapping and kills the process instead of landing silently in a neighbour.  (That is how the
     four-rows-past-U^-1 read of the 16-wavefront streaming kernels showed itself -- odd padded sizes, last output.)  With
     SR_POISON=1 the new buffers also hold NaN patterns instead of zeros (the block cache hands out used memory as it is).
-    The shape-heavy parity tests run in a child process under that mode and must pass."""
+    The shape-heavy parity tests and the width matrix of test_gpu_widths.py (padded columns D < DT: an unmasked read of
+    one shows up as NaN) run in a child process under that mode and must pass."""
     import subprocess
     env = dict(os.environ, SR_GUARD="1", SR_POISON="1")     # ... and new buffers hold NaN patterns, not zeros
     sel = ("fused_small_model_linearize or ragged or small_batch_streaming or splitk or all_state_action or "
            "row_append or streamed_linearize or fused_small_model_pass or persistent_chain_matches or "
-           "resident_server_answers or one_point_append")
-    r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_gpu_parity.py"), "-q", "-x", "-m", "gpu",
+           "resident_server_answers or one_point_append or test_gpu_widths")
+    r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_gpu_parity.py"),
+                        os.path.join(ROOT, "tests", "test_gpu_widths.py"), "-q", "-x", "-m", "gpu",
                         "-k", sel, "-p", "no:cacheprovider"], env=env, capture_output=True, text=True, timeout=900)
     tail = (r.stdout + r.stderr)[-1500:]
     assert r.returncode == 0, tail
