@@ -147,6 +147,19 @@ int sr_gp_predict(sr_gp_t h, const double* Xq, long T, double* mu, double* var, 
 int sr_gp_predict_grad(sr_gp_t h, const double* Xq, long T, double* mu, double* var, double* jac_mu,
                        double* jac_var, void* stream);
 
+/* ---- batched second-order linearisation: the Hessian of the mean for a batch of queries ----------------
+ * replaces: a loop of linearize_predict(states 1xn, actions 1xm, jacobians=True) over the rows of a batch
+ *           (state_space_models.py:106-138; ssm_pytorch/gaussian_process.py:333-385 builds the Hessian per output by autograd).
+ * Xq T x D -> mu, var (T x n_out), jac_mu, jac_var (T x n_out x D): bit-identical to sr_gp_predict_grad on the same
+ * inputs; hess_mu (T x n_out x D x D), exactly symmetric.  Per chunk of sr_gp_set_chunk queries the pass of
+ * sr_gp_predict_grad, then one pass over the chunk's K* slab (ARD-RBF) or over Z (the general family) that sums
+ * alpha_i d2 k(x_t, z_i)/dx2 in centred coordinates z_i - x_t.  All kernel identifiers, any n_out, D <= 8
+ * (SR_EUNSUPPORTED beyond: sr_gp_linearize serves one query of any D).  No pointer may be NULL (T = 0 excepted).
+ * Memory: the workspace of sr_gp_predict_grad and a grow-only n_split x n_out x (D (D + 1) / 2 + 1) x chunk doubles of
+ * partial sums, owned by the handle and freed by sr_gp_release_scratch. */
+int sr_gp_linearize_batch(sr_gp_t h, const double* Xq, long T, double* mu, double* var,
+                          double* jac_mu, double* jac_var, double* hess_mu, void* stream);
+
 /* ---- single query with second-order outputs (the CasADi Jacobian callback) ------------------------
  * replaces: linearize_predict(states 1xn, actions 1xm, jacobians=True)  state_space_models.py:106-138,
  *           consumed at :402-415; reference implementation ssm_pytorch/gaussian_process.py:333-385.

@@ -331,6 +331,10 @@ int sr_launch_var_bal(const double* Wt, const double* Ks, double* Vt, double* pa
 //                                            results + flag by the final stage's workgroup): N = 1000 32 -> 26 us (r04_call_latency)
 //  second order of one query (sr_gp_linearize)  K0 LIN up to Np = 384 (18 us at N = 200), streamed above: one launch for D <= 3
 //                                            (SR_LIN_FUSED_MAX_D): N = 5000 61 -> 51 us (r02_latency_grid)
+//  Hessian of the mean of a batch            KH sr_hess_kernel (sr_predict_grad.hip, behind the gradient pass): one thread per
+//   (sr_gp_linearize_batch)                  (query, output), the training rows split until the grid holds SR_HESS_WGS workgroups,
+//                                            at least SR_HESS_MIN_ROWS rows per split (T = 2 at N = 5000: 157 splits; T = 65536: 2);
+//                                            sizes set from the K* pass's 768-workgroup target, not swept (profiles/r08_linearize_batch.txt)
 //  multi-step chains (sr_capi_reach.hip)     persistent kernel K0c up to SR_CHAIN_GROUPS workgroups (device CUs - 16 at most),
 //                                            1 launch for H <= 2, <= 2 launches for T <= 1024, <= 6 beyond (N = 200 H = 15: 1024
 //                                            rollouts 203 against 253 us, 4096 in six launches 608 / 722, r03_chain_bench); one-step
@@ -365,6 +369,15 @@ static inline int sr_flow_panel(int nb) { return nb <= 12 ? 2 : (nb <= 28 ? 3 : 
 #define SR_APPEND1G_MAX_W 128        /* workgroups per output of that grid */
 #define SR_SLIDE_STEPS SR_NB         /* in-place one-point appends a set of model buffers can take: zeroed slack behind U^-1 (SR_SLIDE_STEPS (Np + 1) doubles), alpha and yT (SR_SLIDE_STEPS each) */
 #define SR_STREAM_FUSED32_MAX_NCB 8   // 32 columns per workgroup are evaluated inside the MFMA kernel up to this many 256-column blocks (Np <= 2048)
+#define SR_HESS_WGS 1024             /* Hessian-of-the-mean pass: workgroups the row splits aim at ... */
+#define SR_HESS_MIN_ROWS 32          /* ... with at least this many training rows per split */
+static inline int sr_hess_nsplit(int N, int n_out, long Tp) {
+    const long blocks = ((Tp + 255) / 256) * n_out;
+    long ns = (SR_HESS_WGS + blocks - 1) / blocks;
+    const long cap = ((long)N + SR_HESS_MIN_ROWS - 1) / SR_HESS_MIN_ROWS;
+    if (ns > cap) ns = cap;
+    return ns < 1 ? 1 : (int)ns;
+}
 
 static inline bool sr_gp_small_wanted(int Np, long T, int D, bool general) {
     (void)general;   // ARD-RBF and the general family both have a one-launch kernel

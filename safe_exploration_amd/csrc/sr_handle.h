@@ -69,6 +69,9 @@ struct sr_gp {
     // sr_gp_predict_grad (grow-only): V = U^-T K* of a chunk (n_out x Np x Tp) and the row blocks' partial sums of
     // d var/dx (n_out x Np/128 x D x Tp); capacities in doubles
     double* grad_v = nullptr; long grad_v_cap = 0; double* grad_part = nullptr; long grad_part_cap = 0;
+    // sr_gp_linearize_batch (grow-only): the training-row splits' partial sums of the Hessian of the mean
+    // (n_split x n_out x (D (D + 1) / 2 + 1) x Tp); capacity in doubles
+    double* hess_part = nullptr; long hess_part_cap = 0;
     // log det(K + noise) per output as of the last <= 16-row append (read back with its status words): the blocking read of
     // sr_gp_logdet costs the exploration loop 30 us per step
     std::vector<double> logdet_host; int logdet_valid = 0;

@@ -13,6 +13,7 @@
 // c = c0 + sum a_j x_j z_ij, g = kappa'(r)/r; dk(x,x)/dx_j = 2 (a_j v + b_j) x_j  (the closed forms of
 // sr_linearize_general_kernel, there for one query).
 // mu, var and d mu/dx come from the K* pass and sr_finalize exactly as in sr_gp_predict.
+// sr_gp_linearize_batch (below) adds the Hessian of the mean behind that pass: KH / KHF.
 #include "sr_handle.h"
 using namespace srh;
 
@@ -352,6 +353,240 @@ extern "C" int sr_gp_predict_grad(sr_gp_t h, const double* Xq, long T, double* m
         const long Tc = std::min(h->chunk, T - t0);
         SR_TRY(grad_pass(h, Tc, Xq + t0 * h->D, mu + t0 * h->n_out, var + t0 * h->n_out,
                          jac_mu ? jac_mu + t0 * h->n_out * h->D : nullptr, jac_var + t0 * h->n_out * h->D, s));
+    }
+    return SR_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// sr_gp_linearize_batch: the pass of sr_gp_predict_grad, then the Hessian of the mean for every query of the chunk.
+//   KH  sr_hess_kernel        : per output d and query t, over the training rows i of one split (blockIdx.z)
+//         RBF      H_jc = sum_i alpha_i k_ti (z_ij - x_j)(z_ic - x_c) / (l_j^2 l_c^2)  [- delta_jc / l_j^2 sum_i alpha_i k_ti]
+//                  k_ti read from the chunk's K* slab (the K* pass of grad_pass left it there);
+//         general  H_jl = sum_i alpha_i [v g (a_j z_j u_l + a_l z_l u_j) + c v (h u_j u_l + g s_j^2 delta_jl)]
+//                  (the closed form of sr_linearize_general_kernel, sr_linearize.hip; kappa, g and h recomputed per pair).
+//       Summed in centred coordinates z_i - x_t: the expanded form W^T [1 | Z | Z Z^T] would be one matrix product, but it
+//       cancels terms of size |x|^2 sum |alpha k| down to the result and loses the digits the fp64 bars need.
+//       One thread per (query, output); Z rows and alpha staged through LDS (broadcast reads); the upper triangle of the
+//       D x D block (plus sum_i alpha_i k_ti for RBF) -> hpart[split][d][q][t]                           [HBM / VALU bound]
+//   KHF sr_hess_finish_kernel : the splits in ascending order (deterministic), the diagonal term, both halves of the triangle
+//       written from the one value (exactly symmetric)
+// ------------------------------------------------------------------------------------------------
+#define SR_HZT 256
+struct sr_hess_args {
+    const double* Ks; const double* Z; const double* alpha; const double* ls; const double* kp; const double* Xq;
+    double* hpart;                             // nsplit x n_out x nhp x Tp
+    int N, Np, D, n_out, nsplit, nhp;          // nhp: D (D + 1) / 2 triangle entries (+ 1 for sum alpha k, RBF)
+    long T, Tp;
+};
+
+// entry q of the D-wide upper triangle, row by row: (0,0) (0,1) .. (0,D-1) (1,1) ..
+__host__ __device__ static inline int sr_tri_index(int j, int c, int D) { return j * D - j * (j - 1) / 2 + (c - j); }
+
+template <int DT, bool GEN>
+__global__ __launch_bounds__(256) void sr_hess_kernel(sr_hess_args a) {
+    constexpr int NH = DT * (DT + 1) / 2;
+    __shared__ double zs[SR_HZT * DT];
+    __shared__ double al[SR_HZT];
+    const int d = blockIdx.y, sp = blockIdx.z;
+    const long t = (long)blockIdx.x * 256 + threadIdx.x;
+    const bool live = t < a.T;
+    const int D = a.D, off = a.Np - a.N;
+    double x[DT], sc[DT], av[DT], acc[NH], sw = 0.0;     // sc: 1 / l_j^2 (RBF) or s_j^2 (general)
+    int kind = 0;
+    double vv = 0.0, c0 = 0.0;
+    const double* kp = GEN ? a.kp + (long)d * SR_KP(D) : nullptr;
+    if (GEN) { kind = (int)kp[0]; vv = kp[1]; c0 = kp[2]; }
+#pragma unroll
+    for (int j = 0; j < DT; ++j) {
+        x[j] = (live && j < D) ? a.Xq[t * D + j] : 0.0;
+        if (GEN) {
+            const double sj = (j < D) ? kp[3 + j] : 0.0;
+            sc[j] = sj * sj;
+            av[j] = (j < D) ? kp[3 + D + j] : 0.0;
+        } else {
+            const double l = (j < D) ? a.ls[d * D + j] : 1.0;
+            sc[j] = (j < D) ? 1.0 / (l * l) : 0.0;
+            av[j] = 0.0;
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < NH; ++q) acc[q] = 0.0;
+    // real training rows only: row i of Z is row i + off of K* and alpha (front padding)
+    const int rows_per = (a.N + a.nsplit - 1) / a.nsplit;
+    const int i_beg = sp * rows_per;
+    const int i_end = min(a.N, i_beg + rows_per);
+    const double* ks = GEN ? nullptr : a.Ks + ((long)d * a.Np + off) * a.Tp + (live ? t : 0);
+    for (int i0 = i_beg; i0 < i_end; i0 += SR_HZT) {
+        const int nrow = min(SR_HZT, i_end - i0);
+        __syncthreads();
+        if (threadIdx.x < nrow) {
+            const int r = threadIdx.x;
+#pragma unroll
+            for (int j = 0; j < DT; ++j) zs[r * DT + j] = (j < D) ? a.Z[(long)(i0 + r) * D + j] : 0.0;
+            al[r] = a.alpha[(long)d * a.Np + off + i0 + r];
+        }
+        __syncthreads();
+        if (!live) continue;
+        if (!GEN) {
+#pragma unroll 4
+            for (int r = 0; r < nrow; ++r) {
+                const double w = al[r] * ks[(long)(i0 + r) * a.Tp];
+                double df[DT];
+#pragma unroll
+                for (int j = 0; j < DT; ++j) df[j] = (zs[r * DT + j] - x[j]) * sc[j];
+                sw += w;
+                int q = 0;
+#pragma unroll
+                for (int j = 0; j < DT; ++j) {
+                    const double wd = w * df[j];
+#pragma unroll
+                    for (int c = j; c < DT; ++c) { acc[q] = fma(wd, df[c], acc[q]); ++q; }
+                }
+            }
+        } else {
+            for (int r = 0; r < nrow; ++r) {
+                double z[DT], u[DT], r2 = 0.0, la = 0.0;
+#pragma unroll
+                for (int j = 0; j < DT; ++j) {
+                    z[j] = zs[r * DT + j];
+                    const double df = x[j] - z[j];
+                    u[j] = sc[j] * df;
+                    r2 = fma(u[j], df, r2);
+                    la = fma(av[j] * x[j], z[j], la);
+                }
+                double g, h;                      // kappa'(r)/r and g'(r)/r (kappa itself is not needed)
+                if (kind == 0) {
+                    h = exp(-0.5 * r2);
+                    g = -h;
+                } else {
+                    const double rr = sqrt(r2);
+                    const double e = exp(-2.23606797749978969641 * rr);
+                    g = -(5.0 / 3.0) * (1.0 + 2.23606797749978969641 * rr) * e;
+                    h = (25.0 / 3.0) * e;
+                }
+                const double pre = (c0 + la) * vv;
+                const double w = al[r];
+                const double vg = vv * g, pg = pre * g, ph = pre * h;
+                int q = 0;
+#pragma unroll
+                for (int j = 0; j < DT; ++j) {
+                    const double azj = av[j] * z[j];
+#pragma unroll
+                    for (int c = j; c < DT; ++c) {
+                        double hv = fma(vg, fma(azj, u[c], av[c] * z[c] * u[j]), ph * u[j] * u[c]);
+                        if (c == j) hv = fma(pg, sc[j], hv);
+                        acc[q] = fma(w, hv, acc[q]);
+                        ++q;
+                    }
+                }
+            }
+        }
+    }
+    if (!live) return;
+    double* hp = a.hpart + ((long)sp * a.n_out + d) * a.nhp * a.Tp + t;
+    int q = 0;
+#pragma unroll
+    for (int j = 0; j < DT; ++j)
+#pragma unroll
+        for (int c = j; c < DT; ++c) {
+            if (c < D) hp[(long)sr_tri_index(j, c, D) * a.Tp] = acc[q];
+            ++q;
+        }
+    if (!GEN) hp[(long)(a.nhp - 1) * a.Tp] = sw;
+}
+
+// KHF: one thread per (query, output, triangle entry), queries fastest (the partials are read along t)
+__global__ __launch_bounds__(256) void sr_hess_finish_kernel(const double* __restrict__ hpart, const double* __restrict__ ls,
+                                                             double* __restrict__ hess, int gen, int n_out, int D,
+                                                             int nsplit, int nhp, long T, long Tp) {
+    const int nhd = D * (D + 1) / 2;
+    const long e = (long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= T * n_out * nhd) return;
+    const long t = e % T;
+    const int q = (int)((e / T) % nhd), d = (int)(e / (T * nhd));
+    int j = 0, c = q;
+    while (c >= D - j) { c -= D - j; ++j; }
+    c += j;
+    const long stride = (long)n_out * nhp * Tp;
+    const double* p = hpart + (long)d * nhp * Tp + t;
+    const bool diag = !gen && c == j;                   // RBF diagonal: sum_i alpha_i k_ti as well
+    double s = 0.0, sw = 0.0;
+    // (unrolled: the loads of several splits in flight -- a small batch has up to N / SR_HESS_MIN_ROWS splits)
+#pragma unroll 8
+    for (int sp = 0; sp < nsplit; ++sp) {
+        s += p[sp * stride + (long)q * Tp];
+        if (diag) sw += p[sp * stride + (long)(nhp - 1) * Tp];
+    }
+    if (diag) {
+        const double l = ls[d * D + j];
+        s -= sw * (1.0 / (l * l));
+    }
+    double* hm = hess + (t * n_out + d) * (long)D * D;
+    hm[j * D + c] = s;
+    hm[c * D + j] = s;
+}
+
+// grow-only workspace of the Hessian pass: the splits' partial sums
+static int hess_buffers(sr_gp* h, long need, hipStream_t s) {
+    if (need > h->hess_part_cap) {
+        (void)hipStreamSynchronize(s);
+        dev_free(h->hess_part);
+        h->hess_part = nullptr; h->hess_part_cap = 0;
+        SR_TRY(dev_alloc(&h->hess_part, (size_t)need));
+        h->hess_part_cap = need;
+    }
+    return SR_OK;
+}
+
+// one chunk after grad_pass: reads the chunk's K* slab (RBF) before the next chunk's K* pass overwrites it
+static int hess_pass(sr_gp* h, long Tc, const double* Xq, double* hess_mu, hipStream_t s) {
+    const long Tp = round_up(Tc, srt::BN);              // the K* slab's row stride, as in grad_pass
+    const int nsplit = sr_hess_nsplit(h->N, h->n_out, Tp);
+    const int nhd = h->D * (h->D + 1) / 2;
+    const int nhp = nhd + (h->general ? 0 : 1);
+    SR_TRY(hess_buffers(h, (long)nsplit * h->n_out * nhp * Tp, s));
+    sr_hess_args a;
+    a.Ks = h->Ks; a.Z = h->Z; a.alpha = h->alpha; a.ls = h->ls; a.kp = h->general ? h->kp : nullptr; a.Xq = Xq;
+    a.hpart = h->hess_part;
+    a.N = h->N; a.Np = h->Np; a.D = h->D; a.n_out = h->n_out; a.nsplit = nsplit; a.nhp = nhp; a.T = Tc; a.Tp = Tp;
+    const dim3 grid((unsigned)((Tp + 255) / 256), h->n_out, nsplit);
+#define SR_HESS_CASE(DT)                                                                                  \
+    do {                                                                                                 \
+        if (h->general) hipLaunchKernelGGL((sr_hess_kernel<DT, true>), grid, dim3(256), 0, s, a);         \
+        else hipLaunchKernelGGL((sr_hess_kernel<DT, false>), grid, dim3(256), 0, s, a);                   \
+    } while (0)
+    if (h->D <= 3) SR_HESS_CASE(3);
+    else if (h->D <= 5) SR_HESS_CASE(5);
+    else if (h->D <= 8) SR_HESS_CASE(8);
+    else { sr_set_error("linearize_batch: D=%d > %d", h->D, SR_GRAD_MAX_D); return SR_EUNSUPPORTED; }
+#undef SR_HESS_CASE
+    SR_HIP(hipGetLastError());
+    const long n = Tc * h->n_out * nhd;
+    hipLaunchKernelGGL(sr_hess_finish_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, h->hess_part, h->ls,
+                       hess_mu, h->general, h->n_out, h->D, nsplit, nhp, Tc, Tp);
+    SR_HIP(hipGetLastError());
+    return SR_OK;
+}
+
+extern "C" int sr_gp_linearize_batch(sr_gp_t h, const double* Xq, long T, double* mu, double* var, double* jac_mu,
+                                     double* jac_var, double* hess_mu, void* stream) {
+    SR_CHECK(h != nullptr, SR_EINVAL, "sr_gp_linearize_batch: NULL handle");
+    SR_CHECK(h->factorized, SR_ESTATE, "sr_gp_linearize_batch: model not factorized");
+    SR_CHECK(T >= 0, SR_EINVAL, "sr_gp_linearize_batch: T=%ld", T);
+    if (T == 0) return SR_OK;
+    SR_CHECK(Xq && mu && var && jac_mu && jac_var && hess_mu, SR_EINVAL, "sr_gp_linearize_batch: NULL argument");
+    if (h->D > SR_GRAD_MAX_D) {
+        sr_set_error("sr_gp_linearize_batch: D=%d > %d (sr_gp_linearize serves one query of any D)", h->D, SR_GRAD_MAX_D);
+        return SR_EUNSUPPORTED;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    SR_DEVICE(h->device);
+    const long nd = (long)h->n_out * h->D;
+    for (long t0 = 0; t0 < T; t0 += h->chunk) {
+        const long Tc = std::min(h->chunk, T - t0);
+        SR_TRY(grad_pass(h, Tc, Xq + t0 * h->D, mu + t0 * h->n_out, var + t0 * h->n_out, jac_mu + t0 * nd,
+                         jac_var + t0 * nd, s));
+        SR_TRY(hess_pass(h, Tc, Xq + t0 * h->D, hess_mu + t0 * nd * h->D, s));
     }
     return SR_OK;
 }

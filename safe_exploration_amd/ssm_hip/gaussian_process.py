@@ -977,6 +977,72 @@ class SimpleGPModel(StateSpaceModel):
         o = hd.fetch(io["d_out"].numel(), stream)
         return o[:n], o[n:a], o[a:b].reshape(n, D), o[b:c].reshape(n, D), o[c:].reshape(n, D, D)
 
+    def linearize_device_batch(self, x_new):
+        """Second-order outputs for a batch on device tensors, no host synchronisation (sr_gp_linearize_batch):
+        x_new (T, D) -> mu (T,n), var (T,n), jac_mu (T,n,D), jac_var (T,n,D), hess_mu (T,n,D,D).  The first four are
+        those of predict_device_grad to the bit; hess_mu is exactly symmetric."""
+        self._need_trained()
+        hd = self._handle
+        x = B.as_dev(x_new, hd.device)
+        if x.dim() != 2 or x.shape[1] != hd.D:
+            raise ValueError("x_new must be (T, {})".format(hd.D))
+        T, n, D = x.shape[0], hd.n_out, hd.D
+        mu, var = B.empty((T, n), hd.device), B.empty((T, n), hd.device)
+        jm, jv = B.empty((T, n, D), hd.device), B.empty((T, n, D), hd.device)
+        hm = B.empty((T, n, D, D), hd.device)
+        check(lib.sr_gp_linearize_batch(hd.h, B.ptr(x), T, B.ptr(mu), B.ptr(var), B.ptr(jm), B.ptr(jv), B.ptr(hm),
+                                        B.stream_ptr(hd.device)))
+        return mu, var, jm, jv, hm
+
+    def _linearize_batch_host(self, x):
+        """linearize_device_batch for a NumPy batch through one staging round trip (as _predict_grad_host)."""
+        hd = self._handle
+        T, n, D = x.shape[0], hd.n_out, hd.D
+        if T == 0 or T * n * (2 + 2 * D + D * D) > B.STAGING_MAX_DOUBLES:
+            return tuple(B.to_numpy(o) for o in self.linearize_device_batch(x))
+        st = getattr(hd, "_staging", None)
+        if st is None:
+            st = hd._staging = B.Staging(hd.device)
+        shapes = [(T, n), (T, n), (T, n, D), (T, n, D), (T, n, D, D)]
+        (dx,), outs = st.stage([x], shapes, zero_copy=True)
+        check(lib.sr_gp_linearize_batch(hd.h, B.ptr(dx), T, B.ptr(outs[0]), B.ptr(outs[1]), B.ptr(outs[2]),
+                                        B.ptr(outs[3]), B.ptr(outs[4]), B.stream_ptr(hd.device)))
+        return tuple(st.fetch())
+
+    def linearize_predict_batch(self, states, actions):
+        """``linearize_predict(..., jacobians=True)`` for a batch of T rows (states (T,n_s), actions (T,n_u)):
+        (mu (T,n), var (T,n), jac_mu (T,n,D), jac_var (T,n,D), hess_mu (T,n,D,D)), NumPy or tensors like the input.
+        Every batch but a single row takes one batched pass (sr_gp_linearize_batch, D <= GRAD_MAX_D); one row the
+        single-query latency route; wider inputs a loop of single-query rows.  Unlike linearize_predict, nothing is
+        cached for ``get_linearize_reverse``."""
+        self._need_trained()
+        hd = self._handle
+        if B.is_tensor(states):
+            x = torch.cat((states, actions), dim=1)
+            if x.shape[1] != hd.D:
+                raise ValueError("states and actions must have {} columns together".format(hd.D))
+            if x.shape[0] != 1 and hd.D <= self.GRAD_MAX_D:
+                return self.linearize_device_batch(x)
+            if x.shape[0] == 1:
+                return tuple(o.unsqueeze(0) for o in self.linearize_device(x[0]))
+            return tuple(B.as_dev(o, hd.device) for o in self._linearize_rows(x.detach().cpu().numpy()))
+        x = np.ascontiguousarray(np.hstack((np.asarray(states, dtype=np.float64), np.asarray(actions, dtype=np.float64))))
+        if x.ndim != 2 or x.shape[1] != hd.D:
+            raise ValueError("states and actions must have {} columns together".format(hd.D))
+        if x.shape[0] != 1 and hd.D <= self.GRAD_MAX_D:
+            return self._linearize_batch_host(x)
+        return self._linearize_rows(x)
+
+    def _linearize_rows(self, x):
+        """one single-query linearisation (_linearize_host) per row of a host batch x (T, D)"""
+        hd = self._handle
+        T, n, D = x.shape[0], hd.n_out, hd.D
+        out = (np.empty((T, n)), np.empty((T, n)), np.empty((T, n, D)), np.empty((T, n, D)), np.empty((T, n, D, D)))
+        for t in range(T):
+            for o, r in zip(out, self._linearize_host(x[t])):
+                o[t] = r
+        return out
+
     # from this many queries on predict(states, actions, jacobians=True) takes the batched gradient pass instead of the
     # single-query linearisation per row (inputs of up to GRAD_MAX_D dimensions: the pass's compiled range)
     GRAD_BATCH_MIN = 2
