@@ -160,6 +160,19 @@ int sr_gp_predict_grad(sr_gp_t h, const double* Xq, long T, double* mu, double* 
 int sr_gp_linearize_batch(sr_gp_t h, const double* Xq, long T, double* mu, double* var,
                           double* jac_mu, double* jac_var, double* hess_mu, void* stream);
 
+/* ---- greedy max-variance subset (choose_datapoints_maxvar) by pivoted Cholesky downdates ----
+ * X n x D (device): the pool.  init_idx k (device, distinct, 0 <= i < n, k >= 1): forced first pivots, in order.
+ * idx m (device): the k seeds then m - k greedy picks; score m (device, may be NULL): Sigma_d var_d(pick) just
+ * before it was picked (seeds: the same quantity).  Kernel and noise are the handle's (sr_gp_set_data*), its
+ * training rows are not read.  k <= m <= n.  One launch per round, no host synchronisation.
+ * replaces: the greedy loop of ssm_gpy/gaussian_process.py:323-343 with fixed hyper-parameters.  Pivot = first argmax of
+ * Sigma_d max(var_d, 1e-15) over the rows not taken (ties: the smaller row); repeated calls are bit-identical.  The k seeds
+ * are read back once and checked before anything is launched (SR_EINVAL: k < 1, k > m, m > n, a seed outside [0, n) or
+ * twice).  Memory: grow-only n_out x (m - 1) x n (padded to 64) doubles of the factor and n_out x n more, owned by the
+ * handle and freed by sr_gp_release_scratch; SR_EHIP when they cannot be allocated. */
+int sr_gp_select_maxvar(sr_gp_t h, const double* X, long n, int m, const int* init_idx, int k,
+                        int* idx, double* score, void* stream);
+
 /* ---- single query with second-order outputs (the CasADi Jacobian callback) ------------------------
  * replaces: linearize_predict(states 1xn, actions 1xm, jacobians=True)  state_space_models.py:106-138,
  *           consumed at :402-415; reference implementation ssm_pytorch/gaussian_process.py:333-385.

@@ -61,6 +61,7 @@ SIGNATURES = {
     "sr_gp_linearize": (_I, [_H, _P, _P, _P, _P, _P, _P, _P]),
     "sr_gp_predict_grad": (_I, [_H, _P, _L, _P, _P, _P, _P, _P]),
     "sr_gp_linearize_batch": (_I, [_H, _P, _L, _P, _P, _P, _P, _P, _P]),
+    "sr_gp_select_maxvar": (_I, [_H, _P, _L, _I, _P, _I, _P, _P, _P]),
     "sr_gp_set_input_transform": (_I, [_H, _P, _I, _P]),
     "sr_onestep_reach": (_I, [_H, _L, _P, _P, _P, _P, _P, _P, _P, _P, _D, _P, _P, _P, _P, _P]),
     "sr_multistep_reach": (_I, [_H, _L, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _D, _P, _P, _P, _P]),

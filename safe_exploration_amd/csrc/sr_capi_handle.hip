@@ -224,6 +224,7 @@ extern "C" int sr_gp_destroy(sr_gp_t h) {
     dev_free(alpha_alloc_of(h)); dev_free(wt_alloc_of(h)); dev_free(h->kp); dev_free(h->lin_v); dev_free(h->lin_g); dev_free(h->small_vp); dev_free(h->splitk_vt); dev_free(h->splitk_part);
     dev_free(h->grad_v); dev_free(h->grad_part);
     dev_free(h->hess_part);
+    dev_free(h->sel_L); dev_free(h->sel_ws);
     dev_free(h->stream_vp); dev_free(h->stream_tickets); dev_free(h->stream_slots); dev_free(h->stream_tab);
     dev_free(h->Tz); dev_free(h->tz_x); dev_free(h->tz_jac);
     dev_free(h->chain_xch); dev_free(h->chain_tickets); dev_free(h->chain_done); dev_free(h->call_ticket);
@@ -491,6 +492,8 @@ extern "C" int sr_gp_release_scratch(sr_gp_t h) {
     dev_free(h->grad_v); h->grad_v = nullptr; h->grad_v_cap = 0;
     dev_free(h->grad_part); h->grad_part = nullptr; h->grad_part_cap = 0;
     dev_free(h->hess_part); h->hess_part = nullptr; h->hess_part_cap = 0;
+    dev_free(h->sel_L); h->sel_L = nullptr; h->sel_L_cap = 0;
+    dev_free(h->sel_ws); h->sel_ws = nullptr; h->sel_ws_cap = 0;
     dev_free(h->yT_alt); dev_free(h->alpha_alt); h->yT_alt = h->alpha_alt = nullptr; h->vec_alt_np = 0;
     // the caller wants the memory back: what these releases left in the block cache goes to the driver too
     return sr_release_cached_memory();

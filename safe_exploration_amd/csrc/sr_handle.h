@@ -72,6 +72,9 @@ struct sr_gp {
     // sr_gp_linearize_batch (grow-only): the training-row splits' partial sums of the Hessian of the mean
     // (n_split x n_out x (D (D + 1) / 2 + 1) x Tp); capacity in doubles
     double* hess_part = nullptr; long hess_part_cap = 0;
+    // sr_gp_select_maxvar (grow-only): the pivoted factor L (n_out x (m - 1) x padded pool) and [var | partial scores |
+    // partial rows | taken marks]; capacities in doubles
+    double* sel_L = nullptr; long sel_L_cap = 0; double* sel_ws = nullptr; long sel_ws_cap = 0;
     // log det(K + noise) per output as of the last <= 16-row append (read back with its status words): the blocking read of
     // sr_gp_logdet costs the exploration loop 30 us per step
     std::vector<double> logdet_host; int logdet_valid = 0;

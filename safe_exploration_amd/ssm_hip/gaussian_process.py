@@ -9,7 +9,7 @@ include/safereach.h (Gram + blocked fp64-MFMA Cholesky at model-update time; fus
 cross-covariance / triangular contraction kernels at prediction time).
 
 Also provided, each through its own C entry point: ``opt_hyp=True`` (L-BFGS-B over ``sr_gp_mll``),
-``choose_datapoints_maxvar``, ``sample_from_gp`` (``sr_gp_sample``), ``information_gain`` (``sr_gp_logdet``),
+``choose_datapoints_maxvar`` (opt-in ``route="downdate"``: ``sr_gp_select_maxvar``), ``sample_from_gp`` (``sr_gp_sample``), ``information_gain`` (``sr_gp_logdet``),
 ``linearize_predict(jacobians=True)`` with ``get_reverse`` / ``get_linearize_reverse`` (``has_reverse`` is True).
 Not provided: sparse GP regression (``do_sparse_gp``, GPy's ``SparseGPRegression``).
 """
@@ -27,6 +27,7 @@ from ..state_space_models import StateSpaceModel
 _server_call = lib.sr_gp_server_call
 
 GPY_JITTER = 1e-8   # GPy's exact inference adds this to diag(K) (from knowledge of GPy; unverifiable here)
+SELECT_ROUTES = ("predict", "downdate")   # choose_datapoints_maxvar(route=...)
 
 
 class _Handle(object):
@@ -307,8 +308,18 @@ class SimpleGPModel(StateSpaceModel):
         idx = np.random.choice(n_data, size=m, replace=False)
         return X[idx, :], y[idx, :]
 
+    # route of choose_datapoints_maxvar when a call names none (set_select_route)
+    _select_route = "predict"
+
+    def set_select_route(self, route):
+        """Route of ``choose_datapoints_maxvar`` for this model when a call names none -- what ``train(m=...)`` and
+        ``update_model`` use: "predict" (the default) or "downdate" (``sr_gp_select_maxvar``)."""
+        if route not in SELECT_ROUTES:
+            raise ValueError("route must be one of {}".format(SELECT_ROUTES))
+        self._select_route = route
+
     def choose_datapoints_maxvar(self, x, y, m, k=10, min_ratio_k=0.25, n_reopt_gp=1, init_idx=None,
-                                 noise_diag=1e-5, return_index=False):
+                                 noise_diag=1e-5, return_index=False, route=None, return_scores=False):
         """Choose m datapoints by the maximum-predicted-variance criterion  (gaussian_process.py:280-345).
 
         Same scheme as the reference: k-means picks ``k`` seed points (one random member per cluster), then
@@ -318,12 +329,23 @@ class SimpleGPModel(StateSpaceModel):
         Differences, both forced: hyper-parameters are fixed (the reference re-optimises them on the pool
         ``n_reopt_gp`` times, :327-328, which also makes those rounds score the pool with a GP conditioned on
         the pool itself), and the seed set is random (k-means + ``np.random.choice``) unless ``init_idx`` is
-        given."""
+        given.
+
+        ``route``: "predict" (the loop above), "downdate" (``sr_gp_select_maxvar``: the same greedy rule as pivoted
+        Cholesky downdates of K_pool + noise on the device -- one launch per round, one read-back at the end, then one fit
+        on the chosen rows) or None (the model's, ``set_select_route``: "predict" unless set).  ``return_scores=True``
+        (downdate route only) appends the m scores sum_d var_d(pick) just before each pick (None when n_data <= m)."""
+        route = self._select_route if route is None else route
+        if route not in SELECT_ROUTES:
+            raise ValueError("route must be one of {}".format(SELECT_ROUTES))
+        if return_scores and route != "downdate":
+            raise ValueError("return_scores needs route='downdate'")
         x = np.asarray(x, dtype=np.float64)
         y = np.asarray(y, dtype=np.float64)
         n_data = x.shape[0]
         if n_data <= m:
-            return (x, y, np.arange(n_data)) if return_index else (x, y)
+            out = (x, y, np.arange(n_data)) if return_index else (x, y)
+            return out + (None,) if return_scores else out
         if init_idx is None:
             from sklearn import cluster
             k = int(np.minimum(int(n_data * min_ratio_k), k))
@@ -332,6 +354,8 @@ class SimpleGPModel(StateSpaceModel):
         chosen = [int(i) for i in init_idx][:m]
         if len(set(chosen)) != len(chosen) or min(chosen) < 0 or max(chosen) >= n_data:
             raise ValueError("init_idx must hold distinct row indices of x")
+        if route == "downdate":
+            return self._choose_downdate(x, y, m, chosen, noise_diag, return_index, return_scores)
         self._fit(x[chosen], y[chosen], noise_diag)
         self._noise_diag = noise_diag
         self.gp_trained = True
@@ -357,6 +381,28 @@ class SimpleGPModel(StateSpaceModel):
         self._z_fit, self._y_z = x[idx], y[idx]
         self._beta = self._inv_K = None
         return (x[idx], y[idx], idx) if return_index else (x[idx], y[idx])
+
+    def _choose_downdate(self, x, y, m, chosen, noise_diag, return_index, return_scores):
+        """choose_datapoints_maxvar(route="downdate"): a fit on the seeds puts kernel and noise on the handle, one
+        sr_gp_select_maxvar over the pool, one read-back of picks and scores, one fit on the chosen rows in pick order."""
+        self._fit(x[chosen], y[chosen], noise_diag)
+        hd = self._handle
+        tx = B.as_dev(x, hd.device)
+        seeds = torch.as_tensor(np.asarray(chosen, dtype=np.int32), device=hd.device)
+        out = B.empty((m + (m + 1) // 2,), hd.device)          # [scores: m doubles | picks: m int32]
+        check(lib.sr_gp_select_maxvar(hd.h, B.ptr(tx), x.shape[0], m, B.ptr(seeds), len(chosen),
+                                      B.ptr(out[m:].view(torch.int32)), B.ptr(out), B.stream_ptr(hd.device)))
+        host = B.to_numpy(out)
+        scores = host[:m].copy()
+        idx = host[m:].view(np.int32)[:m].astype(np.int64)
+        self._fit(x[idx], y[idx], noise_diag)
+        self._noise_diag = noise_diag
+        self.gp_trained = True
+        self.z, self.x_train, self.y_train = x[idx], x, y
+        self._z_fit, self._y_z = x[idx], y[idx]
+        self._beta = self._inv_K = None
+        res = (x[idx], y[idx], idx) if return_index else (x[idx], y[idx])
+        return res + (scores,) if return_scores else res
 
     def train(self, X, y, m=None, opt_hyp=True, noise_diag=1e-5, Z=None, choose_data=True):
         """Condition the GPs on data (ssm_gpy/gaussian_process.py:189-278).
