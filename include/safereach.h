@@ -47,7 +47,9 @@ typedef struct sr_gp* sr_gp_t;
 #define SR_K_ELL       6   /* ellipsoid propagate/sum                                  */
 #define SR_K_TRINV     7   /* GEMMs of the blocked triangular inversion W = U^-T            */
 #define SR_K_SMALL     8   /* one-launch posterior of a small model (Np <= 512, T <= 1024)  */
-#define SR_K_COUNT     9
+#define SR_K_SPARSE_PANEL 9  /* sr_gp_fit_sparse: cross-covariance panel K_fu of a chunk (+ its share of K_uf y) */
+#define SR_K_SPARSE_GEMM  10 /* sr_gp_fit_sparse: streamed G += K_fu^T K_fu on the fp64 MFMA tile                 */
+#define SR_K_COUNT     11
 
 int         sr_version(void);
 const char* sr_last_error(void);
@@ -79,6 +81,22 @@ int sr_gp_set_data_general(sr_gp_t h, const double* Z, const double* Y, const do
  * info [host, n_out ints]: 0, or 1-based index of the first non-positive pivot (then returns SR_ENOTPD).
  * Synchronises the stream before returning. */
 int sr_gp_factorize(sr_gp_t h, void* stream, int* info);
+
+/* ---- sparse GP regression (inducing points): the fit that takes the place of sr_gp_factorize ----------------
+ * replaces: SparseGPRegression(X, y, Z=Z) behind do_sparse_gp  ssm_gpy/gaussian_process.py:204, 224-243, 397-400.
+ * h: created with N = m and given the inducing inputs, the kernel and noise_var = s2 (likelihood variance) by
+ * sr_gp_set_data[_general] (its Y is not read).  X N x D, Y N x n_out: ALL data, streamed in chunks of sr_gp_set_chunk rows
+ * (<= 16384; workspace n_out x chunk x Np + 2 n_out x Np^2 doubles beside that of sr_gp_factorize, freed on return).
+ * Sigma = K_uu + jitter I + K_uf K_fu / s2; alpha = Sigma^-1 K_uf y / s2; Wt = P upper, P P^T = (K_uu + jitter I)^-1 - Sigma^-1.
+ * The handle is then factorized AND sparse; repeated fits with one chunk size are bit-identical (another chunk size: equal to
+ * rounding).  SR_EINVAL N < m, NULL, jitter < 0; SR_ESTATE no data; SR_ENOTPD + info[d] (as sr_gp_factorize; a pivot of K_uu
+ * not above Np eps k_max counts as non-positive); SR_EHIP no workspace.  Synchronises the stream. */
+int sr_gp_fit_sparse(sr_gp_t h, const double* X, const double* Y, long N, double jitter, void* stream, int* info);
+/* 1 after sr_gp_fit_sparse, 0 otherwise (sr_gp_factorize clears the mark), < 0 on error.  On a sparse handle sr_gp_append,
+ * sr_gp_append1_host, sr_gp_mll, sr_gp_logdet and sr_gp_logdet_cached return SR_ESTATE (Wt is not the factor of K_y);
+ * sr_gp_inv_k gives P P^T; export / import, predictions, reachability and the server work unchanged.  The exported state
+ * does not carry the mark (the packed format is unchanged): the receiver of a sparse model must not append. */
+int sr_gp_is_sparse(sr_gp_t h);
 
 /* Condition on m <= 128 ADDITIONAL training points (same hyper-parameters) without refactorising: block row append of
  * the triangular factor, O(N^2 m).  Znew m x D, Ynew m x n_out; info [host, n_out] like sr_gp_factorize.

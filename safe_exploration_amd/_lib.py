@@ -14,7 +14,7 @@ import torch  # noqa: F401  MUST precede CDLL below: PyTorch-ROCm bundles its ow
 from ._build import LIB_PATH
 
 SR_OK, SR_EINVAL, SR_EHIP, SR_ENOTPD, SR_ESTATE, SR_EUNSUPPORTED, SR_EBUSY = 0, -1, -2, -3, -4, -5, -6
-K_GRAM, K_POTRF, K_GEMM, K_KSTAR, K_VAR, K_FINAL, K_ELL, K_TRINV, K_SMALL = range(9)
+K_GRAM, K_POTRF, K_GEMM, K_KSTAR, K_VAR, K_FINAL, K_ELL, K_TRINV, K_SMALL, K_SPARSE_PANEL, K_SPARSE_GEMM = range(11)
 KERNEL_NAMES = {K_GRAM: "sr_gram_kernel", K_POTRF: "sr_potrf_diag_kernel", K_GEMM: "sr_gemm_tn_kernel",
                 K_KSTAR: "sr_kstar_kernel", K_VAR: "sr_var_kernel", K_FINAL: "sr_finalize_kernel",
                 K_ELL: "sr_ellipsoid_kernel"}
@@ -45,6 +45,8 @@ SIGNATURES = {
     "sr_gp_set_data": (_I, [_H, _P, _P, _P, _P, _P, _P]),
     "sr_gp_set_data_general": (_I, [_H, _P, _P, _P, _P, _P]),
     "sr_gp_factorize": (_I, [_H, _P, _PI]),
+    "sr_gp_fit_sparse": (_I, [_H, _P, _P, _L, _D, _P, _PI]),
+    "sr_gp_is_sparse": (_I, [_H]),
     "sr_gp_append": (_I, [_H, _P, _P, _I, _P, _PI]),
     "sr_gp_append1_host": (_I, [_H, _P, _P, _P, _PI]),
     "sr_gp_padded_n": (_I, [_H, _PL]),

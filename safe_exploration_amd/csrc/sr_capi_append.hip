@@ -416,6 +416,7 @@ extern "C" int sr_gp_grid_append_aborts(sr_gp_t h, long* n) {
 extern "C" int sr_gp_append1_host(sr_gp_t h, const double* x_host, const double* y_host, void* stream, int* info) {
     SR_CHECK(h != nullptr && x_host && y_host, SR_EINVAL, "sr_gp_append1_host: NULL argument");
     SR_CHECK(h->factorized, SR_ESTATE, "sr_gp_append1_host: model not factorized");
+    SR_CHECK(!h->sparse, SR_ESTATE, "sr_gp_append1_host: sparse model (U^-1 is not the factor of K_y): refit with sr_gp_fit_sparse");
     SR_DEVICE(h->device);
     if (!append1_fused(h, 1) || h->n_out > SR_APPEND1_MAX_OUT) {
         if (append1_route(h, 1, true) == 2 && h->n_out <= SR_APPEND1_MAX_OUT) {
@@ -432,6 +433,7 @@ extern "C" int sr_gp_append1_host(sr_gp_t h, const double* x_host, const double*
 extern "C" int sr_gp_append(sr_gp_t h, const double* Znew, const double* Ynew, int m, void* stream, int* info) {
     SR_CHECK(h != nullptr && Znew && Ynew, SR_EINVAL, "sr_gp_append: NULL argument");
     SR_CHECK(h->factorized, SR_ESTATE, "sr_gp_append: model not factorized");
+    SR_CHECK(!h->sparse, SR_ESTATE, "sr_gp_append: sparse model (U^-1 is not the factor of K_y): refit with sr_gp_fit_sparse");
     SR_CHECK(m >= 1 && m <= SR_NB, SR_EINVAL, "sr_gp_append: m=%d outside 1..%d (append in several calls)", m, SR_NB);
     hipStream_t s = (hipStream_t)stream;
     SR_DEVICE(h->device);

@@ -266,7 +266,7 @@ extern "C" int sr_gp_set_data(sr_gp_t h, const double* Z, const double* Y, const
     SR_HIP(hipGetLastError());
     h->general = 0;
     h->have_data = 1;
-    h->factorized = 0; h->logdet_valid = 0;
+    h->factorized = 0; h->logdet_valid = 0; h->sparse = 0;
     h->sf2_host.clear(); h->noise_host.clear();
     return SR_OK;
 }
@@ -288,7 +288,7 @@ extern "C" int sr_gp_set_data_general(sr_gp_t h, const double* Z, const double* 
     h->general = 1;
     h->sf2_host.clear(); h->noise_host.clear();
     h->have_data = 1;
-    h->factorized = 0; h->logdet_valid = 0;
+    h->factorized = 0; h->logdet_valid = 0; h->sparse = 0;
     return SR_OK;
 }
 
@@ -382,7 +382,7 @@ extern "C" int sr_gp_import(sr_gp_t h, const double* alpha, const double* Wt, vo
                             hipMemcpyDeviceToDevice, s));
     SR_HIP(hipMemcpyAsync(h->Wt, Wt, sizeof(double) * h->n_out * h->Np * h->Np,
                           hipMemcpyDeviceToDevice, s));
-    h->factorized = 1; h->logdet_valid = 0;
+    h->factorized = 1; h->logdet_valid = 0; h->sparse = 0;
     return SR_OK;
 }
 
@@ -438,7 +438,7 @@ extern "C" int sr_gp_import_begin(sr_gp_t h, const double* alpha, void* stream) 
     SR_TRY(server_quiesce(h));
     SR_TRY(unslide(h));
     SR_TRY(ensure_wt(h));             // zero below the diagonal from allocation on; nothing ever writes there
-    h->factorized = 0; h->logdet_valid = 0;
+    h->factorized = 0; h->logdet_valid = 0; h->sparse = 0;
     h->import_open = 1;
     SR_HIP(hipMemsetAsync(h->alpha, 0, sizeof(double) * h->n_out * h->Np, s));
     SR_HIP(hipMemcpy2DAsync(h->alpha + (h->Np - h->N), sizeof(double) * h->Np, alpha, sizeof(double) * h->N,
@@ -466,7 +466,7 @@ extern "C" int sr_gp_import_end(sr_gp_t h) {
     SR_CHECK(h != nullptr, SR_EINVAL, "sr_gp_import_end: NULL handle");
     SR_CHECK(h->import_open, SR_ESTATE, "sr_gp_import_end: no import in progress");
     h->import_open = 0;
-    h->factorized = 1; h->logdet_valid = 0;
+    h->factorized = 1; h->logdet_valid = 0; h->sparse = 0;
     return SR_OK;
 }
 

@@ -291,9 +291,9 @@ static int ensure_fact_streams(sr_gp* h, int regime) {
     return SR_OK;
 }
 
-extern "C" int sr_gp_factorize(sr_gp_t h, void* stream, int* info) {
-    SR_CHECK(h != nullptr, SR_EINVAL, "sr_gp_factorize: NULL handle");
-    SR_CHECK(h->have_data, SR_ESTATE, "sr_gp_factorize: call sr_gp_set_data first");
+// the update itself.  src == NULL: the exact fit (Gram matrix of the handle's data, alpha = K_y^-1 y); else the same chain of
+// launches on the caller's matrices (srh::factorize_matrix, sr_handle.h)
+static int factorize_impl(sr_gp* h, void* stream, int* info, const sr_fact_src* src) {
     SR_DEVICE(h->device);
     SR_TRY(server_quiesce(h));
     SR_TRY(unslide(h));
@@ -540,7 +540,11 @@ extern "C" int sr_gp_factorize(sr_gp_t h, void* stream, int* info) {
         }
         {
             sr_prof_scope ps(&h->prof, SR_K_GRAM, sc);
-            if (h->general)
+            if (src) {
+                for (int b = 0; b < nd; ++b)
+                    SR_FH(hipMemcpyAsync(U + (size_t)b * per, src->mat + (size_t)(d0 + b) * NN, NN * sizeof(double),
+                                         hipMemcpyDeviceToDevice, sc));
+            } else if (h->general)
                 SR_F(sr_launch_gram_general(h->Z, h->kp + (size_t)d0 * SR_KP(h->D), 0.0, h->noise + d0, U, h->N, Np, h->D, sc,
                                             nd, sP));
             else
@@ -800,8 +804,13 @@ extern "C" int sr_gp_factorize(sr_gp_t h, void* stream, int* info) {
         if (early_done) SR_FH(hipStreamWaitEvent(sc, h->ev_inv[1], 0));
         SR_F(inv_stage(nb, sc, true));                    // whatever the stages have left
         // alpha = Wt (W y)   (v behind W in the scratch)
-        SR_F(sr_launch_trmv(W, Np, h->yT + (size_t)d0 * Np, W + NN, Np, 1, sc, nd, sP, Np, sP));
-        SR_F(sr_launch_trmv(Wt, Np, W + NN, h->alpha + (size_t)d0 * Np, Np, 0, sc, nd, sN, sP, Np));
+        const double* rhs = src ? src->rhs : h->yT;
+        if (rhs) {
+            SR_F(sr_launch_trmv(W, Np, rhs + (size_t)d0 * Np, W + NN, Np, 1, sc, nd, sP, Np, sP));
+            SR_F(sr_launch_trmv(Wt, Np, W + NN, h->alpha + (size_t)d0 * Np, Np, 0, sc, nd, sN, sP, Np));
+        }
+        // the factor itself, index-reversed and transposed, in place of its inverse (diagonal blocks: U, the rest: W)
+        if (src && src->reversed) SR_F(sr_launch_reversed_factor(U, W, Wt, Np, sc, nd, sP, sN));
     }
     if (own_streams) {
         SR_FH(hipEventRecord(h->fact_join, sc));
@@ -841,11 +850,11 @@ extern "C" int sr_gp_factorize(sr_gp_t h, void* stream, int* info) {
             (void)hipMemset(h->fact_flags, 0, sizeof(unsigned) * (size_t)(4 + 3 * h->fact_flags_nb));
             h->fact_epoch = 0;
         }
-        return sr_gp_factorize(h, stream, info);
+        return factorize_impl(h, stream, info, src);
     }
     int bad = 0;
     for (int d = 0; d < h->n_out; ++d) {
-        if (info_h[d] > 0) info_h[d] = std::max(1, info_h[d] - (h->Np - h->N));   // padded -> training index
+        if (info_h[d] > 0 && !src) info_h[d] = std::max(1, info_h[d] - (h->Np - h->N));   // padded -> training index
         if (info) info[d] = info_h[d];
         if (info_h[d] != 0 && !bad) bad = d + 1;
     }
@@ -856,6 +865,17 @@ extern "C" int sr_gp_factorize(sr_gp_t h, void* stream, int* info) {
     }
     h->factorized = 1;
     return SR_OK;
+}
+
+extern "C" int sr_gp_factorize(sr_gp_t h, void* stream, int* info) {
+    SR_CHECK(h != nullptr, SR_EINVAL, "sr_gp_factorize: NULL handle");
+    SR_CHECK(h->have_data, SR_ESTATE, "sr_gp_factorize: call sr_gp_set_data first");
+    h->sparse = 0;                                       // an exact fit on the handle's inputs (again)
+    return factorize_impl(h, stream, info, nullptr);
+}
+
+int srh::factorize_matrix(sr_gp* h, void* stream, int* info, const sr_fact_src* src) {
+    return factorize_impl(h, stream, info, src);
 }
 
 extern "C" int sr_gp_set_fact_pipeline(sr_gp_t h, int on) {
@@ -908,6 +928,7 @@ extern "C" int sr_gp_set_fact_panel(sr_gp_t h, int panel) {
 extern "C" int sr_gp_mll(sr_gp_t h, double* nll, double* grad, void* stream) {
     SR_CHECK(h && nll && grad, SR_EINVAL, "sr_gp_mll: NULL argument");
     SR_CHECK(h->factorized, SR_ESTATE, "sr_gp_mll: model not factorized");
+    SR_CHECK(!h->sparse, SR_ESTATE, "sr_gp_mll: sparse model (U^-1 is not the factor of K_y)");
     SR_CHECK(h->general, SR_ESTATE, "sr_gp_mll: set the data with sr_gp_set_data_general (packed parameters)");
     hipStream_t s = (hipStream_t)stream;
     SR_DEVICE(h->device);
@@ -941,6 +962,7 @@ extern "C" int sr_gp_mll(sr_gp_t h, double* nll, double* grad, void* stream) {
 extern "C" int sr_gp_logdet_cached(sr_gp_t h, double* logdet_host) {
     SR_CHECK(h && logdet_host, SR_EINVAL, "sr_gp_logdet_cached: NULL argument");
     SR_CHECK(h->factorized, SR_ESTATE, "sr_gp_logdet_cached: model not factorized");
+    SR_CHECK(!h->sparse, SR_ESTATE, "sr_gp_logdet_cached: sparse model (U^-1 is not the factor of K_y)");
     if (!h->logdet_valid || (int)h->logdet_host.size() != h->n_out) {
         sr_set_error("sr_gp_logdet_cached: no host copy");
         return SR_ESTATE;
@@ -952,6 +974,7 @@ extern "C" int sr_gp_logdet_cached(sr_gp_t h, double* logdet_host) {
 extern "C" int sr_gp_logdet(sr_gp_t h, double* logdet, void* stream) {
     SR_CHECK(h && logdet, SR_EINVAL, "sr_gp_logdet: NULL argument");
     SR_CHECK(h->factorized, SR_ESTATE, "sr_gp_logdet: model not factorized");
+    SR_CHECK(!h->sparse, SR_ESTATE, "sr_gp_logdet: sparse model (U^-1 is not the factor of K_y)");
     SR_DEVICE(h->device);
     return sr_launch_logdet(h->Wt, h->Np, h->n_out, logdet, (hipStream_t)stream);
 }

@@ -176,6 +176,10 @@ int sr_launch_mll(const double* Kinv, int Np, int N, const double* alpha, const 
                   hipStream_t s);
 int sr_launch_logdet(const double* Wt, int Np, int n_out, double* out, hipStream_t s);
 int sr_launch_fill(double* p, size_t n, double v, hipStream_t s);
+// Wt = J U^T J from the factor as the model update leaves it (diagonal 128-blocks in U, block rows in W; sr_sparse.hip);
+// nbatch members, U / W sS and Wt sD doubles apart
+int sr_launch_reversed_factor(const double* U, const double* W, double* Wt, int Np, hipStream_t s, int nbatch, long sS,
+                              long sD);
 int sr_launch_sub_block(double* S, const double* G, int pf, hipStream_t s);
 int sr_launch_append_assemble(const double* Wt0, int Np0, int off0, int N0, const double* Y2,
                               const double* invS, int m, double* Wt1, int Np1, int off1, hipStream_t s);

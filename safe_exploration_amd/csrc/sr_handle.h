@@ -53,6 +53,7 @@ struct sr_gp {
     unsigned* call_ticket = nullptr;        // sr_gp_call1: workgroups done (reset by the last one)
     int general = 0;
     int have_data = 0, factorized = 0;
+    int sparse = 0;          // the posterior is that of sr_gp_fit_sparse: Wt Wt^T = K_uu^-1 - Sigma^-1, not K_y^-1
     int import_open = 0;     // between sr_gp_import_begin and sr_gp_import_end
     // per-chunk workspace (grow-only)
     long chunk = 65536, ws_Tp = 0, ws_part = 0;     // ws_part: capacity of mu_part in units of n_out doubles
@@ -200,6 +201,14 @@ static inline hipError_t device_sync() {
     if (hipGetDevice(&dev) == hipSuccess) servers_quiesce_device(dev);
     return hipDeviceSynchronize();
 }
+
+// The chain of launches of sr_gp_factorize on the caller's matrices (sr_capi_update.hip; the sparse fit, sr_sparse.hip):
+// mat n_out x Np x Np symmetric in the padded layout (identity on the padding; the upper block triangle is read), copied
+// into the scratch in place of the Gram matrix; rhs n_out x Np in place of yT (NULL: alpha is not written).
+// -> Wt = U^-1 with U^T U = mat, or, reversed != 0, Wt = J U^T J (J the reversal of the padded index: upper triangular,
+// Wt Wt^T = J mat J).  info [host, n_out]: the 1-based PADDED index of the first non-positive pivot.
+struct sr_fact_src { const double* mat; const double* rhs; int reversed; };
+int factorize_matrix(sr_gp* h, void* stream, int* info, const sr_fact_src* src);
 
 // posterior pass and its workspace (sr_capi_posterior.hip)
 int pick_nsplit(const sr_gp* h, long Tp);

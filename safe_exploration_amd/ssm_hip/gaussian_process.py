@@ -11,7 +11,10 @@ cross-covariance / triangular contraction kernels at prediction time).
 Also provided, each through its own C entry point: ``opt_hyp=True`` (L-BFGS-B over ``sr_gp_mll``),
 ``choose_datapoints_maxvar`` (opt-in ``route="downdate"``: ``sr_gp_select_maxvar``), ``sample_from_gp`` (``sr_gp_sample``), ``information_gain`` (``sr_gp_logdet``),
 ``linearize_predict(jacobians=True)`` with ``get_reverse`` / ``get_linearize_reverse`` (``has_reverse`` is True).
-Not provided: sparse GP regression (``do_sparse_gp``, GPy's ``SparseGPRegression``).
+Sparse GP regression (``do_sparse_gp = True``, GPy's ``SparseGPRegression``): ``train(X, y, m, Z=..., opt_hyp=False)`` fits
+the DTC posterior of m inducing inputs over ALL of X, y through ``sr_gp_fit_sparse``; ``beta`` / ``inv_K`` are GPy's
+``woodbury_vector`` / ``woodbury_inv`` and every prediction route works as on an exact model of m points.
+Not provided: ``opt_hyp=True`` and ``information_gain()`` of a sparse model (NotImplementedError).
 """
 import ctypes
 import os
@@ -27,6 +30,7 @@ from ..state_space_models import StateSpaceModel
 _server_call = lib.sr_gp_server_call
 
 GPY_JITTER = 1e-8   # GPy's exact inference adds this to diag(K) (from knowledge of GPy; unverifiable here)
+SPARSE_JITTER = 1e-6   # GPy's VarDTC.const_jitter, added to diag(K_uu) (from knowledge of GPy; unverifiable here)
 SELECT_ROUTES = ("predict", "downdate")   # choose_datapoints_maxvar(route=...)
 
 
@@ -415,6 +419,9 @@ class SimpleGPModel(StateSpaceModel):
             raise ValueError("X must be (N, n_s_in+n_u) and y (N, n_s_out)")
         if X.shape[1] != self.n_s_in + self.n_u or y.shape[1] != self.n_s_out:
             raise ValueError("X must be (N, n_s_in+n_u) and y (N, n_s_out)")
+        if self.do_sparse_gp:
+            self._train_sparse(X, y, m, opt_hyp, noise_diag, Z, choose_data)
+            return
         Zs, yz = self._select_subset(X, y, m, Z, choose_data, noise_diag)
         if opt_hyp:
             self.optimize_hyperparameters(Zs, yz)
@@ -425,6 +432,69 @@ class SimpleGPModel(StateSpaceModel):
         self.x_train = X
         self.y_train = y
         self.gp_trained = True
+
+    def _train_sparse(self, X, y, m, opt_hyp, noise_diag, Z, choose_data, jitter=None):
+        """``do_sparse_gp``: m inducing inputs -- the caller's ``Z`` (gaussian_process.py:204) or the rows
+        ``_select_subset`` picks -- summarise all of X, y (``sr_gp_fit_sparse``; GPy's SparseGPRegression posterior,
+        :224-243).  The likelihood variance is sigma_n^2 + noise_diag (:252-253)."""
+        if m is None:
+            raise ValueError("Number of inducing points m needs to be specified for sparse gp regression")
+        if opt_hyp:
+            raise NotImplementedError("opt_hyp=True with do_sparse_gp: the variational bound is not optimised here")
+        if Z is not None:
+            Zu = np.ascontiguousarray(Z, dtype=np.float64)
+            if Zu.ndim != 2 or Zu.shape[1] != X.shape[1]:
+                raise ValueError("Z must be (m, n_s_in+n_u)")
+            if X.shape[0] < Zu.shape[0]:
+                raise ValueError("sparse GP regression needs at least as many data rows as inducing inputs")
+        else:
+            Zu, _ = self._select_subset(X, y, m, None, choose_data, noise_diag)
+        self._fit_sparse(Zu, X, y, noise_diag, SPARSE_JITTER if jitter is None else jitter)
+        self._noise_diag = noise_diag
+        # the device model is a model of the m inducing rows; they carry no targets of their own
+        self._z_fit, self._y_z = Zu, np.zeros((Zu.shape[0], self.n_s_out))
+        self.z = Zu
+        self._m_sparse = m
+        self.x_train = X
+        self.y_train = y
+        self.gp_trained = True
+
+    def _fit_sparse(self, Zu, X, Y, noise_diag, jitter):
+        dev = B.resolve_device(self._device_arg)
+        m, D = Zu.shape
+        old = self._handle
+        if (old is not None and not old.shared and (old.N, old.D, old.n_out) == (m, D, self.n_s_out)
+                and old.device == dev and old.Np_now() == old.Np):
+            handle = old
+        else:
+            handle = _Handle(dev, m, D, self.n_s_out)
+        s2 = self._noise + float(noise_diag)
+        s = B.stream_ptr(dev)
+        self._set_data(handle, Zu, np.zeros((m, self.n_s_out)), s2, dev, s)
+        if getattr(self, "_sparse_chunk", None) is not None:
+            check(lib.sr_gp_set_chunk(handle.h, self._sparse_chunk))
+        tx = B.as_dev(np.ascontiguousarray(X, dtype=np.float64), dev)
+        ty = B.as_dev(np.ascontiguousarray(Y, dtype=np.float64), dev)
+        info = (ctypes.c_int * self.n_s_out)()
+        check(lib.sr_gp_fit_sparse(handle.h, B.ptr(tx), B.ptr(ty), X.shape[0], float(jitter), s, info))
+        self._handle = handle
+        self._beta = None
+        self._inv_K = None
+        if old is not None and old is not handle and getattr(old, "_server_armed", False):
+            try:
+                self.start_server(old._server_idle)
+            except RuntimeError as e:
+                warnings.warn("resident server not re-armed after the model update: {}".format(e))
+
+    def set_sparse_chunk(self, chunk):
+        """Data rows per streamed chunk of the following sparse fits (``sr_gp_set_chunk``; at most 16384 are used)."""
+        if int(chunk) < 1:
+            raise ValueError("chunk must be positive")
+        self._sparse_chunk = int(chunk)
+
+    @property
+    def is_sparse(self):
+        return self._handle is not None and lib.sr_gp_is_sparse(self._handle.h) == 1
 
     def _free_hyp(self, i):
         """[(key, size)] of the hyper-parameters of output i that ``opt_hyp`` may move: everything the caller
@@ -518,7 +588,7 @@ class SimpleGPModel(StateSpaceModel):
         """ssm_gpy/gaussian_process.py:347-419."""
         x = np.asarray(x, dtype=np.float64)
         y = np.asarray(y, dtype=np.float64)
-        if (not replace_old and not opt_hyp and self.gp_trained and self._handle is not None
+        if (not self.do_sparse_gp and not replace_old and not opt_hyp and self.gp_trained and self._handle is not None
                 and not self._handle.shared and self.m is None and self.x_train is not None and not self.z_fixed
                 and noise_diag == self._noise_diag and 0 < x.shape[0] <= self._append_limit_now()):
             self._append(x, y)                       # O(N^2 m) block row append instead of O(N^3)
@@ -526,7 +596,10 @@ class SimpleGPModel(StateSpaceModel):
         if not replace_old and self.x_train is not None:
             x = np.vstack((self.x_train, x))
             y = np.vstack((self.y_train, y))
-        self.train(x, y, self.m, opt_hyp=opt_hyp, noise_diag=noise_diag, Z=self.Z,
+        m = self.m
+        if m is None and self.do_sparse_gp:
+            m = getattr(self, "_m_sparse", None)         # a sparse model keeps its size: refit over the grown / replaced data
+        self.train(x, y, m, opt_hyp=opt_hyp, noise_diag=noise_diag, Z=self.Z,
                    choose_data=choose_data)
 
     # More new points than this: refactorise.  None = by model size, N / 5 (at least 16): measured break-even of
@@ -1192,6 +1265,8 @@ class SimpleGPModel(StateSpaceModel):
         here carries GPy's 1e-8 inference jitter on top: absolute deviation <= N*1e-8/sigma_n^2."""
         self._need_trained()
         hd = self._handle
+        if self.do_sparse_gp or lib.sr_gp_is_sparse(hd.h) == 1:
+            raise NotImplementedError("information_gain of a sparse model: its factor is not that of K_y")
         if x is not None and np.shape(x)[0] != hd.N:
             raise ValueError("information_gain is defined on the training inputs (got {} rows, model holds {})"
                              .format(np.shape(x)[0], hd.N))
