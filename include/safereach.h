@@ -433,6 +433,9 @@ int sr_test_flow_fail(int n);
  * sr_gp_grid_append_aborts: how often that has happened to h so far. */
 int sr_test_grid_append_abort(int n);
 int sr_gp_grid_append_aborts(sr_gp_t h, long* n);
+/* diagnostic: in-place one-point appends the model's buffers have taken since they were last plain (0: U^-1, alpha and the
+ * targets start at their allocations; k: they are views k steps in).  Read-only; tests use it to know which state they met. */
+int sr_gp_slide_steps(sr_gp_t h, int* steps);
 /* per-kernel hipEvent timing inside the library (adds an event pair per launch while enabled). */
 int sr_prof_enable(sr_gp_t h, int on);
 int sr_prof_reset (sr_gp_t h);

@@ -413,6 +413,12 @@ extern "C" int sr_gp_grid_append_aborts(sr_gp_t h, long* n) {
     return SR_OK;
 }
 
+extern "C" int sr_gp_slide_steps(sr_gp_t h, int* steps) {
+    SR_CHECK(h && steps, SR_EINVAL, "sr_gp_slide_steps: NULL argument");
+    *steps = h->slide;
+    return SR_OK;
+}
+
 extern "C" int sr_gp_append1_host(sr_gp_t h, const double* x_host, const double* y_host, void* stream, int* info) {
     SR_CHECK(h != nullptr && x_host && y_host, SR_EINVAL, "sr_gp_append1_host: NULL argument");
     SR_CHECK(h->factorized, SR_ESTATE, "sr_gp_append1_host: model not factorized");

@@ -942,6 +942,9 @@ extern "C" int sr_gp_mll(sr_gp_t h, double* nll, double* grad, void* stream) {
         dev_free(W); dev_free(Kinv); dev_free(partial); dev_free(ld);
         return rc;
     }
+    // No unslide(): after in-place appends Wt / alpha / yT are views into their allocations (sr_gp::slide), and everything
+    // below reads them as they are -- the diagonal, the transpose and the reduction load single doubles (8-byte alignment is
+    // all a view keeps), the GEMM reads the transposed copy.  tests/test_gpu_mll.py holds that at odd and even slides.
     rc = sr_launch_logdet(h->Wt, Np, h->n_out, ld, s);
     for (int d = 0; d < h->n_out && rc == SR_OK; ++d) {
         // K_y^-1 = U^-1 U^-T = sum_k W[k][i] W[k][j]  (W = Wt^T, k-major)
@@ -990,7 +993,7 @@ extern "C" int sr_gp_inv_k(sr_gp_t h, int d, double* inv_k, void* stream) {
     double *W = nullptr, *out = nullptr;
     int rc;
     if ((rc = dev_alloc(&W, NN)) || (rc = dev_alloc(&out, NN))) { dev_free(W); dev_free(out); return rc; }
-    // K^-1 = U^-1 U^-T = sum_k W[k][i] W[k][j]  (W = Wt^T, k-major)
+    // K^-1 = U^-1 U^-T = sum_k W[k][i] W[k][j]  (W = Wt^T, k-major; a slid view of U^-1 is read as it is: see sr_gp_mll)
     rc = sr_launch_transpose(h->Wt + (size_t)d * NN, W, Np, s);
     if (rc == SR_OK) rc = sr_launch_gemm_tn(W, Np, W, Np, out, Np, Np, Np, Np, 1.0, 0.0, 0, s);
     hipError_t e = hipSuccess;
