@@ -4,6 +4,7 @@
 #include "sr_mfma_tile.h"
 #include <atomic>
 #include "sr_pivot_dev.h"
+#include "sr_kernel_dev.h"
 #include "sr_final_dev.h"
 
 // ---- helpers of the block row-append update (sr_gp_append) --------------------------------------
@@ -260,17 +261,8 @@ __global__ __launch_bounds__(1024) void sr_append1_small_kernel(sr_append1_args 
         double v = 0.0;
         if (row < Np0 && row >= off0) {
             const double* z = a.Z + (long)(row - off0) * D;
-            if (a.kp) {                                      // general family (sr_common.h), as sr_gram_general_kernel
-                const double* kp = a.kp + (long)d * SR_KP(D);
-                const double *sv = kp + 3, *av = kp + 3 + D, *bv = kp + 3 + 2 * D;
-                double r2 = 0.0, la = 0.0, lb = 0.0;
-                for (int c = 0; c < D; ++c) {
-                    const double t = (z[c] - zn[c]) * sv[c];
-                    r2 = fma(t, t, r2);
-                    la = fma(av[c] * z[c], zn[c], la);
-                    lb = fma(bv[c] * z[c], zn[c], lb);
-                }
-                v = (kp[2] + la) * kp[1] * sr_kappa((int)kp[0], r2) + lb;
+            if (a.kp) {                                      // general family, the Gram's own form
+                v = sr_kpair(sr_kview(a.kp + (long)d * SR_KP(D), D), D, z, zn);
             } else {
                 double r2 = 0.0;
                 for (int c = 0; c < D; ++c) {
@@ -323,17 +315,8 @@ __global__ __launch_bounds__(1024) void sr_append1_small_kernel(sr_append1_args 
     const double g = block_sum(g_t);
     if (tid == 0) {
         double prior;                                        // k(z_new, z_new)
-        if (a.kp) {
-            const double* kp = a.kp + (long)d * SR_KP(D);
-            double la = 0.0, lb = 0.0;
-            for (int c = 0; c < D; ++c) {
-                la = fma(kp[3 + D + c] * zn[c], zn[c], la);
-                lb = fma(kp[3 + 2 * D + c] * zn[c], zn[c], lb);
-            }
-            prior = (kp[2] + la) * kp[1] + lb;               // kappa(0) = 1
-        } else {
-            prior = a.sf2[d];
-        }
+        if (a.kp) prior = sr_kdiag(a.kp + (long)d * SR_KP(D), D, zn);
+        else prior = a.sf2[d];
         double sch = prior + a.noise[d] - g;                 // Schur complement of the new point
         if (!(sch > 0.0)) {                                  // also catches NaN
             if (wy == 0) a.info[d] = N0 + 1;
@@ -517,16 +500,7 @@ __global__ __launch_bounds__(1024) void sr_append1_grid_kernel(sr_append1g_args 
         if (row >= off0) {
             const double* z = a.Z + (long)(row - off0) * D;
             if (a.kp) {
-                const double* kp = a.kp + (long)d * SR_KP(D);
-                const double *sv = kp + 3, *av = kp + 3 + D, *bv = kp + 3 + 2 * D;
-                double r2 = 0.0, la = 0.0, lb = 0.0;
-                for (int c = 0; c < D; ++c) {
-                    const double t = (z[c] - zn[c]) * sv[c];
-                    r2 = fma(t, t, r2);
-                    la = fma(av[c] * z[c], zn[c], la);
-                    lb = fma(bv[c] * z[c], zn[c], lb);
-                }
-                v = (kp[2] + la) * kp[1] * sr_kappa((int)kp[0], r2) + lb;
+                v = sr_kpair(sr_kview(a.kp + (long)d * SR_KP(D), D), D, z, zn);
             } else {
                 double r2 = 0.0;
                 for (int c = 0; c < D; ++c) {
@@ -623,17 +597,8 @@ __global__ __launch_bounds__(1024) void sr_append1_grid_kernel(sr_append1g_args 
             double gsum = 0.0;
             for (int cb = 0; cb < g.ncb; ++cb) gsum += sr_ld<true>(g.gpart + (long)dd * g.ncb + cb);
             double prior;                                    // k(z_new, z_new)
-            if (a.kp) {
-                const double* kp = a.kp + (long)dd * SR_KP(D);
-                double la = 0.0, lb = 0.0;
-                for (int c = 0; c < D; ++c) {
-                    la = fma(kp[3 + D + c] * zn[c], zn[c], la);
-                    lb = fma(kp[3 + 2 * D + c] * zn[c], zn[c], lb);
-                }
-                prior = (kp[2] + la) * kp[1] + lb;           // kappa(0) = 1
-            } else {
-                prior = a.sf2[dd];
-            }
+            if (a.kp) prior = sr_kdiag(a.kp + (long)dd * SR_KP(D), D, zn);
+            else prior = a.sf2[dd];
             double sch = prior + a.noise[dd] - gsum;         // Schur complement of the new point
             const bool pos = sch > 0.0;                      // false for NaN too
             if (!pos) { ok_all = 0; sch = 1.0; }

@@ -184,10 +184,7 @@ int sr_launch_sub_block(double* S, const double* G, int pf, hipStream_t s);
 int sr_launch_append_assemble(const double* Wt0, int Np0, int off0, int N0, const double* Y2,
                               const double* invS, int m, double* Wt1, int Np1, int off1, hipStream_t s);
 
-// General kernel family (formulas ssm_gpy/gp_models_utils_casadi.py:17-157):
-//   k(x,y) = (c0 + sum_j a_j x_j y_j) * v * kappa(r) + sum_j b_j x_j y_j ,  r^2 = sum_j ((x_j-y_j) s_j)^2
-//   kappa = exp(-r^2/2) (RBF, 0) or (1 + sqrt5 r + 5/3 r^2) exp(-sqrt5 r) (Matern-5/2, 1)
-// packed per output as SR_KP(D) doubles: [kappa, v, c0, s[D], a[D], b[D]]
+// General kernel family (sr_kernel_dev.h), packed per output as SR_KP(D) doubles: [kappa id, v, c0, s[D], a[D], b[D]]
 #define SR_KP(D) (3 + 3 * (D))
 int sr_launch_gram_general(const double* Z, const double* kp, double noise, const double* noise_dev, double* K, int N,
                            int Np, int D, hipStream_t s, int nbatch = 1, long strideK = 0);

@@ -7,6 +7,7 @@
 #include "sr_mfma_tile.h"
 #include "sr_flow.h"
 #include "sr_pivot_dev.h"
+#include "sr_kernel_dev.h"
 // ------------------------------------------------------------------------------------------------
 // Gram matrix K[i][j] = sf2 exp(-0.5 |(z_i - z_j)/l|^2) + noise (i==j); identity on the padding.
 // (kernel spec: ssm_gpy/gp_models_utils_casadi.py:17-40; noise on the diagonal:
@@ -72,7 +73,7 @@ int sr_launch_gram(const double* Z, const double* ls, double sf2, double noise, 
     return SR_OK;
 }
 
-// general kernel family (see sr_common.h; kappa: sr_pivot_dev.h); diagonal = k(z_i, z_i) + noise
+// general kernel family (sr_kernel_dev.h); diagonal = k(z_i, z_i) + noise
 
 __global__ __launch_bounds__(256) void sr_gram_general_kernel(const double* __restrict__ Z,
                                                               const double* __restrict__ kp, double noise,
@@ -92,19 +93,7 @@ __global__ __launch_bounds__(256) void sr_gram_general_kernel(const double* __re
     if (i < off || j < off) {
         v = (i == j) ? 1.0 : 0.0;
     } else {
-        const double* zi = Z + (long)(i - off) * D;
-        const double* zj = Z + (long)(j - off) * D;
-        const int kind = (int)kp[0];
-        const double var = kp[1], c0 = kp[2];
-        const double *sv = kp + 3, *av = kp + 3 + D, *bv = kp + 3 + 2 * D;
-        double r2 = 0.0, la = 0.0, lb = 0.0;
-        for (int c = 0; c < D; ++c) {
-            const double t = (zi[c] - zj[c]) * sv[c];
-            r2 = fma(t, t, r2);
-            la = fma(av[c] * zi[c], zj[c], la);
-            lb = fma(bv[c] * zi[c], zj[c], lb);
-        }
-        v = (c0 + la) * var * sr_kappa(kind, (i == j) ? 0.0 : r2) + lb;
+        v = sr_kpair(sr_kview(kp, D), D, Z + (long)(i - off) * D, Z + (long)(j - off) * D, i == j);
         if (i == j) v += noise;
     }
     K[(long)i * Np + j] = v;

@@ -2,7 +2,7 @@
 // (sr_finalize_wave_kernel, sr_lin_final_kernel) and by the fused small-batch kernels of sr_stream.hip, whose last
 // workgroup runs them in place of a further launch.
 #pragma once
-#include "sr_common.h"
+#include "sr_kernel_dev.h"
 
 __device__ __forceinline__ double sr_wave_sum(double v) {
 #pragma unroll
@@ -139,8 +139,7 @@ __device__ __forceinline__ void sr_lin_final_dev(const sr_lin_args& a, const dou
         if (a.kp == nullptr) kxx = a.sf2[d];
         else {
             const double* kp = a.kp + (long)d * SR_KP(a.D);
-            for (int j = 0; j < a.D; ++j)
-                x2a = fma((kp[3 + a.D + j] * kp[1] + kp[3 + 2 * a.D + j]) * sr_lin_x(a, j), sr_lin_x(a, j), x2a);
+            for (int j = 0; j < a.D; ++j) x2a = sr_kxx_term(kp, a.D, j, sr_lin_x(a, j), x2a);
             kxx = kp[2] * kp[1] + x2a;
         }
         double v = kxx - dt[0];
@@ -152,8 +151,7 @@ __device__ __forceinline__ void sr_lin_final_dev(const sr_lin_args& a, const dou
         if (jac_mu) jac_mu[d * a.D + t] = tot[1 + t];
         double dkxx = 0.0;
         if (a.kp != nullptr) {
-            const double* kp = a.kp + (long)d * SR_KP(a.D);
-            dkxx = 2.0 * (kp[3 + a.D + t] * kp[1] + kp[3 + 2 * a.D + t]) * sr_lin_x(a, t);
+            dkxx = sr_dkxx(a.kp + (long)d * SR_KP(a.D), a.D, t, sr_lin_x(a, t));
         }
         if (a.jac_var) a.jac_var[d * a.D + t] = dkxx - 2.0 * dt[1 + t];
     }
@@ -219,8 +217,7 @@ __device__ __forceinline__ void sr_lin_final_wave(const sr_lin_args& a, const do
         if (a.kp == nullptr) kxx = a.sf2[d];
         else {
             const double* kp = a.kp + (long)d * SR_KP(a.D);
-            for (int j = 0; j < a.D; ++j)
-                x2a = fma((kp[3 + a.D + j] * kp[1] + kp[3 + 2 * a.D + j]) * sr_lin_x(a, j), sr_lin_x(a, j), x2a);
+            for (int j = 0; j < a.D; ++j) x2a = sr_kxx_term(kp, a.D, j, sr_lin_x(a, j), x2a);
             kxx = kp[2] * kp[1] + x2a;
         }
         double v = kxx - dt[0];
@@ -232,8 +229,7 @@ __device__ __forceinline__ void sr_lin_final_wave(const sr_lin_args& a, const do
         if (jac_mu) jac_mu[d * a.D + lane] = tot[1 + lane];
         double dkxx = 0.0;
         if (a.kp != nullptr) {
-            const double* kp = a.kp + (long)d * SR_KP(a.D);
-            dkxx = 2.0 * (kp[3 + a.D + lane] * kp[1] + kp[3 + 2 * a.D + lane]) * sr_lin_x(a, lane);
+            dkxx = sr_dkxx(a.kp + (long)d * SR_KP(a.D), a.D, lane, sr_lin_x(a, lane));
         }
         if (a.jac_var) a.jac_var[d * a.D + lane] = dkxx - 2.0 * dt[1 + lane];
     }

@@ -100,14 +100,8 @@ __global__ __launch_bounds__(256) void sr_linearize_kernel(sr_lin_args a) {
     }
 }
 
-// General kernel family of sr_common.h (Matern-5/2, linear x stationary + linear; the kernels the reference's
-// journal experiments use, ssm_gpy/gp_models_utils_casadi.py:43-157), differentiated by hand -- the reference
-// leaves these derivatives to CasADi's AD.  With u_j = s_j^2 (x_j - z_j), c = c0 + sum a_j x_j z_j,
-// g = kappa'(r)/r, h = g'(r)/r   (RBF: g = -kappa, h = kappa;  Matern-5/2: g = -5/3 (1 + sqrt5 r) e, h = 25/3 e,
-// e = exp(-sqrt5 r)):
-//   d k/dx_j       = a_j z_j v kappa + c v g u_j + b_j z_j
-//   d2 k/dx_j dx_l = v g (a_j z_j u_l + a_l z_l u_j) + c v (h u_j u_l + g s_j^2 delta_jl)
-//   d var/dx_j     = 2 (a_j v + b_j) x_j - 2 sum_i G_i d k_i/dx_j ,   G = K_y^-1 k*
+// General kernel family (Matern-5/2, linear x stationary + linear; the kernels the reference's journal experiments use):
+// the sums over the training rows of sr_dk and sr_d2k (sr_kernel_dev.h).
 template <int DT>
 __global__ __launch_bounds__(256) void sr_linearize_general_kernel(sr_lin_args a) {
     constexpr int NH = DT * (DT + 1) / 2;
@@ -115,20 +109,15 @@ __global__ __launch_bounds__(256) void sr_linearize_general_kernel(sr_lin_args a
     __shared__ double red[4][NACC];
     const int d = blockIdx.x;
     const int off = a.Np - a.N;
-    const double* kp = a.kp + (long)d * SR_KP(a.D);
-    const int kind = (int)kp[0];
-    const double var = kp[1], c0 = kp[2];
+    sr_kpar<DT> P;
+    P.load(a.kp + (long)d * SR_KP(a.D), a.D);
+    const double var = P.v, c0 = P.c0;
+    const double *s2 = P.s2, *av = P.a, *bv = P.b;
     const double* G = a.g + (long)d * a.Np;
     const double* al = a.alpha + (long)d * a.Np;
-    double s2[DT], av[DT], bv[DT], x[DT], acc[NACC];
+    double x[DT], acc[NACC];
 #pragma unroll
-    for (int j = 0; j < DT; ++j) {
-        const double sj = (j < a.D) ? kp[3 + j] : 0.0;
-        s2[j] = sj * sj;
-        av[j] = (j < a.D) ? kp[3 + a.D + j] : 0.0;
-        bv[j] = (j < a.D) ? kp[3 + 2 * a.D + j] : 0.0;
-        x[j] = (j < a.D) ? a.x[j] : 0.0;
-    }
+    for (int j = 0; j < DT; ++j) x[j] = (j < a.D) ? a.x[j] : 0.0;
 #pragma unroll
     for (int q = 0; q < NACC; ++q) acc[q] = 0.0;
     for (int i = threadIdx.x; i < a.N; i += 256) {
@@ -142,31 +131,18 @@ __global__ __launch_bounds__(256) void sr_linearize_general_kernel(sr_lin_args a
             la = fma(av[j] * x[j], z[j], la);
         }
         double kap, g, h;
-        if (kind == 0) {
-            kap = exp(-0.5 * r2);
-            g = -kap;
-            h = kap;
-        } else {
-            const double rr = sqrt(r2);
-            const double e = exp(-2.23606797749978969641 * rr);
-            kap = (1.0 + 2.23606797749978969641 * rr + (5.0 / 3.0) * r2) * e;
-            g = -(5.0 / 3.0) * (1.0 + 2.23606797749978969641 * rr) * e;
-            h = (25.0 / 3.0) * e;
-        }
+        sr_radial<2>(P.kind, r2, kap, g, h);
         const double pre = (c0 + la) * var;
         const double Gi = G[i + off], w = al[i + off];
         const double vk = var * kap, pg = pre * g, ph = pre * h, vg = var * g;
         int q = DT;
 #pragma unroll
         for (int j = 0; j < DT; ++j) {
-            const double azj = av[j] * z[j];
-            acc[j] = fma(Gi, fma(vk, azj, fma(pg, u[j], bv[j] * z[j])), acc[j]);
+            acc[j] = fma(Gi, sr_dk(j, u, z, av, bv, vk, pg), acc[j]);
 #pragma unroll
             for (int c = 0; c < DT; ++c)
                 if (c >= j) {
-                    double hv = fma(vg, fma(azj, u[c], av[c] * z[c] * u[j]), ph * u[j] * u[c]);
-                    if (c == j) hv = fma(pg, s2[j], hv);
-                    acc[q] = fma(w, hv, acc[q]);
+                    acc[q] = fma(w, sr_d2k(j, c, u, z, av, s2, vg, pg, ph), acc[q]);
                     ++q;
                 }
         }
@@ -184,7 +160,7 @@ __global__ __launch_bounds__(256) void sr_linearize_general_kernel(sr_lin_args a
 #pragma unroll
         for (int j = 0; j < DT; ++j) {
             if (j < a.D)
-                a.jac_var[d * a.D + j] = 2.0 * (av[j] * var + bv[j]) * x[j] -
+                a.jac_var[d * a.D + j] = 2.0 * (av[j] * var + bv[j]) * x[j] -         // (sr_dkxx from the loaded a_j, b_j)
                                          2.0 * (red[0][j] + red[1][j] + red[2][j] + red[3][j]);
 #pragma unroll
             for (int c = 0; c < DT; ++c)
@@ -257,17 +233,14 @@ __global__ __launch_bounds__(256) void sr_lin_columns_kernel(sr_lin_args a, int 
                         ++q;
                     }
             }
-        } else {                                         // general family, formulas of sr_linearize_general_kernel
-            const double* kp = a.kp + (long)d * SR_KP(a.D);
-            const int kind = (int)kp[0];
-            const double var = kp[1], c0 = kp[2];
-            double s2[DT], av[DT], bv[DT], la = 0.0, lb = 0.0;
+        } else {                                         // general family
+            sr_kpar<DT> P;
+            P.load(a.kp + (long)d * SR_KP(a.D), a.D);
+            const double var = P.v, c0 = P.c0;
+            const double *s2 = P.s2, *av = P.a, *bv = P.b;
+            double la = 0.0, lb = 0.0;
 #pragma unroll
             for (int j = 0; j < DT; ++j) {
-                const double sj = (j < a.D) ? kp[3 + j] : 0.0;
-                s2[j] = sj * sj;
-                av[j] = (j < a.D) ? kp[3 + a.D + j] : 0.0;
-                bv[j] = (j < a.D) ? kp[3 + 2 * a.D + j] : 0.0;
                 z[j] = (j < a.D) ? a.Z[(long)i * a.D + j] : 0.0;
                 x[j] = (j < a.D) ? sr_lin_x(a, j) : 0.0;
                 const double df = x[j] - z[j];
@@ -277,17 +250,7 @@ __global__ __launch_bounds__(256) void sr_lin_columns_kernel(sr_lin_args a, int 
                 lb = fma(bv[j] * x[j], z[j], lb);
             }
             double kap, g, h;
-            if (kind == 0) {
-                kap = exp(-0.5 * r2);
-                g = -kap;
-                h = kap;
-            } else {
-                const double rr = sqrt(r2);
-                const double e = exp(-2.23606797749978969641 * rr);
-                kap = (1.0 + 2.23606797749978969641 * rr + (5.0 / 3.0) * r2) * e;
-                g = -(5.0 / 3.0) * (1.0 + 2.23606797749978969641 * rr) * e;
-                h = (25.0 / 3.0) * e;
-            }
+            sr_radial<2>(P.kind, r2, kap, g, h);
             const double pre = (c0 + la) * var;
             const double k = fma(pre, kap, lb);
             col[0] = k;
@@ -296,16 +259,13 @@ __global__ __launch_bounds__(256) void sr_lin_columns_kernel(sr_lin_args a, int 
             int q = 1 + DT;
 #pragma unroll
             for (int j = 0; j < DT; ++j) {
-                const double azj = av[j] * z[j];
-                const double dk = fma(vk, azj, fma(pg, u[j], bv[j] * z[j]));
+                const double dk = sr_dk(j, u, z, av, bv, vk, pg);
                 col[1 + j] = dk;
                 acc[1 + j] = w * dk;
 #pragma unroll
                 for (int c = 0; c < DT; ++c)
                     if (c >= j) {
-                        double hv = fma(vg, fma(azj, u[c], av[c] * z[c] * u[j]), ph * u[j] * u[c]);
-                        if (c == j) hv = fma(pg, s2[j], hv);
-                        acc[q] = w * hv;
+                        acc[q] = w * sr_d2k(j, c, u, z, av, s2, vg, pg, ph);
                         ++q;
                     }
             }

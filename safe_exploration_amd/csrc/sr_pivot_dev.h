@@ -1,5 +1,5 @@
 // sr_pivot_dev.h -- scalar helpers shared by sr_factor.hip and sr_append.hip: the pivot chains (diagonal-block kernel of the
-// Cholesky, one-point row append) and the radial part of the general kernel family.
+// Cholesky, one-point row append).
 #pragma once
 #include "sr_common.h"
 
@@ -25,12 +25,4 @@ __device__ __forceinline__ void sr_sqrt_rsqrt(double d, double& sd, double& inv)
     h = fma(h, r2, h);
     sd = g;
     inv = h + h;
-}
-
-
-// radial part kappa(r) of the general kernel family (sr_common.h): 0 RBF, else Matern-5/2
-__device__ __forceinline__ double sr_kappa(int kind, double r2) {
-    if (kind == 0) return exp(-0.5 * r2);
-    const double r = sqrt(r2);
-    return (1.0 + 2.23606797749978969641 * r + (5.0 / 3.0) * r2) * exp(-2.23606797749978969641 * r);
 }

@@ -127,7 +127,7 @@ __global__ __launch_bounds__(256) void sr_kstar_kernel(sr_kstar_args a) {
         }
 }
 
-// K1g: the same pass for the general kernel family of sr_common.h (Matern-5/2, linear x stationary +
+// K1g: the same pass for the general kernel family of sr_kernel_dev.h (Matern-5/2, linear x stationary +
 // linear).  Inputs stay unscaled in LDS because the linear parts need x_j z_j; per pair
 //   k = (c0 + sum a_j x_j z_j) v kappa(r) + sum b_j x_j z_j
 //   dk/dx_j = a_j z_j v kappa + (c0 + ...) v g (x_j - z_j) s_j^2 + b_j z_j ,  g = kappa'(r)/r
@@ -140,23 +140,20 @@ __global__ __launch_bounds__(256) void sr_kstar_general_kernel(sr_kstar_args a) 
     const long t = (long)blockIdx.x * 256 + threadIdx.x;
     const bool live = t < a.T;
     const bool inpad = t < (a.Tw ? a.Tw : a.Tp);
-    const double* kp = a.kp + (long)d * SR_KP(a.D);
-    const int kind = (int)kp[0];
-    const double var = kp[1], c0 = kp[2];
-    double s2[DT], ax[DT], bx[DT], av[DT], bv[DT], x[DT], g[DT];
+    sr_kpar<DT> P;
+    P.load(a.kp + (long)d * SR_KP(a.D), a.D);
+    const double var = P.v, c0 = P.c0;
+    const double *s2 = P.s2, *av = P.a, *bv = P.b;
+    double ax[DT], bx[DT], x[DT], g[DT];
     double kxx = c0 * var;
 #pragma unroll
     for (int j = 0; j < DT; ++j) {
-        const double sj = (j < a.D) ? kp[3 + j] : 0.0;
-        av[j] = (j < a.D) ? kp[3 + a.D + j] : 0.0;
-        bv[j] = (j < a.D) ? kp[3 + 2 * a.D + j] : 0.0;
         double xv = 0.0;
         if (live && j < a.D) xv = (j < a.na) ? a.xa[t * a.lda + j] : a.xb[t * a.ldb + (j - a.na)];
         x[j] = xv;
-        s2[j] = sj * sj;
         ax[j] = av[j] * xv;
         bx[j] = bv[j] * xv;
-        kxx = fma(ax[j] * var + bx[j], xv, kxx);
+        kxx = fma(ax[j] * var + bx[j], xv, kxx);         // (this kernel's own order: a_j x_j and b_j x_j serve the pairs too)
         g[j] = 0.0;
     }
     double mu = 0.0;
@@ -191,16 +188,8 @@ __global__ __launch_bounds__(256) void sr_kstar_general_kernel(sr_kstar_args a) 
                     la = fma(ax[j], z, la);
                     lb = fma(bx[j], z, lb);
                 }
-                double kap, gk;              // kappa and kappa'(r)/r
-                if (kind == 0) {
-                    kap = exp(-0.5 * r2);
-                    gk = -kap;
-                } else {
-                    const double rr = sqrt(r2);
-                    const double e = exp(-2.23606797749978969641 * rr);
-                    kap = (1.0 + 2.23606797749978969641 * rr + (5.0 / 3.0) * r2) * e;
-                    gk = -(5.0 / 3.0) * (1.0 + 2.23606797749978969641 * rr) * e;
-                }
+                double kap, gk, hk;          // kappa and kappa'(r)/r
+                sr_radial<1>(P.kind, r2, kap, gk, hk);
                 const double pre = (c0 + la) * var;
                 const double k = live ? fma(pre, kap, lb) : 0.0;
                 ks_col[(long)(i0 + r) * a.Tp] = k;

@@ -9,12 +9,13 @@
 //   KF  sr_grad_finish    : jac_var[t][d][j] = dk(x,x)/dx_j - 2 sum_kb gpart (row blocks in ascending order)
 //
 // RBF: dk_i/dx_j = k_i (z_ij - x_j) / l_j^2 (the 1 / l_j^2 goes into the finish), dk(x,x)/dx = 0.
-// General family (sr_common.h): dk_i/dx_j = a_j z_ij v kappa + c v g u_j + b_j z_ij, u_j = s_j^2 (x_j - z_ij),
+// General family (sr_kernel_dev.h): dk_i/dx_j = a_j z_ij v kappa + c v g u_j + b_j z_ij, u_j = s_j^2 (x_j - z_ij),
 // c = c0 + sum a_j x_j z_ij, g = kappa'(r)/r; dk(x,x)/dx_j = 2 (a_j v + b_j) x_j  (the closed forms of
 // sr_linearize_general_kernel, there for one query).
 // mu, var and d mu/dx come from the K* pass and sr_finalize exactly as in sr_gp_predict.
 // sr_gp_linearize_batch (below) adds the Hessian of the mean behind that pass: KH / KHF.
 #include "sr_handle.h"
+#include "sr_kernel_dev.h"
 using namespace srh;
 
 // ------------------------------------------------------------------------------------------------
@@ -120,18 +121,8 @@ __device__ __forceinline__ void grad_tile(const sr_grad_args& a, int d, int x, i
         for (int j = 0; j < DT; ++j) zs[threadIdx.x * DT + j] = (i >= 0 && j < D) ? a.Z[(long)i * D + j] : 0.0;
     }
     __syncthreads();
-    double c0 = 0.0, vv = 0.0, s2[DT], av[DT], bv[DT];
-    int kind = 0;
-    if (GEN) {
-        kind = (int)kp[0]; vv = kp[1]; c0 = kp[2];
-#pragma unroll
-        for (int j = 0; j < DT; ++j) {
-            const double sj = (j < D) ? kp[3 + j] : 0.0;
-            s2[j] = sj * sj;
-            av[j] = (j < D) ? kp[3 + D + j] : 0.0;
-            bv[j] = (j < D) ? kp[3 + 2 * D + j] : 0.0;
-        }
-    }
+    sr_kpar<DT> P;                                       // (read by the general form only)
+    if (GEN) P.load(kp, D);
 #pragma unroll
     for (int ni = 0; ni < 4; ++ni) {
         const int col = srt::acc_col(wn, ni, lane);
@@ -162,24 +153,16 @@ __device__ __forceinline__ void grad_tile(const sr_grad_args& a, int d, int x, i
 #pragma unroll
                     for (int j = 0; j < DT; ++j) {
                         const double df = xq[j] - zs[row * DT + j];
-                        r2 = fma(df * s2[j], df, r2);
-                        la = fma(av[j] * xq[j], zs[row * DT + j], la);
+                        r2 = fma(df * P.s2[j], df, r2);
+                        la = fma(P.a[j] * xq[j], zs[row * DT + j], la);
                     }
-                    double kap, gk;                      // kappa and kappa'(r)/r
-                    if (kind == 0) {
-                        kap = exp(-0.5 * r2);
-                        gk = -kap;
-                    } else {
-                        const double rr = sqrt(r2);
-                        const double e = exp(-2.23606797749978969641 * rr);
-                        kap = (1.0 + 2.23606797749978969641 * rr + (5.0 / 3.0) * r2) * e;
-                        gk = -(5.0 / 3.0) * (1.0 + 2.23606797749978969641 * rr) * e;
-                    }
-                    const double gvk = g * vv * kap, gcg = g * (c0 + la) * vv * gk;
+                    double kap, gk, hk;                  // kappa and kappa'(r)/r
+                    sr_radial<1>(P.kind, r2, kap, gk, hk);
+                    const double gvk = g * P.v * kap, gcg = g * (P.c0 + la) * P.v * gk;
 #pragma unroll
                     for (int j = 0; j < DT; ++j) {
                         const double z = zs[row * DT + j];
-                        sum[j] = fma(gvk * av[j] + g * bv[j], z, fma(gcg * s2[j], xq[j] - z, sum[j]));
+                        sum[j] = fma(gvk * P.a[j] + g * P.b[j], z, fma(gcg * P.s2[j], xq[j] - z, sum[j]));
                     }
                 }
             }
@@ -235,8 +218,7 @@ __global__ __launch_bounds__(256) void sr_grad_finish_kernel(const double* __res
         for (int kb = 0; kb < nrb; ++kb) s += p[(long)kb * D * Tp];
         double out;
         if (kp) {
-            const double* k = kp + (long)d * SR_KP(D);
-            out = 2.0 * (k[3 + D + j] * k[1] + k[3 + 2 * D + j]) * Xq[t * D + j] - 2.0 * s;
+            out = sr_dkxx(kp + (long)d * SR_KP(D), D, j, Xq[t * D + j]) - 2.0 * s;
         } else {
             const double l = ls[d * D + j];
             out = -2.0 * s / (l * l);
@@ -363,7 +345,7 @@ extern "C" int sr_gp_predict_grad(sr_gp_t h, const double* Xq, long T, double* m
 //         RBF      H_jc = sum_i alpha_i k_ti (z_ij - x_j)(z_ic - x_c) / (l_j^2 l_c^2)  [- delta_jc / l_j^2 sum_i alpha_i k_ti]
 //                  k_ti read from the chunk's K* slab (the K* pass of grad_pass left it there);
 //         general  H_jl = sum_i alpha_i [v g (a_j z_j u_l + a_l z_l u_j) + c v (h u_j u_l + g s_j^2 delta_jl)]
-//                  (the closed form of sr_linearize_general_kernel, sr_linearize.hip; kappa, g and h recomputed per pair).
+//                  (sr_d2k of sr_kernel_dev.h; g and h recomputed per pair).
 //       Summed in centred coordinates z_i - x_t: the expanded form W^T [1 | Z | Z Z^T] would be one matrix product, but it
 //       cancels terms of size |x|^2 sum |alpha k| down to the result and loses the digits the fp64 bars need.
 //       One thread per (query, output); Z rows and alpha staged through LDS (broadcast reads); the upper triangle of the
@@ -391,22 +373,15 @@ __global__ __launch_bounds__(256) void sr_hess_kernel(sr_hess_args a) {
     const long t = (long)blockIdx.x * 256 + threadIdx.x;
     const bool live = t < a.T;
     const int D = a.D, off = a.Np - a.N;
-    double x[DT], sc[DT], av[DT], acc[NH], sw = 0.0;     // sc: 1 / l_j^2 (RBF) or s_j^2 (general)
-    int kind = 0;
-    double vv = 0.0, c0 = 0.0;
-    const double* kp = GEN ? a.kp + (long)d * SR_KP(D) : nullptr;
-    if (GEN) { kind = (int)kp[0]; vv = kp[1]; c0 = kp[2]; }
+    double x[DT], il2[DT], acc[NH], sw = 0.0;            // il2: 1 / l_j^2 (RBF)
+    sr_kpar<DT> P;
+    if (GEN) P.load(a.kp + (long)d * SR_KP(D), D);
 #pragma unroll
     for (int j = 0; j < DT; ++j) {
         x[j] = (live && j < D) ? a.Xq[t * D + j] : 0.0;
-        if (GEN) {
-            const double sj = (j < D) ? kp[3 + j] : 0.0;
-            sc[j] = sj * sj;
-            av[j] = (j < D) ? kp[3 + D + j] : 0.0;
-        } else {
+        if (!GEN) {
             const double l = (j < D) ? a.ls[d * D + j] : 1.0;
-            sc[j] = (j < D) ? 1.0 / (l * l) : 0.0;
-            av[j] = 0.0;
+            il2[j] = (j < D) ? 1.0 / (l * l) : 0.0;
         }
     }
 #pragma unroll
@@ -433,7 +408,7 @@ __global__ __launch_bounds__(256) void sr_hess_kernel(sr_hess_args a) {
                 const double w = al[r] * ks[(long)(i0 + r) * a.Tp];
                 double df[DT];
 #pragma unroll
-                for (int j = 0; j < DT; ++j) df[j] = (zs[r * DT + j] - x[j]) * sc[j];
+                for (int j = 0; j < DT; ++j) df[j] = (zs[r * DT + j] - x[j]) * il2[j];
                 sw += w;
                 int q = 0;
 #pragma unroll
@@ -450,35 +425,23 @@ __global__ __launch_bounds__(256) void sr_hess_kernel(sr_hess_args a) {
                 for (int j = 0; j < DT; ++j) {
                     z[j] = zs[r * DT + j];
                     const double df = x[j] - z[j];
-                    u[j] = sc[j] * df;
+                    u[j] = P.s2[j] * df;
                     r2 = fma(u[j], df, r2);
-                    la = fma(av[j] * x[j], z[j], la);
+                    la = fma(P.a[j] * x[j], z[j], la);
                 }
-                double g, h;                      // kappa'(r)/r and g'(r)/r (kappa itself is not needed)
-                if (kind == 0) {
-                    h = exp(-0.5 * r2);
-                    g = -h;
-                } else {
-                    const double rr = sqrt(r2);
-                    const double e = exp(-2.23606797749978969641 * rr);
-                    g = -(5.0 / 3.0) * (1.0 + 2.23606797749978969641 * rr) * e;
-                    h = (25.0 / 3.0) * e;
-                }
-                const double pre = (c0 + la) * vv;
+                double kap, g, h;                 // kappa'(r)/r and g'(r)/r (kappa itself is not needed: nobody reads it)
+                sr_radial<2>(P.kind, r2, kap, g, h);
+                const double pre = (P.c0 + la) * P.v;
                 const double w = al[r];
-                const double vg = vv * g, pg = pre * g, ph = pre * h;
+                const double vg = P.v * g, pg = pre * g, ph = pre * h;
                 int q = 0;
 #pragma unroll
-                for (int j = 0; j < DT; ++j) {
-                    const double azj = av[j] * z[j];
+                for (int j = 0; j < DT; ++j)
 #pragma unroll
                     for (int c = j; c < DT; ++c) {
-                        double hv = fma(vg, fma(azj, u[c], av[c] * z[c] * u[j]), ph * u[j] * u[c]);
-                        if (c == j) hv = fma(pg, sc[j], hv);
-                        acc[q] = fma(w, hv, acc[q]);
+                        acc[q] = fma(w, sr_d2k(j, c, u, z, P.a, P.s2, vg, pg, ph), acc[q]);
                         ++q;
                     }
-                }
             }
         }
     }

@@ -15,7 +15,7 @@
 // inside one launch: the pivot row's L and var are read by everyone and written by no one (a taken row is never updated),
 // a row's var / L / taken mark belong to the workgroup of that row.
 #include "sr_handle.h"
-#include "sr_pivot_dev.h"
+#include "sr_kernel_dev.h"
 #include <climits>
 using namespace srh;
 
@@ -53,18 +53,7 @@ __device__ __forceinline__ double sel_kernel(const sr_sel_args& a, int d, const 
         }
         return a.sf2[d] * exp(-0.5 * r2);
     }
-    const double* kp = a.kp + (long)d * SR_KP(D);
-    const int kind = (int)kp[0];
-    const double v = kp[1], c0 = kp[2];
-    const double *sv = kp + 3, *av = kp + 3 + D, *bv = kp + 3 + 2 * D;
-    double r2 = 0.0, la = 0.0, lb = 0.0;
-    for (int c = 0; c < D; ++c) {
-        const double t = (xi[c] - xj[c]) * sv[c];
-        r2 = fma(t, t, r2);
-        la = fma(av[c] * xi[c], xj[c], la);
-        lb = fma(bv[c] * xi[c], xj[c], lb);
-    }
-    return (c0 + la) * v * sr_kappa(kind, diag ? 0.0 : r2) + lb;
+    return sr_kpair(sr_kview(a.kp + (long)d * SR_KP(D), D), D, xi, xj, diag);
 }
 
 __device__ __forceinline__ double sel_clip(double v) { return (v > SR_VAR_CLIP) ? v : SR_VAR_CLIP; }   // as sr_finalize

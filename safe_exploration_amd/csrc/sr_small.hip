@@ -54,7 +54,7 @@ __global__ __launch_bounds__(1024) void sr_gp_small_kernel(sr_kstar_args a, cons
     sr_small_publish(a, tid);
 }
 
-// General kernel family (Matern-5/2, linear x stationary + linear: sr_common.h; the kernels of the reference's
+// General kernel family (Matern-5/2, linear x stationary + linear: sr_kernel_dev.h; the kernels of the reference's
 // journal experiments) through the same one-launch pass.  k = c v kappa + l with c = c0 + sum a x z, l = sum b x z:
 //   dk/dx_j = a_j z_j v kappa + c v g s_j^2 (x_j - z_j) + b_j z_j ,  g = kappa'(r)/r
 // so the mean-Jacobian needs four products against M[i] = alpha_i [1, z_i] instead of one:
@@ -83,22 +83,18 @@ __global__ __launch_bounds__(1024) void sr_gp_small_general_kernel(sr_kstar_args
     const long t0 = (long)blockIdx.x * SR_FQ;
     const int off = NP - a.N;
     const double* kp = a.kp + (long)d * SR_KP(a.D);
-    const int kind = (int)kp[0];
-    const double vv = kp[1], c0 = kp[2];
     const bool live = t0 + ln < a.T;
 
     // per lane: the query; the kernel parameters s_j^2, a_j, b_j are wavefront-uniform
     double x[DT];
-    double s2[DT], av[DT], bv[DT];
 #pragma unroll
     for (int j = 0; j < DT; ++j) {
         x[j] = 0.0;
         if (live && j < a.D) x[j] = a.xv_on ? a.xv[j] : ((j < a.na) ? a.xa[(t0 + ln) * a.lda + j] : a.xb[(t0 + ln) * a.ldb + (j - a.na)]);
-        const double sj = (j < a.D) ? kp[3 + j] : 0.0;
-        s2[j] = sj * sj;
-        av[j] = (j < a.D) ? kp[3 + a.D + j] : 0.0;
-        bv[j] = (j < a.D) ? kp[3 + 2 * a.D + j] : 0.0;
     }
+    sr_kpar<DT> P;                                       // (after the query: loaded first, <256, 8> spills 12 registers, not 8)
+    P.load(kp, a.D);
+    const double vv = P.v, c0 = P.c0;
     sr_d4 acc[4];
 #pragma unroll
     for (int q = 0; q < 4; ++q) acc[q] = sr_d4{0.0, 0.0, 0.0, 0.0};
@@ -112,21 +108,13 @@ __global__ __launch_bounds__(1024) void sr_gp_small_general_kernel(sr_kstar_args
         for (int j = 0; j < DT; ++j) {
             const double z = (valid && j < a.D) ? a.Z[(long)(i - off) * a.D + j] : 0.0;
             const double df = x[j] - z;
-            r2 = fma(df * s2[j], df, r2);
-            la = fma(av[j] * x[j], z, la);
-            lb = fma(bv[j] * x[j], z, lb);
+            r2 = fma(df * P.s2[j], df, r2);
+            la = fma(P.a[j] * x[j], z, la);
+            lb = fma(P.b[j] * x[j], z, lb);
             if (ln == j + 1) bfrag = al * z;
         }
-        double kap, g;
-        if (kind == 0) {
-            kap = exp(-0.5 * r2);
-            g = -kap;
-        } else {
-            const double rr = sqrt(r2);
-            const double e = exp(-2.23606797749978969641 * rr);
-            kap = (1.0 + 2.23606797749978969641 * rr + (5.0 / 3.0) * r2) * e;
-            g = -(5.0 / 3.0) * (1.0 + 2.23606797749978969641 * rr) * e;
-        }
+        double kap, g, h;
+        sr_radial<1>(P.kind, r2, kap, g, h);
         const bool on = valid && live;
         const double cc = c0 + la;
         const double k = on ? fma(cc * vv, kap, lb) : 0.0;
@@ -164,7 +152,7 @@ __global__ __launch_bounds__(1024) void sr_gp_small_general_kernel(sr_kstar_args
             if (j == DT) {
                 mu[(t0 + t) * a.n_out + d] = Rs[0][t][0];
             } else if (jac && j < a.D) {
-                const double sj = kp[3 + j], aj = kp[3 + a.D + j], bj = kp[3 + 2 * a.D + j];
+                const double sj = sr_kp_s(kp, j), aj = sr_kp_a(kp, a.D, j), bj = sr_kp_b(kp, a.D, j);
                 jac[((t0 + t) * a.n_out + d) * a.D + j] =
                     aj * vv * Rs[1][t][1 + j] + vv * sj * sj * (xq[t][j] * Rs[2][t][0] - Rs[2][t][1 + j]) +
                     bj * Rs[3][t][1 + j];
@@ -176,10 +164,7 @@ __global__ __launch_bounds__(1024) void sr_gp_small_general_kernel(sr_kstar_args
 #pragma unroll
         for (int sidx = 0; sidx < NSTRIP; ++sidx) qn += redC[sidx][tid];
         double kxx = c0 * vv;
-        for (int j = 0; j < a.D; ++j) {
-            const double xv = xq[tid][j];
-            kxx = fma((kp[3 + a.D + j] * vv + kp[3 + 2 * a.D + j]) * xv, xv, kxx);
-        }
+        for (int j = 0; j < a.D; ++j) kxx = sr_kxx_term(kp, a.D, j, xq[tid][j], kxx);
         double v = kxx - qn;
         if (!(v > SR_VAR_CLIP)) v = SR_VAR_CLIP;
         var[(t0 + tid) * a.n_out + d] = v;

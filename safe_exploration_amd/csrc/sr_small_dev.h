@@ -360,11 +360,11 @@ __device__ __forceinline__ void sr_small_outputs(const sr_kstar_args& a, const s
 }
 
 // ------------------------------------------------------------------------------------------------------------------
-// GENERAL kernel family (sr_common.h: k = (c0 + sum a x z) v kappa(r) + sum b x z, kappa in {RBF, Matern-5/2} -- the
+// GENERAL kernel family (sr_kernel_dev.h: k = (c0 + sum a x z) v kappa(r) + sum b x z, kappa in {RBF, Matern-5/2} -- the
 // reference's mat52 / lin_rbf / lin_mat52, ssm_gpy/gp_models_utils_casadi.py:43-157, which its journal experiments run:
 // experiments/journal_experiment_configs/defaultconfig_episode.py:39), ONE query with second-order outputs, on the same
 // MFMA tile as the ARD-RBF form above.  With u_j = s_j^2 (x_j - z_j), c = c0 + sum a x z, g = kappa'/r, h = g'/r
-// (sr_linearize.hip):
+// (sr_kernel_dev.h):
 //   dk/dx_j        = a_j z_j v kappa + c v g u_j + b_j z_j
 //   d2k/dx_j dx_l  = v g (a_j z_j u_l + a_l z_l u_j) + c v (h u_j u_l + g s_j^2 delta_jl)
 // Two products against the SAME right-hand side M[i][:] = alpha_i [1, z_i - x] (16 columns, 1 + D used):
@@ -381,21 +381,6 @@ struct sr_gen_lds {
     sr_small_lds<NP, DT> s;     // ks, xq (row 0: the query, UNSCALED), pA, Rs (P1), pB, redC
     double (*pA2)[256];         // per-wavefront partial P2
     double (*Rs2)[16];          // P2
-};
-// packed parameters of one output (SR_KP(D) doubles: kappa id, v, c0, s[D], a[D], b[D]) -> what the evaluation uses
-template <int DT>
-struct sr_gen_par {
-    int kind; double v, c0, s2[DT], a[DT], b[DT];
-    __device__ __forceinline__ void load(const double* kp, int D) {
-        kind = (int)kp[0]; v = kp[1]; c0 = kp[2];
-#pragma unroll
-        for (int j = 0; j < DT; ++j) {
-            const double sj = (j < D) ? kp[3 + j] : 0.0;
-            s2[j] = sj * sj;
-            a[j] = (j < D) ? kp[3 + D + j] : 0.0;
-            b[j] = (j < D) ? kp[3 + 2 * D + j] : 0.0;
-        }
-    }
 };
 // rows for KEEP: z_ij UNSCALED, alpha_i (0 on padding rows)
 template <int NP, int DT>
@@ -425,7 +410,7 @@ __device__ __forceinline__ void sr_small_phase_a_gen(const sr_kstar_args& a, int
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int lk = lane >> 4, ln = lane & 15;
     const int off = NP - a.N;
-    sr_gen_par<DT> P;
+    sr_kpar<DT> P;
     P.load(kp, a.D);
     double x[DT];
 #pragma unroll
@@ -457,17 +442,7 @@ __device__ __forceinline__ void sr_small_phase_a_gen(const sr_kstar_args& a, int
             lb = fma(P.b[j] * x[j], z[j], lb);
         }
         double kap, g, hh;
-        if (P.kind == 0) {
-            kap = exp(-0.5 * r2);
-            g = -kap;
-            hh = kap;
-        } else {
-            const double rr = sqrt(r2);
-            const double e = exp(-2.23606797749978969641 * rr);
-            kap = (1.0 + 2.23606797749978969641 * rr + (5.0 / 3.0) * r2) * e;
-            g = -(5.0 / 3.0) * (1.0 + 2.23606797749978969641 * rr) * e;
-            hh = (25.0 / 3.0) * e;
-        }
+        sr_radial<2>(P.kind, r2, kap, g, hh);
         const double pre = (P.c0 + la) * P.v;
         k0 = valid ? fma(pre, kap, lb) : 0.0;
         vk = valid ? P.v * kap : 0.0;
@@ -562,22 +537,22 @@ __device__ __forceinline__ double sr_gen_record_elem(int e, int D, const sr_gen_
     if (e == 0) return R1[0][0];
     if (e == 1) {
         double kxx = c0 * v;
-        for (int j = 0; j < D; ++j) kxx = fma((kp[3 + D + j] * v + kp[3 + 2 * D + j]) * x[j], x[j], kxx);
+        for (int j = 0; j < D; ++j) kxx = sr_kxx_term(kp, D, j, x[j], kxx);
         return kxx;
     }
     if (e < 2 + D) return R1[1 + (e - 2)][0];
     if (e < 2 + 2 * D) {
         const int j = e - (2 + D);
-        return 2.0 * (kp[3 + D + j] * v + kp[3 + 2 * D + j]) * x[j];
+        return sr_dkxx(kp, D, j, x[j]);
     }
     if (e < 2 + 2 * D + D * D) {
         const int q = e - (2 + 2 * D);
         const int j = min(q / D, q % D), l = max(q / D, q % D);       // (j <= l: the matrix comes out exactly symmetric)
-        const double aj = kp[3 + D + j], al = kp[3 + D + l], sl = kp[3 + l];
+        const double aj = sr_kp_a(kp, D, j), al = sr_kp_a(kp, D, l), sl = sr_kp_s(kp, l);
         const double s1jl = fma(x[j], R2[1 + l][0], R2[1 + l][1 + j]);
         const double s1lj = fma(x[l], R2[1 + j][0], R2[1 + j][1 + l]);
         double hv = aj * s1jl + al * s1lj - sl * sl * R1[9 + j][1 + l];
-        if (j == l) hv = fma(kp[3 + j] * kp[3 + j], R1[8][0], hv);
+        if (j == l) hv = fma(sr_kp_s(kp, j) * sr_kp_s(kp, j), R1[8][0], hv);
         return hv;
     }
     return 0.0;

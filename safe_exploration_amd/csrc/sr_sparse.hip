@@ -13,7 +13,7 @@
 // Order of every sum: chunks in ascending order, inside a chunk the GEMM's k order and the strips of SR_SP_ROWS rows in
 // ascending order -- two fits of the same data with the same chunk are bit-identical.
 #include "sr_handle.h"
-#include "sr_pivot_dev.h"
+#include "sr_kernel_dev.h"
 using namespace srh;
 
 #define SR_SP_ROWS 32            // data rows per workgroup of the panel kernel (one partial sum of b per strip and column)
@@ -40,8 +40,8 @@ __global__ __launch_bounds__(256) void sr_sp_panel_kernel(const double* __restri
     const bool real = j < Np && j >= off;
     double sc[SR_MAX_D], zj[SR_MAX_D];
     if (kp) {
-        const double* sv = kp + (long)d * SR_KP(D) + 3;
-        for (int c = 0; c < D; ++c) { sc[c] = sv[c]; zj[c] = real ? Z[(long)(j - off) * D + c] : 0.0; }
+        const sr_kview k(kp + (long)d * SR_KP(D), D);
+        for (int c = 0; c < D; ++c) { sc[c] = k.sv[c]; zj[c] = real ? Z[(long)(j - off) * D + c] : 0.0; }
     } else {
         for (int c = 0; c < D; ++c) {
             sc[c] = 1.0 / ls[(long)d * D + c];
@@ -61,22 +61,10 @@ __global__ __launch_bounds__(256) void sr_sp_panel_kernel(const double* __restri
     double* Pd = P + (long)d * sP + (long)r0 * Np + j;
     double acc = 0.0;
     if (kp) {
-        const double* kd = kp + (long)d * SR_KP(D);
-        const int kind = (int)kd[0];
-        const double var = kd[1], c0 = kd[2];
-        const double *av = kd + 3 + D, *bv = kd + 3 + 2 * D;
+        const sr_kview k(kp + (long)d * SR_KP(D), D, sc);    // (s[D]: the thread's copy)
         for (int u = 0; u < SR_SP_ROWS; ++u) {
             double v = 0.0;
-            if (real && r0 + u < rows) {
-                double r2 = 0.0, la = 0.0, lb = 0.0;
-                for (int c = 0; c < D; ++c) {
-                    const double t = (xs[u][c] - zj[c]) * sc[c];
-                    r2 = fma(t, t, r2);
-                    la = fma(av[c] * xs[u][c], zj[c], la);
-                    lb = fma(bv[c] * xs[u][c], zj[c], lb);
-                }
-                v = (c0 + la) * var * sr_kappa(kind, r2) + lb;
-            }
+            if (real && r0 + u < rows) v = sr_kpair(k, D, xs[u], zj);
             Pd[(long)u * Np] = v;
             acc = fma(v, ys[u], acc);
         }

@@ -5,11 +5,12 @@
 //
 //   nll   = 1/2 y^T alpha + 1/2 log det K_y + N/2 log 2 pi
 //   d nll / d theta = 1/2 sum_ij M_ij dK_ij/d theta ,   M = K_y^-1 - alpha alpha^T
-// with the general kernel family of sr_common.h, k = (c0 + sum a x y) v kappa(r) + sum b x y:
-//   dk/dv = c kappa,  dk/dc0 = v kappa,  dk/ds_j = c v g s_j (x_j - y_j)^2  (g = kappa'(r)/r),
+// with the general kernel family of sr_kernel_dev.h, k = (c0 + sum a x y) v kappa(r) + sum b x y (c = c0 + sum a x y, g as
+// sr_radial gives it):
+//   dk/dv = c kappa,  dk/dc0 = v kappa,  dk/ds_j = c v g s_j (x_j - y_j)^2,
 //   dk/da_j = x_j y_j v kappa,  dk/db_j = x_j y_j,  dK_y/dnoise = I.
 // One thread per (i, j) pair of a 16 x 16 tile, deterministic two-stage reduction.
-#include "sr_common.h"
+#include "sr_kernel_dev.h"
 
 template <int DT>
 __global__ __launch_bounds__(256) void sr_mll_grad_kernel(const double* __restrict__ Kinv, int Np, int N,
@@ -35,24 +36,16 @@ __global__ __launch_bounds__(256) void sr_mll_grad_kernel(const double* __restri
         for (int c = 0; c < DT; ++c) {
             const double x = (c < D) ? Z[(long)i * D + c] : 0.0;
             const double y = (c < D) ? Z[(long)j * D + c] : 0.0;
-            const double s = (c < D) ? kp[3 + c] : 0.0;
-            const double a = (c < D) ? kp[3 + D + c] : 0.0;
+            const double s = (c < D) ? sr_kp_s(kp, c) : 0.0;
+            const double a = (c < D) ? sr_kp_a(kp, D, c) : 0.0;
             const double df = x - y;
             xy[c] = x * y;
             sd2[c] = s * df * df;                      // s_c (x_c - y_c)^2
             r2 = fma(s * sd2[c], 1.0, r2);
             la = fma(a, xy[c], la);
         }
-        double kap, g;
-        if (kind == 0) {
-            kap = exp(-0.5 * r2);
-            g = -kap;
-        } else {
-            const double rr = sqrt(r2);
-            const double e = exp(-2.23606797749978969641 * rr);
-            kap = (1.0 + 2.23606797749978969641 * rr + (5.0 / 3.0) * r2) * e;
-            g = -(5.0 / 3.0) * (1.0 + 2.23606797749978969641 * rr) * e;
-        }
+        double kap, g, h;
+        sr_radial<1>(kind, r2, kap, g, h);
         const double cc = c0 + la;
         acc[0] = m * cc * kap;
         acc[1] = m * var * kap;
