@@ -113,14 +113,8 @@ static int append1_slide(sr_gp* h, const double* Znew, const double* Ynew, hipSt
     }
     const size_t o_ld = 0, o_info = o_ld + (size_t)nld, o_grid = o_info + (size_t)n_out,
                  need = o_grid + (size_t)sr_append1_grid_ws(Np0, n_out);
-    if (h->app_cap < need) {
-        (void)device_sync();
-        dev_free(h->app_ws);
-        h->app_ws = nullptr; h->app_cap = 0;
-        SR_TRY(dev_alloc(&h->app_ws, need));
-        h->app_cap = need;
-    }
-    double* ws = h->app_ws;
+    SR_TRY(h->app_ws.grow(need, wait::device()));
+    double* ws = h->app_ws.get();
     if (!h->appg_cnt) {
         SR_TRY(dev_alloc(&h->appg_cnt, (size_t)SR_APPEND1_MAX_OUT));          // (unsigned counters in a block of doubles)
         SR_HIP(hipMemsetAsync(h->appg_cnt, 0, sizeof(double) * SR_APPEND1_MAX_OUT, s));
@@ -224,14 +218,8 @@ static int append_small(sr_gp* h, const double* Znew, const double* Ynew, int m,
                  o_g = o_y2 + n_out * s_y2, o_sb = o_g + n_out * BB, o_inv = o_sb + n_out * BB,
                  o_ld = o_inv + n_out * BB, o_info = o_ld + (size_t)nld, o_grid = o_info + (size_t)n_out,
                  need = o_grid + (route == 2 ? (size_t)sr_append1_grid_ws(Np0, n_out) : 0);
-    if (h->app_cap < need) {
-        (void)device_sync();
-        dev_free(h->app_ws);
-        h->app_ws = nullptr; h->app_cap = 0;
-        SR_TRY(dev_alloc(&h->app_ws, need));
-        h->app_cap = need;
-    }
-    double* ws = h->app_ws;
+    SR_TRY(h->app_ws.grow(need, wait::device()));
+    double* ws = h->app_ws.get();
     double *U12t = ws + o_u12, *Xt = ws + o_xt, *Y2 = ws + o_y2, *G = ws + o_g, *Sb = ws + o_sb, *invS = ws + o_inv;
     int* info_dev = reinterpret_cast<int*>(ws + o_info);
     double *Z1 = nullptr, *yT1 = nullptr, *alpha1 = nullptr, *Wt1 = nullptr;
@@ -300,12 +288,8 @@ static int append_small(sr_gp* h, const double* Znew, const double* Ynew, int m,
     const long Tp = srt::BN;
     const int nsplit = pick_nsplit(h, Tp);
     SR_A(ensure_ws(h, Tp, nsplit));
-    sr_kstar_args ka;
-    ka.Z = h->Z; ka.alpha = h->alpha; ka.ls = h->ls; ka.sf2 = h->sf2;
-    ka.kp = h->general ? h->kp : nullptr; ka.kxx = h->kxx;
-    ka.xa = Znew; ka.lda = D; ka.na = D; ka.xb = nullptr; ka.ldb = 0; ka.nb = 0;
-    ka.Ks = h->Ks; ka.mu_part = h->mu_part; ka.jac_part = h->jac_part;
-    ka.N = N0; ka.Np = Np0; ka.D = D; ka.n_out = n_out; ka.nsplit = nsplit; ka.T = m; ka.Tp = Tp;
+    sr_kstar_args ka = kstar_ws(h, nsplit, m, Tp);          // (h->N, h->Np are still N0, Np0: the commit is below)
+    ka.xa = Znew; ka.lda = D; ka.na = D;
     SR_A(sr_launch_kstar(ka, s));
     if (!h->small_vp) SR_A(dev_alloc(&h->small_vp, (size_t)sr_var_small_ws(Np0, n_out)));
     SR_A(sr_launch_var_small(h->Wt, h->Ks, h->small_vp, h->var_part, N0, Np0, Tp, n_out, m, s, 0, false));   // (no norms wanted)
@@ -386,23 +370,17 @@ static int append_small(sr_gp* h, const double* Znew, const double* Ynew, int m,
         if (!vec_alt) { dev_free(h->yT_alt); dev_free(h->alpha_alt); }
         h->yT_alt = old_yT; h->alpha_alt = old_alpha; h->vec_alt_np = Np0;
         // keep the previous buffer for the next append (bounded: not for huge factors)
-        if (!reuse_alt) dev_free(h->Wt_alt);
+        if (reuse_alt) h->Wt_alt = nullptr;      // (that buffer holds the model now)
+        drop_wt_alt(h);
         if ((size_t)n_out * NN0 * sizeof(double) <= SR_FACT_PAR_BYTES * 2) { h->Wt_alt = old_wt; h->wt_alt_cap = (size_t)n_out * NN0; h->wt_alt_off = off0; }
-        else { dev_free(old_wt); h->Wt_alt = nullptr; h->wt_alt_cap = 0; h->wt_alt_off = -1; }
+        else dev_free(old_wt);
     } else {
         dev_free(old_wt);
         dev_free(old_yT); dev_free(old_alpha);
         dev_free(h->yT_alt); dev_free(h->alpha_alt); h->yT_alt = h->alpha_alt = nullptr; h->vec_alt_np = 0;
-        dev_free(h->Wt_alt); h->Wt_alt = nullptr; h->wt_alt_cap = 0; h->wt_alt_off = -1;
+        drop_wt_alt(h);
         h->Np = Np1;
-        free_ws(h);
-        dev_free(h->lin_v); dev_free(h->lin_g); dev_free(h->small_vp); dev_free(h->splitk_vt); dev_free(h->splitk_part);
-        h->lin_v = h->lin_g = h->small_vp = h->splitk_vt = h->splitk_part = nullptr;
-        h->splitk_cap = 0;
-        dev_free(h->stream_vp); dev_free(h->stream_tickets);
-        h->stream_vp = nullptr; h->stream_vp_cap = 0; h->stream_tickets = nullptr;
-        dev_free(h->fact_ws); h->fact_ws = nullptr; h->fact_cap = 0;
-        dev_free(h->app_ws); h->app_ws = nullptr; h->app_cap = 0;
+        drop_np_sized(h);
     }
     return SR_OK;
 }
@@ -460,14 +438,8 @@ extern "C" int sr_gp_append(sr_gp_t h, const double* Znew, const double* Ynew, i
                  o_x = o_u12t + PB, o_y2 = o_x + PB, o_g = o_y2 + PB, o_sb = o_g + BB, o_inv = o_sb + BB, o_wdm = o_inv + BB,
                  o_wtr = o_wdm + BB, o_part = o_wtr + NN0, o_info = o_part + (size_t)((Np0 + APP_KS - 1) / APP_KS) * PB,
                  need = o_info + (size_t)n_out;
-    if (h->app_cap < need) {
-        (void)device_sync();
-        dev_free(h->app_ws);
-        h->app_ws = nullptr; h->app_cap = 0;
-        SR_TRY(dev_alloc(&h->app_ws, need));
-        h->app_cap = need;
-    }
-    double* ws = h->app_ws;
+    SR_TRY(h->app_ws.grow(need, wait::device()));
+    double* ws = h->app_ws.get();
     double *Xq = ws + o_xq, *Ks = ws + o_ks, *U12 = ws + o_u12, *U12t = ws + o_u12t, *X = ws + o_x, *Y2 = ws + o_y2,
            *G = ws + o_g, *Sb = ws + o_sb, *invS = ws + o_inv, *wdm = ws + o_wdm, *Wtr = ws + o_wtr, *part = ws + o_part;
     int* info_dev = reinterpret_cast<int*>(ws + o_info);
@@ -507,12 +479,9 @@ extern "C" int sr_gp_append(sr_gp_t h, const double* Znew, const double* Ynew, i
     // mean partial sums (the old model's mean at the new points) feed the alpha update below
     const int nsplit = pick_nsplit(h, SR_NB);
     SR_A(ensure_ws(h, SR_NB, nsplit));
-    sr_kstar_args ka;
-    ka.Z = h->Z; ka.alpha = h->alpha; ka.ls = h->ls; ka.sf2 = h->sf2;
-    ka.kp = h->general ? h->kp : nullptr; ka.kxx = h->kxx;
-    ka.xa = Xq; ka.lda = D; ka.na = D; ka.xb = nullptr; ka.ldb = 0; ka.nb = 0;
-    ka.Ks = Ks; ka.mu_part = h->mu_part; ka.jac_part = h->jac_part;
-    ka.N = N0; ka.Np = Np0; ka.D = D; ka.n_out = n_out; ka.nsplit = nsplit; ka.T = SR_NB; ka.Tp = SR_NB;
+    sr_kstar_args ka = kstar_ws(h, nsplit, SR_NB, SR_NB);   // (h->N, h->Np are still N0, Np0: the commit is below)
+    ka.xa = Xq; ka.lda = D; ka.na = D;
+    ka.Ks = Ks;                                             // K* of the new points in the append's own scratch
     SR_A(sr_launch_kstar(ka, s));
     for (int d = 0; d < n_out; ++d) {
         const double* Wt0 = h->Wt + (size_t)d * NN0;
@@ -560,22 +529,16 @@ extern "C" int sr_gp_append(sr_gp_t h, const double* Znew, const double* Ynew, i
     h->logdet_valid = 0;
     if (Np1 == Np0) {
         // keep the previous buffer for the next append (bounded: not for huge factors)
-        if (!reuse_alt) dev_free(h->Wt_alt);
+        if (reuse_alt) h->Wt_alt = nullptr;      // (that buffer holds the model now)
+        drop_wt_alt(h);
         if ((size_t)n_out * NN0 * sizeof(double) <= SR_FACT_PAR_BYTES * 2) { h->Wt_alt = old_wt; h->wt_alt_cap = (size_t)n_out * NN0; h->wt_alt_off = off0; }
-        else { dev_free(old_wt); h->Wt_alt = nullptr; h->wt_alt_cap = 0; h->wt_alt_off = -1; }
+        else dev_free(old_wt);
     } else {
         // everything sized by Np is dropped and re-created lazily
         dev_free(old_wt);
-        dev_free(h->Wt_alt); h->Wt_alt = nullptr; h->wt_alt_cap = 0; h->wt_alt_off = -1;
+        drop_wt_alt(h);
         h->Np = Np1;
-        free_ws(h);
-        dev_free(h->lin_v); dev_free(h->lin_g); dev_free(h->small_vp); dev_free(h->splitk_vt); dev_free(h->splitk_part);
-        h->lin_v = h->lin_g = h->small_vp = h->splitk_vt = h->splitk_part = nullptr;
-        h->splitk_cap = 0;
-        dev_free(h->stream_vp); dev_free(h->stream_tickets);
-        h->stream_vp = nullptr; h->stream_vp_cap = 0; h->stream_tickets = nullptr;
-        dev_free(h->fact_ws); h->fact_ws = nullptr; h->fact_cap = 0;
-        dev_free(h->app_ws); h->app_ws = nullptr; h->app_cap = 0;
+        drop_np_sized(h);
     }
     return SR_OK;
 }

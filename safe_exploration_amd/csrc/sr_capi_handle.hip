@@ -215,23 +215,42 @@ void srh::free_ws(sr_gp* h) {
     h->ws_Tp = 0; h->ws_part = 0;
 }
 
+// Everything whose size or content depends on the padded size: dropped when a block append crosses a 128-row boundary
+// (h->Np is the new size already) and re-created lazily.
+void srh::drop_np_sized(sr_gp* h) {
+    free_ws(h);
+    h->lin_v.drop(); h->splitk_vt.drop(); h->stream_vp.drop(); h->fact_ws.drop(); h->app_ws.drop();
+    dev_free(h->lin_g); dev_free(h->small_vp); dev_free(h->splitk_part); dev_free(h->stream_tickets);
+    h->lin_g = h->small_vp = h->splitk_part = nullptr; h->stream_tickets = nullptr;
+    // tz_x, tz_jac: sized by the queries of a chunk, checked against their capacity on every use
+    // stream_tab: keyed by Np (stream_tab_key), planned again when the key changes
+    // stream_slots: one fixed size (SR_ST1_SLOTS_MAX) for every model
+    // grad_v, grad_part, hess_part: checked against their capacity on every use
+    // sel_L, sel_ws: sized by the candidate pool, checked against their capacity on every use
+}
+
+// what sr_gp_release_scratch gives back: the big scratch of the update, the appends, the gradient / Hessian passes and the
+// selection, and the spare model buffers of the appends
+static void release_big(sr_gp* h) {
+    h->fact_ws.drop(); h->app_ws.drop();
+    h->grad_v.drop(); h->grad_part.drop(); h->hess_part.drop(); h->sel_L.drop(); h->sel_ws.drop();
+    drop_wt_alt(h);
+    dev_free(h->yT_alt); dev_free(h->alpha_alt); h->yT_alt = h->alpha_alt = nullptr; h->vec_alt_np = 0;
+}
+
 extern "C" int sr_gp_destroy(sr_gp_t h) {
     if (!h) return SR_OK;
     sr_dev_guard guard(h->device);
     server_release(h);
     (void)device_sync();
+    drop_np_sized(h);
+    release_big(h);
+    h->stream_slots.drop(); h->stream_tab.drop(); h->tz_x.drop(); h->tz_jac.drop();
     dev_free(h->Z); dev_free(yT_alloc_of(h)); dev_free(h->ls); dev_free(h->sf2); dev_free(h->noise);
-    dev_free(alpha_alloc_of(h)); dev_free(wt_alloc_of(h)); dev_free(h->kp); dev_free(h->lin_v); dev_free(h->lin_g); dev_free(h->small_vp); dev_free(h->splitk_vt); dev_free(h->splitk_part);
-    dev_free(h->grad_v); dev_free(h->grad_part);
-    dev_free(h->hess_part);
-    dev_free(h->sel_L); dev_free(h->sel_ws);
-    dev_free(h->stream_vp); dev_free(h->stream_tickets); dev_free(h->stream_slots); dev_free(h->stream_tab);
-    dev_free(h->Tz); dev_free(h->tz_x); dev_free(h->tz_jac);
+    dev_free(alpha_alloc_of(h)); dev_free(wt_alloc_of(h)); dev_free(h->kp); dev_free(h->Tz);
     dev_free(h->chain_xch); dev_free(h->chain_tickets); dev_free(h->chain_done); dev_free(h->call_ticket);
     if (h->chain_status_host) (void)hipHostFree(h->chain_status_host);
-    dev_free(h->yT_alt); dev_free(h->alpha_alt);
-    free_ws(h);
-    dev_free(h->fact_ws); dev_free(h->app_ws); dev_free(h->appg_cnt); dev_free(h->Wt_alt); dev_free(h->fact_flags); dev_free(h->flow_flags); if (h->flow_segs) (void)hipFree(h->flow_segs);
+    dev_free(h->appg_cnt); dev_free(h->fact_flags); dev_free(h->flow_flags); if (h->flow_segs) (void)hipFree(h->flow_segs);
     if (h->app_pin) (void)hipHostFree(h->app_pin);
     for (hipEvent_t e : {h->fact_join, h->ev_panel[0], h->ev_panel[1], h->ev_bulk[0], h->ev_bulk[1], h->ev_inv[0], h->ev_inv[1]})
         if (e) (void)hipEventDestroy(e);
@@ -486,15 +505,7 @@ extern "C" int sr_gp_release_scratch(sr_gp_t h) {
     SR_CHECK(h != nullptr, SR_EINVAL, "sr_gp_release_scratch: NULL handle");
     SR_DEVICE(h->device);
     SR_HIP(device_sync());
-    dev_free(h->fact_ws); h->fact_ws = nullptr; h->fact_cap = 0;
-    dev_free(h->Wt_alt); h->Wt_alt = nullptr; h->wt_alt_cap = 0; h->wt_alt_off = -1;
-    dev_free(h->app_ws); h->app_ws = nullptr; h->app_cap = 0;
-    dev_free(h->grad_v); h->grad_v = nullptr; h->grad_v_cap = 0;
-    dev_free(h->grad_part); h->grad_part = nullptr; h->grad_part_cap = 0;
-    dev_free(h->hess_part); h->hess_part = nullptr; h->hess_part_cap = 0;
-    dev_free(h->sel_L); h->sel_L = nullptr; h->sel_L_cap = 0;
-    dev_free(h->sel_ws); h->sel_ws = nullptr; h->sel_ws_cap = 0;
-    dev_free(h->yT_alt); dev_free(h->alpha_alt); h->yT_alt = h->alpha_alt = nullptr; h->vec_alt_np = 0;
+    release_big(h);
     // the caller wants the memory back: what these releases left in the block cache goes to the driver too
     return sr_release_cached_memory();
 }

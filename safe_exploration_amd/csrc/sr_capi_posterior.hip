@@ -71,14 +71,7 @@ int srh::prepare_ws(sr_gp* h, long Tc) {
 // once, reduction and final stage hang behind tickets.  ARD-RBF with D <= 5 and <= 4 columns: ONE launch (the
 // workgroups evaluate their chunk of the columns themselves); otherwise the column pass (K1 / sr_lin_columns) first.
 static int stream_buffers(sr_gp* h, int ncols, hipStream_t s) {
-    const long need = sr_stream_vp_doubles(h->Np, h->n_out, sr_stream_width(ncols));
-    if (need > h->stream_vp_cap) {
-        (void)hipStreamSynchronize(s);
-        dev_free(h->stream_vp);
-        h->stream_vp = nullptr; h->stream_vp_cap = 0;
-        SR_TRY(dev_alloc(&h->stream_vp, (size_t)need));
-        h->stream_vp_cap = need;
-    }
+    SR_TRY(h->stream_vp.grow((size_t)sr_stream_vp_doubles(h->Np, h->n_out, sr_stream_width(ncols)), wait::stream(s)));
     if (!h->stream_tickets) {
         const int n = sr_stream_tickets(h->Np, h->n_out);
         SR_TRY(dev_alloc(&h->stream_tickets, (size_t)n));
@@ -103,24 +96,18 @@ static int stream_items(sr_gp* h, sr_stream_args& a, int ncols, int width_min, b
         int n = 0, nwg = 0;
         const int kr = sr_stream_items(h->Np, h->n_out, nc, h->ncu, can_fuse, tab, &n, &nwg);
         if (kr > 0) {
-            if ((long)tab.size() > h->stream_tab_cap) {
-                (void)hipStreamSynchronize(s);
-                dev_free(h->stream_tab);
-                h->stream_tab = nullptr; h->stream_tab_cap = 0;
-                SR_TRY(dev_alloc(&h->stream_tab, tab.size()));
-                h->stream_tab_cap = (long)tab.size();
-            }
+            SR_TRY(h->stream_tab.grow(tab.size(), wait::stream(s)));
             SR_HIP(hipStreamSynchronize(s));                      // (a launch that still reads the old table)
-            SR_HIP(hipMemcpy(h->stream_tab, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice));
+            SR_HIP(hipMemcpy(h->stream_tab.get(), tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice));
         }
         h->stream_tab_key = key; h->stream_tab_kr = kr; h->stream_tab_n = n; h->stream_tab_nwg = nwg;
     }
-    a.item_tab = h->stream_tab; a.kr = h->stream_tab_kr; a.nitems = h->stream_tab_n; a.nwg = h->stream_tab_nwg;
+    a.item_tab = h->stream_tab.get(); a.kr = h->stream_tab_kr; a.nitems = h->stream_tab_n; a.nwg = h->stream_tab_nwg;
     return SR_OK;
 }
 
 static void stream_common(const sr_gp* h, sr_stream_args& a, int ncols, long Tp) {
-    a.Wt = h->Wt; a.Ks = h->Ks; a.Vp = h->stream_vp; a.part = h->var_part; a.tickets = h->stream_tickets;
+    a.Wt = h->Wt; a.Ks = h->Ks; a.Vp = h->stream_vp.get(); a.part = h->var_part; a.tickets = h->stream_tickets;
     a.N = h->N; a.Np = h->Np; a.D = h->D; a.n_out = h->n_out; a.k_lo = h->Np - h->N; a.ncols = ncols; a.ncols_pad = ncols;
     a.Tp = Tp;
     a.Z = h->Z; a.alpha = h->alpha; a.ls = h->ls; a.sf2 = h->sf2;
@@ -151,12 +138,8 @@ static int stream_predict(sr_gp* h, long Tc, const double* xa, long lda, int na,
     SR_TRY(ensure_ws(h, Tp, std::max(nsplit, 2 * ncb)));
     SR_TRY(stream_buffers(h, mfma_small ? 16 : (int)Tc, s));
     if (!fused) {
-        sr_kstar_args ka;
-        ka.Z = h->Z; ka.alpha = h->alpha; ka.ls = h->ls; ka.sf2 = h->sf2;
-        ka.kp = h->general ? h->kp : nullptr; ka.kxx = h->kxx;
+        sr_kstar_args ka = kstar_ws(h, nsplit, Tc, Tp);
         ka.xa = xa; ka.lda = lda; ka.na = na; ka.xb = xb; ka.ldb = ldb; ka.nb = nb;
-        ka.Ks = h->Ks; ka.mu_part = h->mu_part; ka.jac_part = h->jac_part;
-        ka.N = h->N; ka.Np = h->Np; ka.D = h->D; ka.n_out = h->n_out; ka.nsplit = nsplit; ka.T = Tc; ka.Tp = Tp;
         sr_prof_scope ps(&h->prof, SR_K_KSTAR, s);
         SR_TRY(sr_launch_kstar(ka, s));
     }
@@ -164,26 +147,21 @@ static int stream_predict(sr_gp* h, long Tc, const double* xa, long lda, int na,
     stream_common(h, a, (int)Tc, Tp);
     a.mode = 0; a.dot0 = 0; a.width_min = mfma_small ? 16 : 0;
     a.xa = xa; a.lda = lda; a.na = na; a.xb = xb; a.ldb = ldb;
-    a.fa.mu_part = h->mu_part; a.fa.jac_part = h->jac_part; a.fa.var_part = h->var_part; a.fa.sf2 = h->sf2;
-    a.fa.ls = h->ls; a.fa.kxx = h->general ? h->kxx : nullptr; a.fa.mu = mu; a.fa.var = var; a.fa.jac = jac;
-    a.fa.n_out = h->n_out; a.fa.D = h->D; a.fa.nsplit = nsplit; a.fa.nrb = ncb; a.fa.T = Tc; a.fa.Tp = Tp;
+    a.fa = final_args(h, nsplit, ncb, Tc, Tp, h->var_part, mu, var, jac);
     // ONE query evaluated in the kernel: the polling finaliser and its self-validating slots (sr_stream1_kernel) where they
     // fit its LDS; their pattern is "empty" from the allocation on, the finaliser leaves it behind again
     static const bool st1_poll = sr_lab_env("SR_ST1_POLL", 1) != 0;           // (lab build: A/B against the two ticket levels)
     const long nslot = sr_st1_slots(ncb, h->n_out, h->D);
     if (fused && Tc == 1 && !fused_mfma && nslot <= SR_ST1_SLOTS_MAX && 2 * ncb <= 64 && st1_poll) {
-        if (h->stream_slots_cap < nslot) {
-            (void)hipStreamSynchronize(s);
-            dev_free(h->stream_slots);
-            h->stream_slots = nullptr; h->stream_slots_cap = 0;
-            SR_TRY(dev_alloc(&h->stream_slots, (size_t)SR_ST1_SLOTS_MAX));
-            h->stream_slots_cap = SR_ST1_SLOTS_MAX;
+        bool grew = false;
+        SR_TRY(h->stream_slots.grow((size_t)SR_ST1_SLOTS_MAX, wait::stream(s), &grew));      // (one size for every model)
+        if (grew) {
             double empty;
             const unsigned long long bits = SR_ST1_EMPTY;
             memcpy(&empty, &bits, sizeof(double));
-            SR_TRY(sr_launch_fill(h->stream_slots, (size_t)SR_ST1_SLOTS_MAX, empty, s));
+            SR_TRY(sr_launch_fill(h->stream_slots.get(), (size_t)SR_ST1_SLOTS_MAX, empty, s));
         }
-        a.slots = h->stream_slots;
+        a.slots = h->stream_slots.get();
     }
     SR_TRY(stream_items(h, a, (int)Tc, a.width_min, fused, s));
     h->last_streamed = 0;
@@ -200,27 +178,20 @@ static int stream_linearize(sr_gp* h, const double* x, double* mu, double* var, 
     SR_TRY(stream_buffers(h, ncols, s));
     const int nblk256 = (h->Np + 255) / 256;
     const size_t need = (size_t)h->n_out * std::max(nblk256, 2 * ncb) * sr_lin_nacc(h->D);
-    if (!h->lin_v || h->lin_cap < need) {
-        (void)hipStreamSynchronize(s);
-        dev_free(h->lin_v);
-        h->lin_v = nullptr; h->lin_cap = 0;
-        SR_TRY(dev_alloc(&h->lin_v, std::max(need, (size_t)h->n_out * h->Np)));
-        h->lin_cap = std::max(need, (size_t)h->n_out * h->Np);
-    }
+    SR_TRY(h->lin_v.grow(std::max(need, (size_t)h->n_out * h->Np), wait::stream(s)));      // (sr_gp_linearize's v fits too)
     sr_lin_args la;
-    la.Z = h->Z; la.alpha = h->alpha; la.ls = h->ls; la.sf2 = h->sf2; la.Ks = h->Ks; la.g = nullptr;
+    model_args(la, h);
+    la.Ks = h->Ks; la.g = nullptr;
     la.x = x; la.xb = nullptr; la.na = h->D;
-    la.kp = h->general ? h->kp : nullptr;
-    la.jac_var = jac_var; la.hess_mu = hess_mu;
-    la.N = h->N; la.Np = h->Np; la.D = h->D; la.n_out = h->n_out; la.Tp = Tp;
+    la.jac_var = jac_var; la.hess_mu = hess_mu; la.Tp = Tp;
     if (!fused) {
         sr_prof_scope ps(&h->prof, SR_K_KSTAR, s);
-        SR_TRY(sr_launch_lin_columns(la, sr_stream_width(ncols), h->Ks, h->lin_v, s));
+        SR_TRY(sr_launch_lin_columns(la, sr_stream_width(ncols), h->Ks, h->lin_v.get(), s));
     }
     sr_stream_args a{};
     stream_common(h, a, ncols, Tp);
     a.mode = 1; a.dot0 = 1;
-    a.la = la; a.lin_part = h->lin_v; a.lin_part_w = h->lin_v;
+    a.la = la; a.lin_part = h->lin_v.get(); a.lin_part_w = h->lin_v.get();
     a.nblk = fused ? 2 * ncb : nblk256;
     a.lin_dt = h->D <= 3 ? 3 : (h->D <= 5 ? 5 : (h->D <= 8 ? 8 : 12));
     a.lmu = mu; a.lvar = var; a.ljac_mu = jac_mu;
@@ -252,11 +223,8 @@ int srh::gp_pass(sr_gp* h, long Tc, const double* xa, long lda, int na, const do
     const bool one_streamed = h->Np == SR_ONE_STREAMED_NP && Tc == 1 && !h->general && h->D <= SR_STREAM_FUSED_MAX_D;
     if (h->small_path == 1 && !h->force_stream && !one_streamed && sr_gp_small_wanted(h->Np, Tc, h->D, h->general != 0)) {
         // small model, few queries: one launch, no workspace (sr_small.hip)
-        sr_kstar_args ka{};
-        ka.Z = h->Z; ka.alpha = h->alpha; ka.ls = h->ls; ka.sf2 = h->sf2;
-        ka.kp = h->general ? h->kp : nullptr;
+        sr_kstar_args ka = kstar_model(h);
         ka.xa = xa; ka.lda = lda; ka.na = na; ka.xb = xb; ka.ldb = ldb; ka.nb = nb;
-        ka.N = h->N; ka.Np = h->Np; ka.D = h->D; ka.n_out = h->n_out; ka.nsplit = 1;
         ka.T = Tc; ka.Tp = Tc;
         h->last_streamed = 0;
         sr_prof_scope ps(&h->prof, SR_K_SMALL, s);
@@ -268,13 +236,8 @@ int srh::gp_pass(sr_gp* h, long Tc, const double* xa, long lda, int na, const do
     const long Tp = round_up(Tc, srt::BN);
     const int nsplit = pick_nsplit(h, Tp);
     SR_TRY(ensure_ws(h, Tp, nsplit));
-    sr_kstar_args ka;
-    ka.Z = h->Z; ka.alpha = h->alpha; ka.ls = h->ls; ka.sf2 = h->sf2;
-    ka.kp = h->general ? h->kp : nullptr; ka.kxx = h->kxx;
+    sr_kstar_args ka = kstar_ws(h, nsplit, Tc, Tp);
     ka.xa = xa; ka.lda = lda; ka.na = na; ka.xb = xb; ka.ldb = ldb; ka.nb = nb;
-    ka.Ks = h->Ks; ka.mu_part = h->mu_part; ka.jac_part = h->jac_part;
-    ka.N = h->N; ka.Np = h->Np; ka.D = h->D; ka.n_out = h->n_out; ka.nsplit = nsplit;
-    ka.T = Tc; ka.Tp = Tp;
     const bool small_var = h->small_path && ((Tc <= SR_SMALL_T && (h->Np > SR_STREAM_MIN_NP || h->force_stream)) ||
                                              (h->small_path == 1 && h->Np > SR_STREAM_MIN_NP &&
                                               Tc <= (long)SR_SMALL_T * sr_var_small_groups_max(h->Np, h->n_out)));
@@ -298,20 +261,13 @@ int srh::gp_pass(sr_gp* h, long Tc, const double* xa, long lda, int na, const do
         nrb = (h->Np + 255) / 256;
     } else if (h->small_path && sr_var_splitk_wanted(h->Np, Tp, h->n_out)) {
         // few query tiles: equal shares of the k-blocks of all tiles, the segments of a tile added by a second launch
-        const long need = sr_var_bal_ws(h->Np, Tp, h->n_out);
-        if (need > h->splitk_cap) {
-            (void)hipStreamSynchronize(s);
-            dev_free(h->splitk_vt);
-            h->splitk_vt = nullptr; h->splitk_cap = 0;
-            SR_TRY(dev_alloc(&h->splitk_vt, (size_t)need));
-            h->splitk_cap = need;
-        }
+        SR_TRY(h->splitk_vt.grow((size_t)sr_var_bal_ws(h->Np, Tp, h->n_out), wait::stream(s)));
         if (!h->splitk_part) SR_TRY(dev_alloc(&h->splitk_part, (size_t)4 * 1024 * srt::BN));
         var_part = h->splitk_part;
         nrb = 4 * (h->Np / SR_NB);
         sr_prof_scope ps(&h->prof, SR_K_VAR, s);
         SR_TRY(tile_route_alignment(h));
-        SR_TRY(sr_launch_var_bal(h->Wt, h->Ks, h->splitk_vt, h->splitk_part, h->N, h->Np, Tp, h->n_out, s));
+        SR_TRY(sr_launch_var_bal(h->Wt, h->Ks, h->splitk_vt.get(), h->splitk_part, h->N, h->Np, Tp, h->n_out, s));
     } else if (h->small_path && sr_var64_wanted(h->Np, Tp, h->n_out)) {
         // small model, few tiles: 64 x 64 workgroup tiles shorten the critical path of the tiny grid
         if (!h->splitk_part) SR_TRY(dev_alloc(&h->splitk_part, (size_t)4 * 1024 * srt::BN));
@@ -325,10 +281,7 @@ int srh::gp_pass(sr_gp* h, long Tc, const double* xa, long lda, int na, const do
         SR_TRY(tile_route_alignment(h));
         SR_TRY(sr_launch_var(h->Wt, h->Ks, h->var_part, h->N, h->Np, Tp, h->n_out, h->var_group, h->var_variant, s));
     }
-    sr_final_args fa;
-    fa.mu_part = h->mu_part; fa.jac_part = h->jac_part; fa.var_part = var_part; fa.sf2 = h->sf2;
-    fa.ls = h->ls; fa.kxx = h->general ? h->kxx : nullptr; fa.mu = mu; fa.var = var; fa.jac = jac;
-    fa.n_out = h->n_out; fa.D = h->D; fa.nsplit = nsplit; fa.nrb = nrb; fa.T = Tc; fa.Tp = Tp;
+    const sr_final_args fa = final_args(h, nsplit, nrb, Tc, Tp, var_part, mu, var, jac);
     {
         sr_prof_scope ps(&h->prof, SR_K_FINAL, s);
         SR_TRY(sr_launch_finalize(fa, s));
@@ -362,17 +315,14 @@ extern "C" int sr_gp_linearize(sr_gp_t h, const double* x, double* mu, double* v
     SR_DEVICE(h->device);
     if (h->small_path == 1 && sr_gp_small_lin_wanted(h->Np, h->D, h->general != 0)) {
         // small model: everything in one launch (sr_small.hip, LIN mode; the general family in its own kernel)
-        sr_kstar_args ka{};
-        ka.Z = h->Z; ka.alpha = h->alpha; ka.ls = h->ls; ka.sf2 = h->sf2;
-        ka.kp = h->general ? h->kp : nullptr;
-        ka.xa = x; ka.lda = h->D; ka.na = h->D; ka.xb = nullptr; ka.ldb = 0; ka.nb = 0;
-        ka.N = h->N; ka.Np = h->Np; ka.D = h->D; ka.n_out = h->n_out; ka.nsplit = 1; ka.T = 1; ka.Tp = 1;
+        sr_kstar_args ka = kstar_model(h);
+        ka.xa = x; ka.lda = h->D; ka.na = h->D; ka.T = 1; ka.Tp = 1;
         sr_prof_scope ps(&h->prof, SR_K_SMALL, s);
         return sr_launch_gp_small_lin(ka, h->Wt, mu, var, jac_mu, jac_var, hess_mu, s);
     }
     if (h->small_path != 0)
         return stream_linearize(h, x, mu, var, jac_mu, jac_var, hess_mu, s);
-    if (!h->lin_v) { SR_TRY(dev_alloc(&h->lin_v, (size_t)h->n_out * h->Np)); h->lin_cap = (size_t)h->n_out * h->Np; }
+    SR_TRY(h->lin_v.grow((size_t)h->n_out * h->Np, wait::none()));       // (never smaller than this: nothing to replace)
     if (!h->lin_g) SR_TRY(dev_alloc(&h->lin_g, (size_t)h->n_out * h->Np));
     h->force_stream = 1;
     const int rc_pass = gp_pass(h, 1, x, h->D, h->D, nullptr, 0, 0, mu, var, jac_mu, s);   // leaves K*(:,0) in the workspace
@@ -380,20 +330,19 @@ extern "C" int sr_gp_linearize(sr_gp_t h, const double* x, double* mu, double* v
     SR_TRY(rc_pass);
     const long Tp = srt::BN;
     if (h->last_streamed)    // v = U^-T k* is what the streaming variance pass just accumulated
-        SR_TRY(sr_launch_var_small_gather(h->small_vp, h->lin_v, h->Np, h->n_out, 0, 1, s));
+        SR_TRY(sr_launch_var_small_gather(h->small_vp, h->lin_v.get(), h->Np, h->n_out, 0, 1, s));
     for (int d = 0; d < h->n_out; ++d) {
         const double* Wt = h->Wt + (size_t)d * h->Np * h->Np;
         const double* ks = h->Ks + (size_t)d * h->Np * Tp;
         if (!h->last_streamed)
-            SR_TRY(sr_launch_trmv_t(Wt, h->Np, ks, Tp, h->lin_v + (size_t)d * h->Np, h->Np, s));  // v = U^-T k*
-        SR_TRY(sr_launch_trmv(Wt, h->Np, h->lin_v + (size_t)d * h->Np, h->lin_g + (size_t)d * h->Np,
+            SR_TRY(sr_launch_trmv_t(Wt, h->Np, ks, Tp, h->lin_v.get() + (size_t)d * h->Np, h->Np, s));  // v = U^-T k*
+        SR_TRY(sr_launch_trmv(Wt, h->Np, h->lin_v.get() + (size_t)d * h->Np, h->lin_g + (size_t)d * h->Np,
                               h->Np, 0, s));                                                       // g = U^-1 v
     }
     sr_lin_args la;
-    la.Z = h->Z; la.alpha = h->alpha; la.ls = h->ls; la.sf2 = h->sf2; la.Ks = h->Ks; la.g = h->lin_g; la.x = x;
-    la.kp = h->general ? h->kp : nullptr;
-    la.jac_var = jac_var; la.hess_mu = hess_mu;
-    la.N = h->N; la.Np = h->Np; la.D = h->D; la.n_out = h->n_out; la.Tp = Tp;
+    model_args(la, h);
+    la.Ks = h->Ks; la.g = h->lin_g; la.x = x;
+    la.jac_var = jac_var; la.hess_mu = hess_mu; la.Tp = Tp;
     return sr_launch_linearize(la, s);
 }
 
@@ -446,15 +395,10 @@ extern "C" int sr_gp_set_input_transform(sr_gp_t h, const double* Tz, int n_x_in
 }
 
 static int ensure_tz(sr_gp* h, long Tc, int n_s, int n_u) {
-    if (h->n_xin == 0 || Tc <= h->tz_cap) return SR_OK;
-    (void)device_sync();
-    dev_free(h->tz_x); dev_free(h->tz_jac);
-    h->tz_x = h->tz_jac = nullptr; h->tz_cap = 0;
-    SR_TRY(dev_alloc(&h->tz_x, (size_t)Tc * SR_MAX_D));
+    if (h->n_xin == 0) return SR_OK;
     // (sized for any later transform of this handle: a smaller n_x_in means a larger n_u = D - n_x_in)
-    SR_TRY(dev_alloc(&h->tz_jac, (size_t)Tc * SR_MAX_NS * (SR_MAX_NS + SR_MAX_D)));
-    h->tz_cap = Tc;
-    return SR_OK;
+    SR_TRY(h->tz_x.grow((size_t)Tc * SR_MAX_D, wait::device()));
+    return h->tz_jac.grow((size_t)Tc * SR_MAX_NS * (SR_MAX_NS + SR_MAX_D), wait::device());
 }
 
 // GP posterior at the (possibly transformed) states p [ldp] and controls k_ff [ldkff]: mu, var into the given buffers,
@@ -467,13 +411,13 @@ int srh::gp_pass_states(sr_gp* h, long Tc, const double* p, long ldp, int n_s, c
     }
     SR_TRY(ensure_tz(h, Tc, n_s, n_u));
     hipLaunchKernelGGL(sr_tz_apply_kernel, dim3((unsigned)((Tc * h->n_xin + 255) / 256)), dim3(256), 0, s, p, ldp, h->Tz,
-                       h->tz_x, Tc, n_s, h->n_xin);
+                       h->tz_x.get(), Tc, n_s, h->n_xin);
     SR_HIP(hipGetLastError());
-    SR_TRY(gp_pass(h, Tc, h->tz_x, h->n_xin, h->n_xin, kff, ldkff, n_u, mu, var, h->jac, s));
+    SR_TRY(gp_pass(h, Tc, h->tz_x.get(), h->n_xin, h->n_xin, kff, ldkff, n_u, mu, var, h->jac, s));
     hipLaunchKernelGGL(sr_tz_jac_kernel, dim3((unsigned)((Tc * h->n_out * (n_s + n_u) + 255) / 256)), dim3(256), 0, s,
-                       h->jac, h->Tz, h->tz_jac, Tc, h->n_out, n_s, h->n_xin, n_u);
+                       h->jac, h->Tz, h->tz_jac.get(), Tc, h->n_out, n_s, h->n_xin, n_u);
     SR_HIP(hipGetLastError());
-    *jac_out = h->tz_jac;
+    *jac_out = h->tz_jac.get();
     return SR_OK;
 }
 
@@ -640,11 +584,8 @@ extern "C" int sr_gp_call1(sr_gp_t h, const double* x_host, int second_order, do
         return SR_EUNSUPPORTED;
     }
     const int n = h->n_out, D = h->D;
-    sr_kstar_args ka{};
-    ka.Z = h->Z; ka.alpha = h->alpha; ka.ls = h->ls; ka.sf2 = h->sf2;
-    ka.kp = h->general ? h->kp : nullptr;
-    ka.xa = nullptr; ka.lda = D; ka.na = D; ka.xb = nullptr; ka.ldb = 0; ka.nb = 0;
-    ka.N = h->N; ka.Np = h->Np; ka.D = D; ka.n_out = n; ka.nsplit = 1; ka.T = 1; ka.Tp = 1;
+    sr_kstar_args ka = kstar_model(h);
+    ka.lda = D; ka.na = D; ka.T = 1; ka.Tp = 1;
     ka.xv_on = 1;
     for (int j = 0; j < D; ++j) ka.xv[j] = x_host[j];
     ka.done_ticket = h->call_ticket; ka.host_flag = flag; ka.host_seq = seq;

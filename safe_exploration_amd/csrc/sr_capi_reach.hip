@@ -196,8 +196,8 @@ static int try_chain(sr_gp* h, long T, int H, int mode, const double* p0, const 
             const long Tc = std::min((long)gmax * SR_SMALL_T, T - t0);
             const int groups = (int)((Tc + SR_SMALL_T - 1) / SR_SMALL_T);
             sr_chain_args ca{};
-            ca.k.Z = h->Z; ca.k.alpha = h->alpha; ca.k.ls = h->ls; ca.k.sf2 = h->sf2;
-            ca.k.N = h->N; ca.k.Np = h->Np; ca.k.D = h->D; ca.k.n_out = h->n_out; ca.k.na = n_s; ca.k.nb = n_u;
+            model_args(ca.k, h);
+            ca.k.na = n_s; ca.k.nb = n_u;
             ca.Wt = h->Wt; ca.T = Tc; ca.H = H; ca.mode = mode;
             ca.p0 = p0 + t0 * n_s; ca.q0 = q0 ? q0 + t0 * nss : nullptr; ca.k_fb0 = k_fb0 ? k_fb0 + t0 * nus : nullptr;
             ca.k_ff = k_ff + t0 * H * n_u; ca.k_fb = k_fb ? k_fb + t0 * (H - 1) * nus : nullptr;

@@ -68,11 +68,8 @@ int server_launch(sr_gp* h, unsigned long long first_seq) {
     for (int d = 0; d < slots_of(h); ++d) sv.reply[SR_SERVER_ALIVE + d] = 1ull;
     ++sv.epoch;
     mb_set_epoch(sv, sv.epoch);
-    sr_kstar_args ka{};
-    ka.Z = h->Z; ka.alpha = h->alpha; ka.ls = h->ls; ka.sf2 = h->sf2;
-    ka.kp = h->general ? h->kp : nullptr;
-    ka.xa = nullptr; ka.lda = h->D; ka.na = h->D; ka.xb = nullptr; ka.ldb = 0; ka.nb = 0;
-    ka.N = h->N; ka.Np = h->Np; ka.D = h->D; ka.n_out = h->n_out; ka.nsplit = 1; ka.T = 1; ka.Tp = 1;
+    sr_kstar_args ka = kstar_model(h);
+    ka.lda = h->D; ka.na = h->D; ka.T = 1; ka.Tp = 1;
     sr_server_args sa{};
     sa.mb = sv.mb_dev; sa.out = sv.out_dev; sa.reply = sv.reply_dev;
     sa.first_seq = first_seq; sa.idle_ticks = sv.idle_ticks; sa.epoch = sv.epoch;

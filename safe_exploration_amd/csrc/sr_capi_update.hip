@@ -340,14 +340,8 @@ static int factorize_impl(sr_gp* h, void* stream, int* info, const sr_fact_src* 
         sr_set_error("%s:%d %s -> %s", __FILE__, __LINE__, #call, hipGetErrorString(e_)); cleanup(); return SR_EHIP; } } while (0)
     double* ws;
     if (keep) {
-        if (h->fact_cap < per * n_par) {
-            (void)device_sync();
-            dev_free(h->fact_ws);
-            h->fact_ws = nullptr; h->fact_cap = 0;
-            SR_F(dev_alloc(&h->fact_ws, per * n_par));
-            h->fact_cap = per * n_par;
-        }
-        ws = h->fact_ws;
+        SR_F(h->fact_ws.grow(per * n_par, wait::device()));
+        ws = h->fact_ws.get();
     } else {
         SR_F(dev_alloc(&scratch, per));
         ws = scratch;

@@ -33,6 +33,59 @@ struct sr_server {
     std::mutex mu;                           // one caller at a time: a call, and a quiesce from another thread's entry point
 };
 
+struct sr_gp;
+namespace srh {
+
+// device memory through the block cache (sr_capi_handle.hip)
+int dev_alloc_bytes(void** p, size_t bytes);
+template <typename T>
+static inline int dev_alloc(T** p, size_t count) { return dev_alloc_bytes((void**)p, count * sizeof(T)); }
+void dev_free(void* p);
+int dev_zero(void* p, size_t bytes);
+
+// resident server (sr_capi_server.hip): off the device before the model is written / before a device-wide wait
+int server_quiesce(sr_gp* h);
+void servers_quiesce_device(int device);
+void server_release(sr_gp* h);
+// hipDeviceSynchronize for the library: resident servers of the current device leave first (they would keep the wait
+// until their idle time-out otherwise)
+static inline hipError_t device_sync() {
+    int dev = 0;
+    if (hipGetDevice(&dev) == hipSuccess) servers_quiesce_device(dev);
+    return hipDeviceSynchronize();
+}
+
+// what must have finished before a scratch block that is being replaced goes back to the block cache: nothing (no launch
+// has seen the block), the work of one stream, or the device (device_sync: several streams may still read the block)
+struct wait {
+    enum { NONE, STREAM, DEVICE } what; hipStream_t s;
+    static wait none() { return {NONE, nullptr}; }
+    static wait stream(hipStream_t s) { return {STREAM, s}; }
+    static wait device() { return {DEVICE, nullptr}; }
+};
+
+// grow-only device scratch of the handle: a block and its capacity in elements.  The contents do not survive a growth.
+template <typename T>
+struct scratch {
+    T* p = nullptr; size_t cap = 0;
+    T* get() const { return p; }
+    void drop() { dev_free(p); p = nullptr; cap = 0; }
+    // room for `need` elements; *grew: the block is a new one (its contents are unspecified)
+    int grow(size_t need, wait w, bool* grew = nullptr) {
+        if (grew) *grew = false;
+        if (need <= cap) return SR_OK;
+        if (w.what == wait::STREAM) SR_HIP(hipStreamSynchronize(w.s));
+        if (w.what == wait::DEVICE) SR_HIP(device_sync());
+        drop();
+        SR_TRY(dev_alloc(&p, need));
+        cap = need;
+        if (grew) *grew = true;
+        return SR_OK;
+    }
+};
+
+}  // namespace srh
+
 struct sr_gp {
     int device = 0, N = 0, Np = 0, D = 0, n_out = 0;
     sr_server srv;
@@ -42,7 +95,7 @@ struct sr_gp {
     double* kp = nullptr;     // general kernel family: n_out x SR_KP(D) packed parameters (else NULL)
     // GP input transform of the reachability / moment entry points: x_gp = Tz x (Tz n_xin x n_s), NULL = identity
     double* Tz = nullptr; int n_xin = 0;
-    double *tz_x = nullptr, *tz_jac = nullptr; long tz_cap = 0;   // transformed inputs / chain-ruled Jacobians (per chunk)
+    srh::scratch<double> tz_x, tz_jac;       // transformed inputs / chain-ruled Jacobians (per chunk; both sized by its queries)
     // persistent multi-step kernel (sr_chain.hip K0c): exchange buffer, per group ticket + epoch + done counter (all of
     // the hand-off state lives on the device), switch
     sr_xel* chain_xch = nullptr; unsigned long long* chain_tickets = nullptr;       // the groups' epochs
@@ -55,31 +108,31 @@ struct sr_gp {
     int have_data = 0, factorized = 0;
     int sparse = 0;          // the posterior is that of sr_gp_fit_sparse: Wt Wt^T = K_uu^-1 - Sigma^-1, not K_y^-1
     int import_open = 0;     // between sr_gp_import_begin and sr_gp_import_end
-    // per-chunk workspace (grow-only)
+    // per-chunk workspace (ensure_ws / free_ws: one group, two capacities)
     long chunk = 65536, ws_Tp = 0, ws_part = 0;     // ws_part: capacity of mu_part in units of n_out doubles
     int ws_locked = 0;       // internal buffers (mu / var / jac) are referenced by an entry point: growing now is a bug
     double *Ks = nullptr, *mu_part = nullptr, *jac_part = nullptr, *var_part = nullptr,
            *mu = nullptr, *var = nullptr, *jac = nullptr, *kxx = nullptr;
-    double *lin_v = nullptr, *lin_g = nullptr, *small_vp = nullptr;   // small-batch scratch
-    size_t lin_cap = 0;                                                 // doubles behind lin_v
-    double* stream_vp = nullptr; long stream_vp_cap = 0;   // fused small-batch path: partial sums (grow-only)
+    srh::scratch<double> lin_v;                      // sr_gp_linearize: v = U^-T k* (n_out x Np) / the streamed route's partial sums
+    double *lin_g = nullptr, *small_vp = nullptr;    // g = U^-1 v (n_out x Np); partial sums of the streaming variance pass
+    srh::scratch<double> stream_vp;                  // fused small-batch path: partial sums
     unsigned* stream_tickets = nullptr;
-    int* stream_tab = nullptr; long stream_tab_cap = 0; long stream_tab_key = -1; int stream_tab_kr = 0, stream_tab_n = 0, stream_tab_nwg = 0;   // work items of the run kernel (+ workgroups they are dealt to)
-    double* stream_slots = nullptr; long stream_slots_cap = 0;    // self-validating hand-over slots of the T = 1 kernel's polling finaliser
-    double* splitk_vt = nullptr; long splitk_cap = 0;   // partial products of the balanced few-query-tile route (grow-only)
-    // sr_gp_predict_grad (grow-only): V = U^-T K* of a chunk (n_out x Np x Tp) and the row blocks' partial sums of
-    // d var/dx (n_out x Np/128 x D x Tp); capacities in doubles
-    double* grad_v = nullptr; long grad_v_cap = 0; double* grad_part = nullptr; long grad_part_cap = 0;
-    // sr_gp_linearize_batch (grow-only): the training-row splits' partial sums of the Hessian of the mean
-    // (n_split x n_out x (D (D + 1) / 2 + 1) x Tp); capacity in doubles
-    double* hess_part = nullptr; long hess_part_cap = 0;
-    // sr_gp_select_maxvar (grow-only): the pivoted factor L (n_out x (m - 1) x padded pool) and [var | partial scores |
-    // partial rows | taken marks]; capacities in doubles
-    double* sel_L = nullptr; long sel_L_cap = 0; double* sel_ws = nullptr; long sel_ws_cap = 0;
+    srh::scratch<int> stream_tab; long stream_tab_key = -1; int stream_tab_kr = 0, stream_tab_n = 0, stream_tab_nwg = 0;   // work items of the run kernel (+ workgroups they are dealt to)
+    srh::scratch<double> stream_slots;               // self-validating hand-over slots of the T = 1 kernel's polling finaliser
+    srh::scratch<double> splitk_vt;                  // partial products of the balanced few-query-tile route
+    // sr_gp_predict_grad: V = U^-T K* of a chunk (n_out x Np x Tp) and the row blocks' partial sums of
+    // d var/dx (n_out x Np/128 x D x Tp)
+    srh::scratch<double> grad_v, grad_part;
+    // sr_gp_linearize_batch: the training-row splits' partial sums of the Hessian of the mean
+    // (n_split x n_out x (D (D + 1) / 2 + 1) x Tp)
+    srh::scratch<double> hess_part;
+    // sr_gp_select_maxvar: the pivoted factor L (n_out x (m - 1) x padded pool) and [var | partial scores |
+    // partial rows | taken marks]
+    srh::scratch<double> sel_L, sel_ws;
     // log det(K + noise) per output as of the last <= 16-row append (read back with its status words): the blocking read of
     // sr_gp_logdet costs the exploration loop 30 us per step
     std::vector<double> logdet_host; int logdet_valid = 0;
-    double* splitk_part = nullptr;                      // n_out x 4 nrb x Tp partial norms (<= 4 MB)     // 2 x (n_out x Np) scratch of sr_gp_linearize
+    double* splitk_part = nullptr;                      // n_out x 4 nrb x Tp partial norms (<= 4 MB)
     int var_group = 64;      // query tiles per scheduling group of the variance kernel.  With the diagonal blocks cut short
                              // (variant 2) 64 beats 32: 70.7 against 70.0 TF at C2', fabric-side fetches 61.3 -> 42.9 M KiB per launch
                              // (scripts/pmc_groups.sh); 256 and more lose the sharing of the K* tiles (68.7 TF)
@@ -91,10 +144,10 @@ struct sr_gp {
                              // their structural zeros (default: 74.5 TF)
     // factorisation: the outputs are independent problems -- below SR_FACT_PAR_BYTES of scratch each gets its own
     // HIP stream (the small-grid kernels of a modest model then overlap) and the scratch stays with the handle
-    double* fact_ws = nullptr; size_t fact_cap = 0;      // n_par x (U, W: Np^2 each, v: Np)
+    srh::scratch<double> fact_ws;                        // n_par x (U, W: Np^2 each, v: Np)
     // row append of few points (m <= 16): scratch and a second U^-1 buffer the new factor is assembled into
     // (kept while the padded size does not change: appends then allocate nothing big)
-    double* app_ws = nullptr; size_t app_cap = 0;
+    srh::scratch<double> app_ws;
     unsigned long long* call_flag = nullptr; unsigned long long call_seq = 0;   // set by sr_gp_call1 around a streamed pass
     // In-place one-point appends (sr_capi_append.hip): Wt, alpha and yT may be VIEWS `slide` steps into their allocations
     // (Wt: slide * (Np + 1) doubles, alpha / yT: slide doubles); every entry point that rewrites the model, and every kernel
@@ -174,13 +227,12 @@ static inline void cpu_relax() {
 #endif
 }
 
-// device memory through the block cache (sr_capi_handle.hip)
-int dev_alloc_bytes(void** p, size_t bytes);
-template <typename T>
-static inline int dev_alloc(T** p, size_t count) { return dev_alloc_bytes((void**)p, count * sizeof(T)); }
-void dev_free(void* p);
-int dev_zero(void* p, size_t bytes);
+// the handle's drop lists (sr_capi_handle.hip): the per-chunk workspace; everything whose size or content depends on the
+// padded size (a block append that crosses a 128-row boundary; re-created lazily)
 void free_ws(sr_gp* h);
+void drop_np_sized(sr_gp* h);
+// the spare factor buffer of the appends goes back (Wt_alt is a model buffer, not scratch: it ping-pongs with Wt)
+static inline void drop_wt_alt(sr_gp* h) { dev_free(h->Wt_alt); h->Wt_alt = nullptr; h->wt_alt_cap = 0; h->wt_alt_off = -1; }
 int ensure_wt(sr_gp* h);
 // doubles of the three model buffers with their slack (see sr_gp::slide)
 static inline size_t wt_doubles(int n_out, int Np) { return (size_t)n_out * Np * Np + (size_t)SR_SLIDE_STEPS * (Np + 1); }
@@ -189,18 +241,6 @@ static inline double* wt_alloc_of(const sr_gp* h) { return h->Wt ? h->Wt - (size
 static inline double* alpha_alloc_of(const sr_gp* h) { return h->alpha ? h->alpha - h->slide : nullptr; }
 static inline double* yT_alloc_of(const sr_gp* h) { return h->yT ? h->yT - h->slide : nullptr; }
 int unslide(sr_gp* h);               // back to plain buffers (fresh allocations, two contiguous copies); no-op when slide == 0
-
-// resident server (sr_capi_server.hip): off the device before the model is written / before a device-wide wait
-int server_quiesce(sr_gp* h);
-void servers_quiesce_device(int device);
-void server_release(sr_gp* h);
-// hipDeviceSynchronize for the library: resident servers of the current device leave first (they would keep the wait
-// until their idle time-out otherwise)
-static inline hipError_t device_sync() {
-    int dev = 0;
-    if (hipGetDevice(&dev) == hipSuccess) servers_quiesce_device(dev);
-    return hipDeviceSynchronize();
-}
 
 // The chain of launches of sr_gp_factorize on the caller's matrices (sr_capi_update.hip; the sparse fit, sr_sparse.hip):
 // mat n_out x Np x Np symmetric in the padded layout (identity on the padding; the upper block triangle is read), copied
@@ -225,5 +265,35 @@ int gp_pass(sr_gp* h, long Tc, const double* xa, long lda, int na, const double*
 int tile_route_alignment(sr_gp* h);
 int gp_pass_states(sr_gp* h, long Tc, const double* p, long ldp, int n_s, const double* kff, long ldkff, int n_u,
                    double* mu, double* var, const double** jac_out, hipStream_t s);
+
+// ---- the model as a launch reads it --------------------------------------------------------------------------------
+// the fields every argument struct of the posterior kernels shares (sr_kstar_args, sr_lin_args)
+template <typename A>
+static inline void model_args(A& a, const sr_gp* h) {
+    a.Z = h->Z; a.alpha = h->alpha; a.ls = h->ls; a.sf2 = h->sf2; a.kp = h->general ? h->kp : nullptr;
+    a.N = h->N; a.Np = h->Np; a.D = h->D; a.n_out = h->n_out;
+}
+// one-launch passes (sr_small.hip, the resident server): the model, no workspace; the caller adds its queries
+static inline sr_kstar_args kstar_model(const sr_gp* h) {
+    sr_kstar_args a{};
+    model_args(a, h);
+    a.nsplit = 1;
+    return a;
+}
+// passes through the per-chunk workspace (ensure_ws first)
+static inline sr_kstar_args kstar_ws(const sr_gp* h, int nsplit, long T, long Tp) {
+    sr_kstar_args a = kstar_model(h);
+    a.Ks = h->Ks; a.mu_part = h->mu_part; a.jac_part = h->jac_part; a.kxx = h->kxx;
+    a.nsplit = nsplit; a.T = T; a.Tp = Tp;
+    return a;
+}
+static inline sr_final_args final_args(const sr_gp* h, int nsplit, int nrb, long T, long Tp, const double* var_part,
+                                       double* mu, double* var, double* jac) {
+    sr_final_args a{};
+    a.mu_part = h->mu_part; a.jac_part = h->jac_part; a.var_part = var_part; a.sf2 = h->sf2;
+    a.ls = h->ls; a.kxx = h->general ? h->kxx : nullptr; a.mu = mu; a.var = var; a.jac = jac;
+    a.n_out = h->n_out; a.D = h->D; a.nsplit = nsplit; a.nrb = nrb; a.T = T; a.Tp = Tp;
+    return a;
+}
 
 }  // namespace srh

@@ -247,25 +247,12 @@ static int launch_grad_g(const sr_grad_args& a, bool gen, int n_out, hipStream_t
     return SR_OK;
 }
 
-// grow-only workspace of the gradient route: V (the shape of K*) and the row blocks' partial sums
+// workspace of the gradient route: V (the shape of K*) and the row blocks' partial sums
 static int grad_buffers(sr_gp* h, long Tp, hipStream_t s) {
     const long nv = (long)h->n_out * h->Np * Tp;
     const long np = (long)h->n_out * (h->Np / SR_NB) * h->D * Tp;
-    if (nv > h->grad_v_cap) {
-        (void)hipStreamSynchronize(s);
-        dev_free(h->grad_v);
-        h->grad_v = nullptr; h->grad_v_cap = 0;
-        SR_TRY(dev_alloc(&h->grad_v, (size_t)nv));
-        h->grad_v_cap = nv;
-    }
-    if (np > h->grad_part_cap) {
-        (void)hipStreamSynchronize(s);
-        dev_free(h->grad_part);
-        h->grad_part = nullptr; h->grad_part_cap = 0;
-        SR_TRY(dev_alloc(&h->grad_part, (size_t)np));
-        h->grad_part_cap = np;
-    }
-    return SR_OK;
+    SR_TRY(h->grad_v.grow((size_t)nv, wait::stream(s)));
+    return h->grad_part.grow((size_t)np, wait::stream(s));
 }
 
 // one chunk: K* pass -> V-storing contraction -> G + epilogue -> finalize (mu, var, jac_mu) + jac_var
@@ -275,13 +262,8 @@ static int grad_pass(sr_gp* h, long Tc, const double* Xq, double* mu, double* va
     const int nsplit = pick_nsplit(h, Tp);
     SR_TRY(ensure_ws(h, Tp, nsplit));
     SR_TRY(grad_buffers(h, Tp, s));
-    sr_kstar_args ka;
-    ka.Z = h->Z; ka.alpha = h->alpha; ka.ls = h->ls; ka.sf2 = h->sf2;
-    ka.kp = h->general ? h->kp : nullptr; ka.kxx = h->kxx;
-    ka.xa = Xq; ka.lda = h->D; ka.na = h->D; ka.xb = nullptr; ka.ldb = 0; ka.nb = 0;
-    ka.Ks = h->Ks; ka.mu_part = h->mu_part; ka.jac_part = h->jac_part;
-    ka.N = h->N; ka.Np = h->Np; ka.D = h->D; ka.n_out = h->n_out; ka.nsplit = nsplit;
-    ka.T = Tc; ka.Tp = Tp;
+    sr_kstar_args ka = kstar_ws(h, nsplit, Tc, Tp);
+    ka.xa = Xq; ka.lda = h->D; ka.na = h->D;
     {
         sr_prof_scope ps(&h->prof, SR_K_KSTAR, s);
         SR_TRY(sr_launch_kstar(ka, s));
@@ -296,23 +278,20 @@ static int grad_pass(sr_gp* h, long Tc, const double* Xq, double* mu, double* va
         const int ngrp = (ntq + group - 1) / group;
         const long blocks = (long)h->n_out * ngrp * nrb * group;
         SR_CHECK(blocks < 2147483647L, SR_EINVAL, "predict_grad: grid too large (%ld blocks)", blocks);
-        hipLaunchKernelGGL(sr_var_v_kernel, dim3((unsigned)blocks), dim3(256), 0, s, h->Wt, h->Ks, h->var_part, h->grad_v,
+        hipLaunchKernelGGL(sr_var_v_kernel, dim3((unsigned)blocks), dim3(256), 0, s, h->Wt, h->Ks, h->var_part, h->grad_v.get(),
                            h->Np, Tp, nrb, ntq, group, k_beg);
         SR_HIP(hipGetLastError());
         sr_grad_args ga;
-        ga.Wt = h->Wt; ga.V = h->grad_v; ga.Ks = h->Ks; ga.Z = h->Z; ga.Xq = Xq; ga.kp = h->general ? h->kp : nullptr;
-        ga.gpart = h->grad_part;
+        ga.Wt = h->Wt; ga.V = h->grad_v.get(); ga.Ks = h->Ks; ga.Z = h->Z; ga.Xq = Xq; ga.kp = h->general ? h->kp : nullptr;
+        ga.gpart = h->grad_part.get();
         ga.N = h->N; ga.Np = h->Np; ga.D = h->D; ga.nrb = nrb; ga.ntq = ntq; ga.group = group; ga.T = Tc; ga.Tp = Tp;
         SR_TRY(launch_grad_g(ga, h->general != 0, h->n_out, s));
     }
-    sr_final_args fa;
-    fa.mu_part = h->mu_part; fa.jac_part = h->jac_part; fa.var_part = h->var_part; fa.sf2 = h->sf2;
-    fa.ls = h->ls; fa.kxx = h->general ? h->kxx : nullptr; fa.mu = mu; fa.var = var; fa.jac = jac_mu;
-    fa.n_out = h->n_out; fa.D = h->D; fa.nsplit = nsplit; fa.nrb = nrb; fa.T = Tc; fa.Tp = Tp;
+    const sr_final_args fa = final_args(h, nsplit, nrb, Tc, Tp, h->var_part, mu, var, jac_mu);
     sr_prof_scope ps(&h->prof, SR_K_FINAL, s);
     SR_TRY(sr_launch_finalize(fa, s));
     const long n = Tc * h->n_out;
-    hipLaunchKernelGGL(sr_grad_finish_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, h->grad_part, h->ls,
+    hipLaunchKernelGGL(sr_grad_finish_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, h->grad_part.get(), h->ls,
                        h->general ? h->kp : nullptr, Xq, jac_var, h->n_out, h->D, nrb, Tc, Tp);
     SR_HIP(hipGetLastError());
     return SR_OK;
@@ -489,28 +468,16 @@ __global__ __launch_bounds__(256) void sr_hess_finish_kernel(const double* __res
     hm[c * D + j] = s;
 }
 
-// grow-only workspace of the Hessian pass: the splits' partial sums
-static int hess_buffers(sr_gp* h, long need, hipStream_t s) {
-    if (need > h->hess_part_cap) {
-        (void)hipStreamSynchronize(s);
-        dev_free(h->hess_part);
-        h->hess_part = nullptr; h->hess_part_cap = 0;
-        SR_TRY(dev_alloc(&h->hess_part, (size_t)need));
-        h->hess_part_cap = need;
-    }
-    return SR_OK;
-}
-
 // one chunk after grad_pass: reads the chunk's K* slab (RBF) before the next chunk's K* pass overwrites it
 static int hess_pass(sr_gp* h, long Tc, const double* Xq, double* hess_mu, hipStream_t s) {
     const long Tp = round_up(Tc, srt::BN);              // the K* slab's row stride, as in grad_pass
     const int nsplit = sr_hess_nsplit(h->N, h->n_out, Tp);
     const int nhd = h->D * (h->D + 1) / 2;
     const int nhp = nhd + (h->general ? 0 : 1);
-    SR_TRY(hess_buffers(h, (long)nsplit * h->n_out * nhp * Tp, s));
+    SR_TRY(h->hess_part.grow((size_t)nsplit * h->n_out * nhp * Tp, wait::stream(s)));       // the splits' partial sums
     sr_hess_args a;
     a.Ks = h->Ks; a.Z = h->Z; a.alpha = h->alpha; a.ls = h->ls; a.kp = h->general ? h->kp : nullptr; a.Xq = Xq;
-    a.hpart = h->hess_part;
+    a.hpart = h->hess_part.get();
     a.N = h->N; a.Np = h->Np; a.D = h->D; a.n_out = h->n_out; a.nsplit = nsplit; a.nhp = nhp; a.T = Tc; a.Tp = Tp;
     const dim3 grid((unsigned)((Tp + 255) / 256), h->n_out, nsplit);
 #define SR_HESS_CASE(DT)                                                                                  \
@@ -525,7 +492,7 @@ static int hess_pass(sr_gp* h, long Tc, const double* Xq, double* hess_mu, hipSt
 #undef SR_HESS_CASE
     SR_HIP(hipGetLastError());
     const long n = Tc * h->n_out * nhd;
-    hipLaunchKernelGGL(sr_hess_finish_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, h->hess_part, h->ls,
+    hipLaunchKernelGGL(sr_hess_finish_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, h->hess_part.get(), h->ls,
                        hess_mu, h->general, h->n_out, h->D, nsplit, nhp, Tc, Tp);
     SR_HIP(hipGetLastError());
     return SR_OK;

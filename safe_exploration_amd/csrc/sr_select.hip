@@ -192,18 +192,6 @@ __global__ __launch_bounds__(256) void sr_select_last_kernel(sr_sel_args a, int 
     }
 }
 
-// grow-only workspace: L (n_out x (m - 1) x npad doubles) and [var | partial scores | partial rows | taken]
-static int sel_grow(double** p, long* cap, long need, hipStream_t s) {
-    if (need <= *cap) return SR_OK;
-    SR_HIP(hipStreamSynchronize(s));          // earlier selections on this stream may still read the old block
-    dev_free(*p);
-    *p = nullptr;
-    *cap = 0;
-    SR_TRY(dev_alloc(p, (size_t)need));
-    *cap = need;
-    return SR_OK;
-}
-
 extern "C" int sr_gp_select_maxvar(sr_gp_t h, const double* X, long n, int m, const int* init_idx, int k, int* idx,
                                    double* score, void* stream) {
     SR_CHECK(h != nullptr, SR_EINVAL, "sr_gp_select_maxvar: NULL handle");
@@ -225,16 +213,18 @@ extern "C" int sr_gp_select_maxvar(sr_gp_t h, const double* X, long n, int m, co
     const int npad = (int)round_up(n, SR_SEL_ROWS), nwg = npad / SR_SEL_ROWS;
     const long mcap = std::max(m - 1, 1);
     const long nvar = (long)h->n_out * npad;
-    SR_TRY(sel_grow(&h->sel_L, &h->sel_L_cap, (long)h->n_out * mcap * npad, s));
-    SR_TRY(sel_grow(&h->sel_ws, &h->sel_ws_cap, nvar + 2L * nwg + (2L * nwg + npad + 1) / 2, s));
+    // L (n_out x (m - 1) x npad doubles) and [var | partial scores | partial rows | taken]; earlier selections on this
+    // stream may still read the old blocks
+    SR_TRY(h->sel_L.grow((size_t)h->n_out * mcap * npad, wait::stream(s)));
+    SR_TRY(h->sel_ws.grow((size_t)(nvar + 2L * nwg + (2L * nwg + npad + 1) / 2), wait::stream(s)));
     sr_sel_args a;
     a.X = X; a.n = (int)n; a.npad = npad; a.D = h->D; a.n_out = h->n_out; a.general = h->general;
     a.ls = h->ls; a.sf2 = h->sf2; a.kp = h->general ? h->kp : nullptr; a.noise = h->noise;
     a.seeds = init_idx; a.k = k;
-    a.L = h->sel_L; a.sL = mcap * npad;
-    a.var = h->sel_ws;
-    a.pscore = h->sel_ws + nvar;
-    a.pidx = (int*)(h->sel_ws + nvar + 2L * nwg);
+    a.L = h->sel_L.get(); a.sL = mcap * npad;
+    a.var = h->sel_ws.get();
+    a.pscore = a.var + nvar;
+    a.pidx = (int*)(a.var + nvar + 2L * nwg);
     a.taken = a.pidx + 2L * nwg;
     a.nwg = nwg;
     a.idx = idx; a.score = score;

@@ -1300,6 +1300,112 @@ def test_small_appends_after_refit_and_release():
     np.testing.assert_allclose(gp.predict(x)[1], full.predict(x)[1], rtol=0, atol=1e-9)
 
 
+def _life_cycle_select(gp, pool, m, seeds):
+    """sr_gp_select_maxvar on the model's own handle (it reads kernel and noise, the model stays): picks, scores"""
+    import torch
+    from safe_exploration_amd import _lib
+    from safe_exploration_amd import _buffers as B
+    dev = gp._handle.device
+    tx = torch.from_numpy(np.ascontiguousarray(pool)).to(dev)
+    ts = torch.tensor(seeds, dtype=torch.int32, device=dev)
+    idx = torch.full((m,), -7, dtype=torch.int32, device=dev)
+    sc = torch.full((m,), float("nan"), dtype=torch.float64, device=dev)
+    _lib.check(_lib.lib.sr_gp_select_maxvar(gp._handle.h, B.ptr(tx), pool.shape[0], m, B.ptr(ts), len(seeds), B.ptr(idx),
+                                            B.ptr(sc), B.stream_ptr(dev)))
+    torch.cuda.synchronize(dev)
+    return idx.cpu(), sc.cpu()
+
+
+@pytest.mark.parametrize("kt", ["rbf", "lin_mat52"])
+def test_scratch_life_cycle_leaves_no_trace(kt):
+    """What the handle's scratch buffers went through -- grown from a smaller request, dropped by an append that changes
+    the padded size, handed back by release_scratch -- does not show in any result: two models with the same data
+    (N0 = 600, D = 3, two outputs, + 60 rows in one blocked append: Np 640 -> 768) give the same BITS, one (A) after a
+    history, the other (B) making every call once on fresh buffers.
+
+    A's history: every kind of call at Np = 640 first (the buffers keyed to the old padded size exist when the append
+    drops them), release_scratch between the append and the first posterior call, every call with a smaller batch
+    before the compared one (each buffer grows at least once), a second release_scratch halfway.
+
+    Routes of predict at Np = 768, n_out = 2, D = 3 by the predicates of the dispatch table (sr_common.h): T = 1 one
+    query (streamed, one launch, polling finaliser; the general family: K* pass + streamed), T = 3 the 2 .. 4-query
+    MFMA form, T = 40 streamed (<= SR_STREAM_MAX_T), T = 300 streamed in groups of 16 (<= 16 x sr_var_small_groups_max
+    = 1008), T = 1100 balanced shares (6 x 9 x 2 = 108 plain workgroups <= 1024), T = 11000 plain 128-tiles (6 x 86 x 2
+    = 1032 > 1024; T = 300 would not get there at this size: it stays in the list for the groups-of-16 route)."""
+    import torch
+    from safe_exploration_amd import SimpleGPModel, gp_reachability as reach
+    rng = np.random.default_rng(2611)
+    N0, m_add, D = 600, 60, 3
+    Z = rng.uniform(-1, 1, (N0 + m_add, D))
+    Y = np.sin(2.0 * Z.dot(rng.standard_normal((D, 2)))) + 0.05 * rng.standard_normal((N0 + m_add, 2))
+    hyp = [dict(orc.make_hyp(kt, rng, D), noise_variance=nv) for nv in (0.02, 0.03)]
+    Ts = (1, 3, 40, 300, 1100, 11000)
+    xq = rng.uniform(-0.9, 0.9, (Ts[-1], D))
+    pool = rng.uniform(-1, 1, (300, D))
+    seeds = [3, 57, 111, 160, 201, 250, 299, 8, 77, 140]
+    tz = np.array([[0.8, -0.3], [0.2, 1.1]])
+
+    def onestep(gp, T):
+        return reach.onestep_reachability_batch(xq[:T, :2], gp, xq[:T, 2:], np.full(2, 0.1), np.full(2, 0.2), None, None,
+                                                2.0, t_z_gp=tz)
+
+    def model():
+        gp = SimpleGPModel(2, 2, 1, kern_types=[kt] * 2, hyp=hyp)
+        gp.train(Z[:N0], Y[:N0], opt_hyp=False)
+        gp.append_limit = 10 ** 9
+        return gp
+
+    def append(gp):
+        gp.update_model(Z[N0:], Y[N0:], opt_hyp=False, replace_old=False)
+        assert gp._handle.N == N0 + m_add and gp._handle.Np == 768
+        return torch.from_numpy(xq).to(gp._handle.device)
+
+    def calls(gp, x, hist):
+        """the compared outputs by name; hist: a smaller batch in front of each call and a release halfway"""
+        out = {}
+        for T in (Ts if hist else Ts[::-1]):
+            out["predict %d" % T] = gp.predict_device(x[:T], True)
+        if hist:
+            gp.predict_device_grad(x[:20])
+        out["grad"] = gp.predict_device_grad(x[:130])
+        if hist:
+            gp.release_scratch()
+            gp.linearize_device_batch(x[:20])
+        out["linearize batch"] = gp.linearize_device_batch(x[:130])
+        out["linearize"] = tuple(np.array(o) for o in gp.linearize_predict(xq[:1, :2], xq[:1, 2:], True))
+        if hist:
+            onestep(gp, 5)
+        out["onestep"] = tuple(np.array(o) for o in onestep(gp, 50))
+        if hist:
+            _life_cycle_select(gp, pool[:150], 20, [3, 57, 111, 8, 77])
+        out["select"] = _life_cycle_select(gp, pool, 40, seeds)
+        return out
+
+    a = model()
+    xa = torch.from_numpy(xq).to(a._handle.device)
+    assert a._handle.Np == 640
+    for T in (3, 40, 300, 1100):
+        a.predict_device(xa[:T], True)
+    a.predict_device_grad(xa[:130])
+    a.linearize_device_batch(xa[:40])
+    a.linearize_predict(xq[:1, :2], xq[:1, 2:], True)
+    onestep(a, 30)
+    _life_cycle_select(a, pool[:100], 12, [3, 57, 8, 77])
+    xa = append(a)
+    a.release_scratch()
+    res_a = calls(a, xa, True)
+    b = model()
+    res_b = calls(b, append(b), False)
+    assert sorted(res_a) == sorted(res_b)
+    for name in res_b:
+        assert len(res_a[name]) == len(res_b[name])
+        for u, v in zip(res_a[name], res_b[name]):
+            if isinstance(u, torch.Tensor):
+                assert torch.equal(u, v), name
+            else:
+                assert np.array_equal(u, v), name
+
+
 def test_distance_to_center_batch_vs_reference_golden():
     """A9 batch kernel against the reference's utils_ellipsoid.distance_to_center outputs."""
     from safe_exploration_amd import utils_ellipsoid as ue
