@@ -254,6 +254,19 @@ int sr_moment_step(int device, long T, int n_s, int n_u, int mode, const double*
                    const double* var_g, const double* jac_g, const double* a, const double* b,
                    double* mu_out, double* sigma_out, void* stream);
 
+/* ---- exact moment matching: the GP at Gaussian inputs (beyond the reference, which has the two approximations above) ----
+ * For T inputs z ~ N(m[t], S[t]) (m T x D; S T x D x D symmetric PSD, may be singular; NULL = all zero) the exact mean,
+ * the FULL covariance across outputs and the expected Jacobian of an ARD-RBF model (Deisenroth's closed forms):
+ *   mu T x n_out ; cov T x n_out x n_out (exactly symmetric, diagonal clipped at 1e-15; exactly zero off the diagonal where
+ *   S[t] == 0) ; V T x n_out x D (may be NULL): cov(z, g_a) = S V_a, and V_a -> d mu_a/dx as S -> 0.
+ * inv_k n_out x N x N: the matrices sr_gp_inv_k writes, back to back (on a sparse handle: P P^T, the matrix of its variance).
+ * Cost: T n_out (n_out + 1) / 2 N^2 evaluations of exp; queries go through in chunks of sr_gp_set_chunk with a grow-only
+ * scratch owned by the handle (freed by sr_gp_release_scratch).  Asynchronous on `stream`; the same inputs give the same bits.
+ * SR_ESTATE not factorized; SR_EUNSUPPORTED a general-family model (the closed form is for ARD-RBF only);
+ * SR_EINVAL NULL argument or T < 0; T == 0 is a no-op. */
+int sr_gp_moment_match(sr_gp_t h, const double* m, const double* S, long T, const double* inv_k,
+                       double* mu, double* cov, double* V, void* stream);
+
 /* replaces: utils.compute_remainder_overapproximations  utils.py:108-144 (batched)
  * q T x n_s x n_s, k_fb T x n_u x n_s -> u_mu T x n_s, u_sigma T x n_s */
 int sr_remainder_overapprox(int device, long T, int n_s, int n_u, const double* q, const double* k_fb,

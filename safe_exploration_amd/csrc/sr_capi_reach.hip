@@ -308,6 +308,35 @@ extern "C" int sr_multistep_moments(sr_gp_t h, long T, int H, int mode, const do
                           gp_var_all, nullptr, (hipStream_t)stream);
 }
 
+// exact moment matching (sr_moment_match.hip).  Reads the model where the handle holds it (alpha may be a slid view: single
+// doubles are loaded, no unslide()); writes nothing into the handle but the grow-only scratch.
+extern "C" int sr_gp_moment_match(sr_gp_t h, const double* m, const double* S, long T, const double* inv_k, double* mu,
+                                  double* cov, double* V, void* stream) {
+    SR_CHECK(h != nullptr, SR_EINVAL, "sr_gp_moment_match: NULL handle");
+    SR_CHECK(h->factorized, SR_ESTATE, "sr_gp_moment_match: model not factorized");
+    if (h->general) {
+        sr_set_error("sr_gp_moment_match: the closed form is for ARD-RBF models only (data set with sr_gp_set_data)");
+        return SR_EUNSUPPORTED;
+    }
+    SR_CHECK(T >= 0, SR_EINVAL, "sr_gp_moment_match: T=%ld", T);
+    if (T == 0) return SR_OK;
+    SR_CHECK(m && inv_k && mu && cov, SR_EINVAL, "sr_gp_moment_match: NULL argument");
+    hipStream_t s = (hipStream_t)stream;
+    SR_DEVICE(h->device);
+    const long per = sr_mm_ws_per_query(h->N, h->D, h->n_out);
+    // a chunk: the handle's, what the launch grid takes, and at most 2^28 doubles (2 GB) of scratch
+    const long chunk = std::max(1L, std::min({h->chunk, sr_mm_max_queries(h->N, h->n_out), ((long)1 << 28) / per}));
+    const long DD = (long)h->D * h->D, nn = (long)h->n_out * h->n_out;
+    SR_TRY(h->mm_ws.grow((size_t)(std::min(chunk, T) * per), wait::stream(s)));
+    for (long t0 = 0; t0 < T; t0 += chunk) {
+        const long Tc = std::min(chunk, T - t0);
+        SR_TRY(sr_launch_moment_match(h->Z, h->alpha, h->ls, h->sf2, h->N, h->Np, h->D, h->n_out, m + t0 * h->D,
+                                      S ? S + t0 * DD : nullptr, Tc, inv_k, mu + t0 * h->n_out, cov + t0 * nn,
+                                      V ? V + t0 * h->n_out * h->D : nullptr, h->mm_ws.get(), s));
+    }
+    return SR_OK;
+}
+
 extern "C" int sr_moment_step(int device, long T, int n_s, int n_u, int mode, const double* mu_x,
                               const double* sigma_x, const double* k_ff, const double* k_fb, const double* mu_g,
                               const double* var_g, const double* jac_g, const double* a, const double* b,

@@ -175,6 +175,13 @@ int sr_launch_mll(const double* Kinv, int Np, int N, const double* alpha, const 
                   const double* kp, int D, const double* logdet, double* partial, double* nll, double* grad,
                   hipStream_t s);
 int sr_launch_logdet(const double* Wt, int Np, int n_out, double* out, hipStream_t s);
+// exact moment matching (sr_moment_match.hip): one chunk of T <= sr_mm_max_queries queries of an ARD-RBF model at Gaussian
+// inputs N(m, S) (S NULL: points); ws: T x sr_mm_ws_per_query doubles (the D x D algebra per query and the partial sums)
+long sr_mm_ws_per_query(int N, int D, int n_out);
+long sr_mm_max_queries(int N, int n_out);
+int sr_launch_moment_match(const double* Z, const double* alpha, const double* ls, const double* sf2, int N, int Np, int D,
+                           int n_out, const double* m, const double* S, long T, const double* inv_k, double* mu,
+                           double* cov, double* V, double* ws, hipStream_t s);
 int sr_launch_fill(double* p, size_t n, double v, hipStream_t s);
 // Wt = J U^T J from the factor as the model update leaves it (diagonal 128-blocks in U, block rows in W; sr_sparse.hip);
 // nbatch members, U / W sS and Wt sD doubles apart

@@ -129,6 +129,9 @@ struct sr_gp {
     // sr_gp_select_maxvar: the pivoted factor L (n_out x (m - 1) x padded pool) and [var | partial scores |
     // partial rows | taken marks]
     srh::scratch<double> sel_L, sel_ws;
+    // sr_gp_moment_match: per query of a chunk the D x D algebra of every output and pair of outputs, and the row tiles'
+    // partial sums of the double sum (sr_mm_ws_per_query doubles each)
+    srh::scratch<double> mm_ws;
     // log det(K + noise) per output as of the last <= 16-row append (read back with its status words): the blocking read of
     // sr_gp_logdet costs the exploration loop 30 us per step
     std::vector<double> logdet_host; int logdet_valid = 0;

@@ -180,6 +180,7 @@ class SimpleGPModel(StateSpaceModel):
         self.y_train = None
         self._beta = None
         self._inv_K = None
+        self._inv_K_dev = None
         self._handle = None
         self._noise_diag = None
         self._z_fit = None           # the inputs / targets the device model is conditioned on (== z unless Z was
@@ -383,7 +384,7 @@ class SimpleGPModel(StateSpaceModel):
         idx = np.asarray(chosen)
         self.z, self.x_train, self.y_train = x[idx], x, y         # the model now is the GP on the chosen rows
         self._z_fit, self._y_z = x[idx], y[idx]
-        self._beta = self._inv_K = None
+        self._beta = self._inv_K = self._inv_K_dev = None
         return (x[idx], y[idx], idx) if return_index else (x[idx], y[idx])
 
     def _choose_downdate(self, x, y, m, chosen, noise_diag, return_index, return_scores):
@@ -404,7 +405,7 @@ class SimpleGPModel(StateSpaceModel):
         self.gp_trained = True
         self.z, self.x_train, self.y_train = x[idx], x, y
         self._z_fit, self._y_z = x[idx], y[idx]
-        self._beta = self._inv_K = None
+        self._beta = self._inv_K = self._inv_K_dev = None
         res = (x[idx], y[idx], idx) if return_index else (x[idx], y[idx])
         return res + (scores,) if return_scores else res
 
@@ -480,6 +481,7 @@ class SimpleGPModel(StateSpaceModel):
         self._handle = handle
         self._beta = None
         self._inv_K = None
+        self._inv_K_dev = None
         if old is not None and old is not handle and getattr(old, "_server_armed", False):
             try:
                 self.start_server(old._server_idle)
@@ -661,6 +663,7 @@ class SimpleGPModel(StateSpaceModel):
             self._z_fit, self._y_z = self.x_train, self.y_train
             self._beta = None
             self._inv_K = None
+            self._inv_K_dev = None
 
     def _grown(self, x0, xs, y0, ys):
         """[x0; xs], [y0; ys] as views of buffers with room to grow (a vstack per appended point copies the whole
@@ -699,6 +702,7 @@ class SimpleGPModel(StateSpaceModel):
         self._handle = handle
         self._beta = None
         self._inv_K = None
+        self._inv_K_dev = None
         if old is not None and old is not handle and getattr(old, "_server_armed", False):
             # a refit with a new size replaced the handle: the server follows -- the model is already in place, so a
             # failure to re-arm leaves the launched routes, not an exception out of the update
@@ -767,6 +771,47 @@ class SimpleGPModel(StateSpaceModel):
             self._inv_K = out
         return self._inv_K
 
+    def inv_K_device(self):
+        """(n_out, N, N) device tensor of the matrices ``sr_gp_inv_k`` writes (K_y^-1 per output; P P^T of a sparse model), kept
+        until the next model update: what ``moment_match_device`` contracts the double sum against."""
+        self._need_trained()
+        if self._inv_K_dev is None:
+            hd = self._handle
+            t = B.empty((hd.n_out, hd.N, hd.N), hd.device)
+            for d in range(hd.n_out):
+                check(lib.sr_gp_inv_k(hd.h, d, B.ptr(t[d]), B.stream_ptr(hd.device)))
+            self._inv_K_dev = t
+        return self._inv_K_dev
+
+    def moment_match_device(self, m, S=None):
+        """Exact moment matching on device tensors (``sr_gp_moment_match``): the GP at T Gaussian inputs z ~ N(m[t], S[t]).
+        m (T, D); S (T, D, D) symmetric PSD (may be singular) or None = point inputs.
+        Returns mu (T, n), cov (T, n, n) -- the full covariance across outputs -- and V (T, n, D) with cov(z, g_a) = S V_a
+        (V -> the mean Jacobian as S -> 0).  ARD-RBF models only (NotImplementedError otherwise).  Asynchronous."""
+        self._need_trained()
+        if any(kt != "rbf" for kt in self.kern_types):
+            raise NotImplementedError("moment matching: the closed form is for ARD-RBF models only")
+        hd = self._handle
+        tm = B.as_dev(m, hd.device)
+        if tm.dim() != 2 or tm.shape[1] != hd.D:
+            raise ValueError("m must be (T, {})".format(hd.D))
+        T = tm.shape[0]
+        tS = B.as_dev(S, hd.device, (T, hd.D, hd.D)) if S is not None else None
+        kinv = self.inv_K_device()
+        mu, cov = B.empty((T, hd.n_out), hd.device), B.empty((T, hd.n_out, hd.n_out), hd.device)
+        V = B.empty((T, hd.n_out, hd.D), hd.device)
+        check(lib.sr_gp_moment_match(hd.h, B.ptr(tm), B.ptr(tS), T, B.ptr(kinv), B.ptr(mu), B.ptr(cov), B.ptr(V),
+                                     B.stream_ptr(hd.device)))
+        return mu, cov, V
+
+    def predict_uncertain(self, mean, cov=None):
+        """NumPy form of ``moment_match_device``: mean (T, D) or (D,), cov (T, D, D) or (D, D) or None
+        -> mu (T, n), Cov (T, n, n), V (T, n, D)."""
+        mean = np.atleast_2d(np.asarray(mean, dtype=np.float64))
+        if cov is not None:
+            cov = np.asarray(cov, dtype=np.float64).reshape(mean.shape[0], mean.shape[1], mean.shape[1])
+        return tuple(B.to_numpy(o) for o in self.moment_match_device(mean, cov))
+
     def export_state(self):
         """(alpha (n_out,N), Wt (n_out,Np,Np)) device tensors -- what a broadcast receiver imports."""
         self._need_trained()
@@ -828,6 +873,7 @@ class SimpleGPModel(StateSpaceModel):
         self._noise_diag = noise_diag
         self._beta = None
         self._inv_K = None
+        self._inv_K_dev = None
         self.z = Z
         self.x_train = Z
         self.y_train = Y
@@ -852,6 +898,7 @@ class SimpleGPModel(StateSpaceModel):
         self._noise_diag = noise_diag
         self._beta = None
         self._inv_K = None
+        self._inv_K_dev = None
         self.z = Z
         self.x_train = Z
         self.y_train = Y

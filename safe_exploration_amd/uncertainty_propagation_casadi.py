@@ -8,14 +8,22 @@ multi_step_taylor_symbolic :88-146, mean_equivalent_multistep :149-207, one_step
 (mean-equivalent); it runs in the same per-query kernel as the robust ellipsoid step.
 The input transform ``a_gp_inp_x`` of the reference (the GP sees ``a_gp_inp_x @ state``, :40-47,60) is supported:
 the state Jacobian is chain-ruled through the constant matrix.
+
+Beyond the reference: EXACT moment matching (``MOMENT_MATCHING``; ``one_step_moment_matching``,
+``multi_step_moment_matching``, ``moment_matching_batch``), the scheme the two above approximate.  The GP is evaluated at
+the Gaussian input z = G x + g0, G = [a_gp_inp_x; K], g0 = [0; k_ff] (``SimpleGPModel.moment_match_device``: mean, full
+covariance across outputs and expected Jacobian V in closed form), and with A = a + b K
+``mu_new = A mu + b k_ff + mu_g``, ``Sigma_new = (A + V G) Sigma (A + V G)^T + Cov - (V G) Sigma (V G)^T``.
+An initial covariance ``sigma_0`` is supported there.
 """
 import numpy as np
+import torch
 
 from . import _buffers as B
 from ._lib import lib, check
 from .ssm_hip.gaussian_process import SimpleGPModel
 
-TAYLOR, MEAN_EQUIVALENT = 1, 2
+TAYLOR, MEAN_EQUIVALENT, MOMENT_MATCHING = 1, 2, 3
 
 
 def _lin(a, b, n_s, n_u):
@@ -143,3 +151,98 @@ def mean_equivalent_multistep(mu_0, ssm, k_ff, k_fb, sigma_0=None, a=None, b=Non
 
 
 multi_step_taylor_symbolic = multi_step_taylor      # the reference's name (uncertainty_propagation_casadi.py:11)
+
+
+# ---------------------------------------------------------------------------------------------- exact moment matching
+def _mm_step(ssm, mu, sigma, kff, K, ta, tb, tz):
+    """One exact step on device tensors: mu (T,n_s), sigma (T,n_s,n_s) or None, kff (T,n_u), K (T,n_u,n_s) or None (= 0),
+    tz (n_x_in,n_s).  The control is u = K x + k_ff.  Returns mu_new, sigma_new, Cov of the GP outputs."""
+    T, n_s = mu.shape
+    zx = mu.matmul(tz.t())
+    if K is None:
+        A = ta.expand(T, n_s, n_s)
+        zu = kff
+        G = torch.cat((tz.expand(T, -1, -1), kff.new_zeros((T, kff.shape[1], n_s))), dim=1)
+    else:
+        A = ta + tb.matmul(K)
+        zu = kff + K.matmul(mu.unsqueeze(2)).squeeze(2)
+        G = torch.cat((tz.expand(T, -1, -1), K), dim=1)
+    S = None if sigma is None else G.matmul(sigma).matmul(G.transpose(1, 2))
+    mu_g, cov, V = ssm.moment_match_device(torch.cat((zx, zu), dim=1), S)
+    mu_new = A.matmul(mu.unsqueeze(2)).squeeze(2) + kff.matmul(tb.t()) + mu_g
+    if sigma is None:
+        return mu_new, cov, cov
+    VG = V.matmul(G)
+    Hm = A + VG
+    sigma_new = Hm.matmul(sigma).matmul(Hm.transpose(1, 2)) + cov - VG.matmul(sigma).matmul(VG.transpose(1, 2))
+    return mu_new, sigma_new, cov
+
+
+def _mm_setup(ssm, a, b, a_gp_inp_x):
+    if not isinstance(ssm, SimpleGPModel):
+        raise TypeError("moment matching needs the HIP SimpleGPModel")
+    ssm._need_trained()
+    hd = ssm._handle
+    n_s = hd.n_out
+    tzn = np.eye(n_s) if a_gp_inp_x is None else np.asarray(a_gp_inp_x, dtype=np.float64)
+    if tzn.ndim != 2 or tzn.shape[1] != n_s or tzn.shape[0] > hd.D:
+        raise ValueError("a_gp_inp_x must be (n_x_in, {}) with n_x_in <= {}".format(n_s, hd.D))
+    n_u = hd.D - tzn.shape[0]
+    a, b = _lin(a, b, n_s, n_u)
+    dev = hd.device
+    return dev, n_s, n_u, B.const_dev(a, dev, (n_s, n_s)), B.const_dev(b, dev, (n_s, n_u)), B.const_dev(tzn, dev, tzn.shape)
+
+
+def moment_matching_batch(mu_0, ssm, k_ff, k_fb, a=None, b=None, sigma_0=None, a_gp_inp_x=None):
+    """Exact moment matching for T trajectories x H steps.  mu_0 (T,n_s); k_ff (T,H,n_u); k_fb (T,H-1,n_u,n_s) (step 0 has
+    no feedback, step i >= 1 uses k_fb[:, i-1]); sigma_0 (T,n_s,n_s) or None (a point).
+    Returns mu_all (T,H,n_s), sigma_all (T,H,n_s,n_s), gp_cov_all (T,H,n_s,n_s) (the GP's full output covariance).
+    H calls of ``sr_gp_moment_match`` with the small algebra in batched torch ops; nothing synchronises between steps.
+    Device tensors in -> device tensors out."""
+    dev, n_s, n_u, ta, tb, tz = _mm_setup(ssm, a, b, a_gp_inp_x)
+    as_t = B.is_tensor(mu_0)
+    mu = B.as_dev(mu_0, dev)
+    T = mu.shape[0]
+    kff = B.as_dev(k_ff, dev)
+    if mu.dim() != 2 or mu.shape[1] != n_s or kff.dim() != 3 or kff.shape[0] != T or kff.shape[2] != n_u:
+        raise ValueError("mu_0 must be (T, {}) and k_ff (T, H, {})".format(n_s, n_u))
+    H = kff.shape[1]
+    kfb = B.as_dev(k_fb, dev, (T, H - 1, n_u, n_s)) if H > 1 else None
+    sigma = B.as_dev(sigma_0, dev, (T, n_s, n_s)) if sigma_0 is not None else None
+    mu_all, sigma_all = B.empty((T, H, n_s), dev), B.empty((T, H, n_s, n_s), dev)
+    cov_all = B.empty((T, H, n_s, n_s), dev)
+    for i in range(H):
+        mu, sigma, cov = _mm_step(ssm, mu, sigma, kff[:, i], None if i == 0 else kfb[:, i - 1], ta, tb, tz)
+        mu_all[:, i], sigma_all[:, i], cov_all[:, i] = mu, sigma, cov
+    outs = (mu_all, sigma_all, cov_all)
+    return outs if as_t else tuple(B.to_numpy(o) for o in outs)
+
+
+def one_step_moment_matching(mu_x, ssm, k_ff, sigma_x=None, k_fb=None, a=None, b=None, a_gp_inp_x=None):
+    """Exact moment matching of N(mu_x, sigma_x) through the GP dynamics with u = k_fb x + k_ff; shapes as
+    ``one_step_taylor``: mu_x (n_s,1), k_ff (n_u,1) -> mu_new (n_s,1), sigma_new (n_s,n_s), diag of the GP's output
+    covariance (1,n_s)."""
+    dev, n_s, n_u, ta, tb, tz = _mm_setup(ssm, a, b, a_gp_inp_x)
+    if sigma_x is not None and k_fb is None:
+        raise ValueError("k_fb is required when sigma_x is given")
+    mu = B.as_dev(np.asarray(mu_x, dtype=np.float64).reshape(1, n_s), dev)
+    kff = B.as_dev(np.asarray(k_ff, dtype=np.float64).reshape(1, n_u), dev)
+    sigma = B.as_dev(sigma_x, dev, (1, n_s, n_s)) if sigma_x is not None else None
+    K = B.as_dev(k_fb, dev, (1, n_u, n_s)) if sigma_x is not None else None
+    mu_new, sigma_new, cov = _mm_step(ssm, mu, sigma, kff, K, ta, tb, tz)
+    return (B.to_numpy(mu_new).reshape(n_s, 1), B.to_numpy(sigma_new)[0],
+            B.to_numpy(torch.diagonal(cov, dim1=1, dim2=2)).reshape(1, n_s))
+
+
+def multi_step_moment_matching(mu_0, ssm, k_ff, k_fb, sigma_0=None, a=None, b=None, a_gp_inp_x=None):
+    """Exact moment matching over H steps; shapes as ``multi_step_taylor``: k_ff (H,n_u), k_fb H-1 gains (n_u,n_s);
+    ``sigma_0`` (n_s,n_s) is supported.  Returns mu_all (H,n_s), sigma_all (H,n_s*n_s), diag of the GP's output covariance
+    (H,n_s)."""
+    k_ff = np.asarray(k_ff, dtype=np.float64)
+    H, n_u = k_ff.shape
+    n_s = np.shape(mu_0)[0]
+    kfb = np.asarray(k_fb, dtype=np.float64).reshape(H - 1, n_u, n_s)[None] if H > 1 else None
+    s0 = None if sigma_0 is None else np.asarray(sigma_0, dtype=np.float64).reshape(1, n_s, n_s)
+    mu_all, sigma_all, cov_all = moment_matching_batch(np.asarray(mu_0, dtype=np.float64).reshape(1, n_s), ssm, k_ff[None],
+                                                       kfb, a, b, s0, a_gp_inp_x)
+    return mu_all[0], sigma_all[0].reshape(H, n_s * n_s), np.diagonal(cov_all[0], axis1=1, axis2=2).copy()
