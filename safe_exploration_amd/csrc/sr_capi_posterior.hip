@@ -193,7 +193,7 @@ static int stream_linearize(sr_gp* h, const double* x, double* mu, double* var, 
     a.mode = 1; a.dot0 = 1;
     a.la = la; a.lin_part = h->lin_v.get(); a.lin_part_w = h->lin_v.get();
     a.nblk = fused ? 2 * ncb : nblk256;
-    a.lin_dt = h->D <= 3 ? 3 : (h->D <= 5 ? 5 : (h->D <= 8 ? 8 : 12));
+    a.lin_dt = sr_width_bucket(h->D);
     a.lmu = mu; a.lvar = var; a.ljac_mu = jac_mu;
     SR_TRY(stream_items(h, a, ncols, 0, false, s));
     h->last_streamed = 0;

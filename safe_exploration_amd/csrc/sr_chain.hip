@@ -423,60 +423,6 @@ __global__ __launch_bounds__(64 * SR_CHAIN_NW) void sr_chain_kernel(sr_chain_arg
     }
 }
 
-template <int NP, int NS, int NU>
-static int launch_chain_np(const sr_chain_args& a, hipStream_t s) {
-    constexpr int DT = (NS + NU <= 3) ? 3 : (NS + NU <= 5 ? 5 : 8);
-    const unsigned groups = (unsigned)((a.T + SR_FQ - 1) / SR_FQ);
-    const size_t ctl_bytes = sizeof(double) * SR_FQ * ((size_t)a.H * NU + (size_t)(a.H - 1) * NU * NS);
-    hipLaunchKernelGGL((sr_chain_kernel<NP, DT, NS, NU>), dim3(groups * SR_CHAIN_WPG(NP, NS) - a.test_drop), dim3(64 * SR_CHAIN_NW), ctl_bytes, s, a);
-    SR_HIP(hipGetLastError());
-    return SR_OK;
-}
-
-template <int NP, int NS, int NU>
-static int chain_occupancy_np(int H, int* blocks) {
-    constexpr int DT = (NS + NU <= 3) ? 3 : (NS + NU <= 5 ? 5 : 8);
-    const size_t ctl_bytes = sizeof(double) * SR_FQ * ((size_t)H * NU + (size_t)(H - 1) * NU * NS);
-    SR_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks, sr_chain_kernel<NP, DT, NS, NU>, 64 * SR_CHAIN_NW, ctl_bytes));
-    return SR_OK;
-}
-template <int NS, int NU>
-static int chain_occupancy_su(int Np, int H, int* blocks) {
-    switch (Np) {
-        case 128: return chain_occupancy_np<128, NS, NU>(H, blocks);
-        case 256: return chain_occupancy_np<256, NS, NU>(H, blocks);
-        case 384: return chain_occupancy_np<384, NS, NU>(H, blocks);
-        case 512: return chain_occupancy_np<512, NS, NU>(H, blocks);
-    }
-    *blocks = 0;
-    return SR_OK;
-}
-int sr_chain_blocks_per_cu(int Np, int n_s, int n_u, int H, int* blocks) {
-    *blocks = 0;
-    if (n_u == 1) {
-        if (n_s == 1) return chain_occupancy_su<1, 1>(Np, H, blocks);
-        if (n_s == 2) return chain_occupancy_su<2, 1>(Np, H, blocks);
-        if (n_s == 3) return chain_occupancy_su<3, 1>(Np, H, blocks);
-        if (n_s == 4) return chain_occupancy_su<4, 1>(Np, H, blocks);
-    } else if (n_u == 2) {
-        if (n_s == 2) return chain_occupancy_su<2, 2>(Np, H, blocks);
-        if (n_s == 3) return chain_occupancy_su<3, 2>(Np, H, blocks);
-    }
-    return SR_OK;
-}
-
-template <int NS, int NU>
-static int launch_chain_su(const sr_chain_args& a, hipStream_t s) {
-    switch (a.k.Np) {
-        case 128: return launch_chain_np<128, NS, NU>(a, s);
-        case 256: return launch_chain_np<256, NS, NU>(a, s);
-        case 384: return launch_chain_np<384, NS, NU>(a, s);
-        case 512: return launch_chain_np<512, NS, NU>(a, s);
-    }
-    sr_set_error("chain: Np=%d not supported", a.k.Np);
-    return SR_EUNSUPPORTED;
-}
-
 // the systems of the reference's experiments (pendulum 2 + 1, cart-pole 4 + 1) and their neighbours; anything else
 // runs the per-step launches
 // Every instantiation is scratch-free (profiles/archive/r03_kernel_resources.txt: 147 .. 254 VGPRs, no spills) since the
@@ -484,6 +430,36 @@ static int launch_chain_su(const sr_chain_args& a, hipStream_t s) {
 // registers of the 256 per lane) without the live ranges of sr_ellipsoid_one beside them, and the tail workgroup holds no
 // fragments.  (Round 2 / early round 3: one body did both -- up to 328 B of scratch per lane, and the dispatcher had
 // to leave n_s = 4 at Np >= 384 and n_s >= 3 at Np = 512 to the per-step launches.)
+// The (n_s, n_u) pairs the chain kernel is compiled for are stated here once (chain_pairs): sr_chain_supported,
+// sr_chain_blocks_per_cu and sr_launch_chain all read this list.
+template <int NS, int NU> struct chain_su { static constexpr int ns = NS, nu = NU; };
+template <class... P> struct chain_list {};
+using chain_pairs = chain_list<chain_su<1, 1>, chain_su<2, 1>, chain_su<3, 1>, chain_su<4, 1>, chain_su<2, 2>, chain_su<3, 2>>;
+
+template <class... P>
+static bool chain_has_pair(int n_s, int n_u, chain_list<P...>) { return ((n_s == P::ns && n_u == P::nu) || ...); }
+
+// f(np, su) for the instantiation of (Np, n_s, n_u): np an integral constant, su a chain_su
+template <class F, class... P>
+static int chain_pick(int Np, int n_s, int n_u, F&& f, chain_list<P...>) {
+    int rc = SR_EUNSUPPORTED;
+    const bool hit = ((n_s == P::ns && n_u == P::nu &&
+                       ((rc = sr_pick_np("chain: Np=%d not supported", Np, [&](auto np) { return f(np, P{}); })), true)) || ...);
+    if (!hit) sr_set_error("chain: n_s=%d n_u=%d not instantiated", n_s, n_u);
+    return rc;
+}
+
+// (asked only for models that sr_chain_supported takes)
+int sr_chain_blocks_per_cu(int Np, int n_s, int n_u, int H, int* blocks) {
+    *blocks = 0;
+    return chain_pick(Np, n_s, n_u, [&](auto np, auto su) {
+        constexpr int NP = decltype(np)::value, NS = decltype(su)::ns, NU = decltype(su)::nu;
+        const size_t ctl_bytes = sizeof(double) * SR_FQ * ((size_t)H * NU + (size_t)(H - 1) * NU * NS);
+        SR_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks, sr_chain_kernel<NP, sr_width_bucket(NS + NU), NS, NU>, 64 * SR_CHAIN_NW, ctl_bytes));
+        return SR_OK;
+    }, chain_pairs{});
+}
+
 static bool sr_chain_dispatched(int Np, int n_s, int n_u) {
     (void)Np; (void)n_s; (void)n_u;
     return true;
@@ -497,7 +473,7 @@ long sr_chain_xels_per_group(int Np, int n_s, int n_u, int H) {
 bool sr_chain_supported(int Np, int D, int n_s, int n_u, int H) {
     if (!(Np % 128 == 0 && Np <= SR_FUSED_NP && D == n_s + n_u)) return false;
     if ((long)H * (n_u + n_u * n_s) * SR_FQ * 8 > 24576) return false;      // the group's control sequence lives in LDS
-    if (!((n_u == 1 && n_s >= 1 && n_s <= 4) || (n_u == 2 && (n_s == 2 || n_s == 3)))) return false;
+    if (!chain_has_pair(n_s, n_u, chain_pairs{})) return false;
     return sr_chain_dispatched(Np, n_s, n_u);
 }
 
@@ -507,16 +483,11 @@ int sr_launch_chain(const sr_chain_args& a, hipStream_t s) {
              "chain: %ld rollouts x %d outputs x %d parts do not fit one launch", a.T, n_s, a.k.Np / 128);
     SR_CHECK((a.T + SR_FQ - 1) / SR_FQ * sr_chain_xels_per_group(a.k.Np, n_s, n_u, a.H) <= (long)SR_CHAIN_XELS, SR_EINVAL,
              "chain: exchange buffer too small for %ld rollouts x %d steps", a.T, a.H);
-    if (n_u == 1) {
-        if (n_s == 1) return launch_chain_su<1, 1>(a, s);
-        if (n_s == 2) return launch_chain_su<2, 1>(a, s);
-        if (n_s == 3) return launch_chain_su<3, 1>(a, s);
-        if (n_s == 4) return launch_chain_su<4, 1>(a, s);
-    } else if (n_u == 2) {
-        if (n_s == 2) return launch_chain_su<2, 2>(a, s);
-        if (n_s == 3) return launch_chain_su<3, 2>(a, s);
-    }
-    sr_set_error("chain: n_s=%d n_u=%d not instantiated", n_s, n_u);
-    return SR_EUNSUPPORTED;
+    return chain_pick(a.k.Np, n_s, n_u, [&](auto np, auto su) {
+        constexpr int NP = decltype(np)::value, NS = decltype(su)::ns, NU = decltype(su)::nu;
+        const unsigned groups = (unsigned)((a.T + SR_FQ - 1) / SR_FQ);
+        const size_t ctl_bytes = sizeof(double) * SR_FQ * ((size_t)a.H * NU + (size_t)(a.H - 1) * NU * NS);
+        return sr_launch(sr_chain_kernel<NP, sr_width_bucket(NS + NU), NS, NU>, dim3(groups * SR_CHAIN_WPG(NP, NS) - a.test_drop),
+                         dim3(64 * SR_CHAIN_NW), ctl_bytes, s, a);
+    }, chain_pairs{});
 }
-

@@ -49,6 +49,8 @@ static inline bool sr_lab_on(const char* name) { return sr_lab_str(name) != null
 #define SR_TRY(expr)                                                                  \
     do { int rc_ = (expr); if (rc_ != SR_OK) return rc_; } while (0)
 
+#include "sr_dispatch.h"   // sr_width_bucket, sr_pick_le / _eq / _np, sr_launch (uses SR_HIP)
+
 typedef double d4_t __attribute__((ext_vector_type(4)));
 
 struct sr_prof_rec { int id; hipEvent_t e0, e1; };

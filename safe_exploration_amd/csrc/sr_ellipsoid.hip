@@ -115,15 +115,8 @@ int sr_launch_distance(long T, int K, int n_s, const double* samples, int per_t,
                        const double* q, double* d, hipStream_t s) {
     if (T <= 0 || K <= 0) return SR_OK;
     dim3 grid((unsigned)((T * K + 255) / 256));
-#define SR_DIST_CASE(NS) case NS: hipLaunchKernelGGL(sr_distance_kernel<NS>, grid, dim3(256), 0, s, T, K, samples, per_t, p, q, d); break
-    switch (n_s) {
-        SR_DIST_CASE(1); SR_DIST_CASE(2); SR_DIST_CASE(3); SR_DIST_CASE(4);
-        SR_DIST_CASE(5); SR_DIST_CASE(6); SR_DIST_CASE(7); SR_DIST_CASE(8);
-        default: sr_set_error("distance: n_s=%d outside 1..%d", n_s, SR_MAX_NS); return SR_EUNSUPPORTED;
-    }
-#undef SR_DIST_CASE
-    SR_HIP(hipGetLastError());
-    return SR_OK;
+    return sr_pick_eq<1, 2, 3, 4, 5, 6, 7, 8>("distance: n_s=%d outside 1..8", n_s, [&](auto ns) {
+        return sr_launch(sr_distance_kernel<decltype(ns)::value>, grid, dim3(256), 0, s, T, K, samples, per_t, p, q, d); });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -174,65 +167,28 @@ int sr_launch_sample(long T, int size, int n_out, int n_u, const double* mu, con
 // ---------------------------------------------------------------------------------------------
 // dispatch on (n_s, n_u)
 // ---------------------------------------------------------------------------------------------
-template <int NS>
-static int launch_ell_ns(const sr_ell_args& a, hipStream_t s) {
-    dim3 grid((unsigned)((a.T + 255) / 256));
-    switch (a.n_u) {
-        case 1: hipLaunchKernelGGL((sr_ellipsoid_kernel<NS, 1>), grid, dim3(256), 0, s, a); break;
-        case 2: hipLaunchKernelGGL((sr_ellipsoid_kernel<NS, 2>), grid, dim3(256), 0, s, a); break;
-        case 3: hipLaunchKernelGGL((sr_ellipsoid_kernel<NS, 3>), grid, dim3(256), 0, s, a); break;
-        case 4: hipLaunchKernelGGL((sr_ellipsoid_kernel<NS, 4>), grid, dim3(256), 0, s, a); break;
-        default: sr_set_error("ellipsoid: n_u=%d outside 1..%d", a.n_u, SR_MAX_NU); return SR_EUNSUPPORTED;
-    }
-    SR_HIP(hipGetLastError());
-    return SR_OK;
+// f(ns, nu) with the two sizes as integral constants; the refusals are the caller's texts
+template <class F>
+static int pick_ns_nu(const char* fmt_ns, int n_s, const char* fmt_nu, int n_u, F&& f) {
+    static_assert(SR_MAX_NS == 8 && SR_MAX_NU == 4, "the two lists below");
+    return sr_pick_eq<1, 2, 3, 4, 5, 6, 7, 8>(fmt_ns, n_s, [&](auto ns) {
+        return sr_pick_eq<1, 2, 3, 4>(fmt_nu, n_u, [&](auto nu) { return f(ns, nu); }); });
 }
 
 int sr_launch_ellipsoid(const sr_ell_args& a, hipStream_t s) {
     if (a.T <= 0) return SR_OK;
-    switch (a.n_s) {
-        case 1: return launch_ell_ns<1>(a, s);
-        case 2: return launch_ell_ns<2>(a, s);
-        case 3: return launch_ell_ns<3>(a, s);
-        case 4: return launch_ell_ns<4>(a, s);
-        case 5: return launch_ell_ns<5>(a, s);
-        case 6: return launch_ell_ns<6>(a, s);
-        case 7: return launch_ell_ns<7>(a, s);
-        case 8: return launch_ell_ns<8>(a, s);
-        default: sr_set_error("ellipsoid: n_s=%d outside 1..%d", a.n_s, SR_MAX_NS); return SR_EUNSUPPORTED;
-    }
-}
-
-template <int NS>
-static int launch_rem_ns(long T, int n_u, const double* q, const double* k, const double* lm,
-                         const double* lsg, double* um, double* us, hipStream_t s) {
-    dim3 grid((unsigned)((T + 255) / 256));
-    switch (n_u) {
-        case 1: hipLaunchKernelGGL((sr_remainder_kernel<NS, 1>), grid, dim3(256), 0, s, T, q, k, lm, lsg, um, us); break;
-        case 2: hipLaunchKernelGGL((sr_remainder_kernel<NS, 2>), grid, dim3(256), 0, s, T, q, k, lm, lsg, um, us); break;
-        case 3: hipLaunchKernelGGL((sr_remainder_kernel<NS, 3>), grid, dim3(256), 0, s, T, q, k, lm, lsg, um, us); break;
-        case 4: hipLaunchKernelGGL((sr_remainder_kernel<NS, 4>), grid, dim3(256), 0, s, T, q, k, lm, lsg, um, us); break;
-        default: sr_set_error("remainder: n_u=%d outside 1..%d", n_u, SR_MAX_NU); return SR_EUNSUPPORTED;
-    }
-    SR_HIP(hipGetLastError());
-    return SR_OK;
+    return pick_ns_nu("ellipsoid: n_s=%d outside 1..8", a.n_s, "ellipsoid: n_u=%d outside 1..4", a.n_u, [&](auto ns, auto nu) {
+        return sr_launch(sr_ellipsoid_kernel<decltype(ns)::value, decltype(nu)::value>, dim3((unsigned)((a.T + 255) / 256)), dim3(256), 0,
+                         s, a); });
 }
 
 int sr_launch_remainder(long T, int n_s, int n_u, const double* q, const double* k_fb,
                         const double* l_mu, const double* l_sigma, double* u_mu, double* u_sigma,
                         hipStream_t s) {
     if (T <= 0) return SR_OK;
-    switch (n_s) {
-        case 1: return launch_rem_ns<1>(T, n_u, q, k_fb, l_mu, l_sigma, u_mu, u_sigma, s);
-        case 2: return launch_rem_ns<2>(T, n_u, q, k_fb, l_mu, l_sigma, u_mu, u_sigma, s);
-        case 3: return launch_rem_ns<3>(T, n_u, q, k_fb, l_mu, l_sigma, u_mu, u_sigma, s);
-        case 4: return launch_rem_ns<4>(T, n_u, q, k_fb, l_mu, l_sigma, u_mu, u_sigma, s);
-        case 5: return launch_rem_ns<5>(T, n_u, q, k_fb, l_mu, l_sigma, u_mu, u_sigma, s);
-        case 6: return launch_rem_ns<6>(T, n_u, q, k_fb, l_mu, l_sigma, u_mu, u_sigma, s);
-        case 7: return launch_rem_ns<7>(T, n_u, q, k_fb, l_mu, l_sigma, u_mu, u_sigma, s);
-        case 8: return launch_rem_ns<8>(T, n_u, q, k_fb, l_mu, l_sigma, u_mu, u_sigma, s);
-        default: sr_set_error("remainder: n_s=%d outside 1..%d", n_s, SR_MAX_NS); return SR_EUNSUPPORTED;
-    }
+    return pick_ns_nu("remainder: n_s=%d outside 1..8", n_s, "remainder: n_u=%d outside 1..4", n_u, [&](auto ns, auto nu) {
+        return sr_launch(sr_remainder_kernel<decltype(ns)::value, decltype(nu)::value>, dim3((unsigned)((T + 255) / 256)), dim3(256), 0,
+                         s, T, q, k_fb, l_mu, l_sigma, u_mu, u_sigma); });
 }
 
 int sr_launch_safety(long T, int n_s, int m, const double* p, const double* q, const double* h_mat,

@@ -301,19 +301,12 @@ __global__ __launch_bounds__(256) void sr_lin_final_kernel(sr_lin_args a, const 
 
 int sr_launch_lin_columns(const sr_lin_args& a, int tq, double* Ks, double* lin_part, hipStream_t s) {
     dim3 grid((a.Np + 255) / 256, a.n_out);
-#define SR_LC_CASE(DT) hipLaunchKernelGGL(sr_lin_columns_kernel<DT>, grid, dim3(256), 0, s, a, tq, Ks, lin_part)
-    if (a.D <= 3) SR_LC_CASE(3);
-    else if (a.D <= 5) SR_LC_CASE(5);
-    else if (a.D <= 8) SR_LC_CASE(8);
-    else if (a.D <= 12) SR_LC_CASE(12);
-    else { sr_set_error("linearize: D=%d > %d", a.D, SR_MAX_D); return SR_EUNSUPPORTED; }
-#undef SR_LC_CASE
-    SR_HIP(hipGetLastError());
-    return SR_OK;
+    return sr_pick_le<3, 5, 8, 12>("linearize", a.D, [&](auto dt) {
+        return sr_launch(sr_lin_columns_kernel<decltype(dt)::value>, grid, dim3(256), 0, s, a, tq, Ks, lin_part); });
 }
 
 int sr_lin_nacc(int D) {
-    const int DT = D <= 3 ? 3 : (D <= 5 ? 5 : (D <= 8 ? 8 : 12));
+    const int DT = sr_width_bucket(D);
     return 1 + DT + DT * (DT + 1) / 2;
 }
 
@@ -321,33 +314,16 @@ int sr_launch_lin_final(const sr_lin_args& a, const double* lin_part, const doub
                         double* var, double* jac_mu, hipStream_t s) {
     const int nblk = (a.Np + 255) / 256;
     // NACC <= 91 (D = 12) and D*D <= 144 threads are needed: one block of 256 covers every case
-    const int DT = a.D <= 3 ? 3 : (a.D <= 5 ? 5 : (a.D <= 8 ? 8 : 12));
-    hipLaunchKernelGGL(sr_lin_final_kernel, dim3(a.n_out), dim3(256), 0, s, a, lin_part, nblk, DT, dots, ncb, mu, var,
-                       jac_mu);
+    hipLaunchKernelGGL(sr_lin_final_kernel, dim3(a.n_out), dim3(256), 0, s, a, lin_part, nblk, sr_width_bucket(a.D), dots, ncb, mu,
+                       var, jac_mu);
     SR_HIP(hipGetLastError());
     return SR_OK;
 }
 
 int sr_launch_linearize(const sr_lin_args& a, hipStream_t s) {
     dim3 grid(a.n_out);
-    if (a.kp) {
-#define SR_LING_CASE(DT) hipLaunchKernelGGL(sr_linearize_general_kernel<DT>, grid, dim3(256), 0, s, a)
-        if (a.D <= 3) SR_LING_CASE(3);
-        else if (a.D <= 5) SR_LING_CASE(5);
-        else if (a.D <= 8) SR_LING_CASE(8);
-        else if (a.D <= 12) SR_LING_CASE(12);
-        else { sr_set_error("linearize: D=%d > %d", a.D, SR_MAX_D); return SR_EUNSUPPORTED; }
-#undef SR_LING_CASE
-        SR_HIP(hipGetLastError());
-        return SR_OK;
-    }
-#define SR_LIN_CASE(DT) hipLaunchKernelGGL(sr_linearize_kernel<DT>, grid, dim3(256), 0, s, a)
-    if (a.D <= 3) SR_LIN_CASE(3);
-    else if (a.D <= 5) SR_LIN_CASE(5);
-    else if (a.D <= 8) SR_LIN_CASE(8);
-    else if (a.D <= 12) SR_LIN_CASE(12);
-    else { sr_set_error("linearize: D=%d > %d", a.D, SR_MAX_D); return SR_EUNSUPPORTED; }
-#undef SR_LIN_CASE
-    SR_HIP(hipGetLastError());
-    return SR_OK;
+    return sr_pick_le<3, 5, 8, 12>("linearize", a.D, [&](auto dt) {
+        constexpr int DT = decltype(dt)::value;
+        return a.kp ? sr_launch(sr_linearize_general_kernel<DT>, grid, dim3(256), 0, s, a)
+                    : sr_launch(sr_linearize_kernel<DT>, grid, dim3(256), 0, s, a); });
 }

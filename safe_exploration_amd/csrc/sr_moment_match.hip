@@ -337,13 +337,15 @@ __global__ __launch_bounds__(256) void sr_mm_final_kernel(sr_mm_args a) {
 }
 
 template <int DT>
-static void mm_launch(const sr_mm_args& a, hipStream_t s) {
+static int mm_launch(const sr_mm_args& a, hipStream_t s) {
     const long nprep = a.T * (a.n_out + a.npairs);
     constexpr int BT = mm_prep_bt<DT>::value;
     hipLaunchKernelGGL((sr_mm_prep_kernel<DT>), dim3((unsigned)((nprep + BT - 1) / BT)), dim3(BT), 0, s, a);
     hipLaunchKernelGGL((sr_mm_mean_kernel<DT>), dim3((unsigned)a.T, a.n_out), dim3(256), 0, s, a);
     hipLaunchKernelGGL((sr_mm_pair_kernel<DT>), dim3((unsigned)a.T, a.nit, a.npairs), dim3(256), 0, s, a);
     hipLaunchKernelGGL(sr_mm_final_kernel, dim3((unsigned)((a.T * a.npairs + 255) / 256)), dim3(256), 0, s, a);
+    SR_HIP(hipGetLastError());
+    return SR_OK;
 }
 
 // queries one launch sequence may take: grid.y / grid.z stay below 65536, the grid of KM2 below 2^23 workgroups
@@ -363,10 +365,5 @@ int sr_launch_moment_match(const double* Z, const double* alpha, const double* l
     a.T = T;
     SR_CHECK(a.npairs < 65536 && a.nit < 65536 && T <= sr_mm_max_queries(N, n_out), SR_EUNSUPPORTED,
              "moment_match: n_out=%d N=%d T=%ld outside the launch grid", n_out, N, T);
-    if (D <= 4) mm_launch<4>(a, s);
-    else if (D <= 8) mm_launch<8>(a, s);
-    else if (D <= SR_MAX_D) mm_launch<12>(a, s);
-    else { sr_set_error("moment_match: D=%d > %d", D, SR_MAX_D); return SR_EUNSUPPORTED; }
-    SR_HIP(hipGetLastError());
-    return SR_OK;
+    return sr_pick_le<4, 8, 12>("moment_match", D, [&](auto dt) { return mm_launch<decltype(dt)::value>(a, s); });
 }

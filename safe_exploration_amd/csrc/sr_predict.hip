@@ -214,41 +214,23 @@ __global__ __launch_bounds__(256) void sr_kstar_general_kernel(sr_kstar_args a) 
 }
 
 int sr_launch_kstar(const sr_kstar_args& a, hipStream_t s) {
-    dim3 grid((unsigned)(((a.Tw ? a.Tw : a.Tp) + 255) / 256), a.n_out, a.nsplit);
-    if (a.kp) {
-#define SR_KSTARG_CASE(DT) hipLaunchKernelGGL(sr_kstar_general_kernel<DT>, grid, dim3(256), 0, s, a)
-        if (a.D <= 3) SR_KSTARG_CASE(3);
-        else if (a.D <= 5) SR_KSTARG_CASE(5);
-        else if (a.D <= 8) SR_KSTARG_CASE(8);
-        else if (a.D <= 12) SR_KSTARG_CASE(12);
-        else { sr_set_error("kstar: D=%d > %d", a.D, SR_MAX_D); return SR_EUNSUPPORTED; }
-#undef SR_KSTARG_CASE
-        SR_HIP(hipGetLastError());
-        return SR_OK;
-    }
-#define SR_KSTAR_CASE(DT) \
-    hipLaunchKernelGGL((sr_kstar_kernel<DT, 1>), grid, dim3(256), 0, s, a)
+    const long tpad = a.Tw ? a.Tw : a.Tp;
+    dim3 grid((unsigned)((tpad + 255) / 256), a.n_out, a.nsplit);
+    if (a.kp)
+        return sr_pick_le<3, 5, 8, 12>("kstar", a.D, [&](auto dt) {
+            return sr_launch(sr_kstar_general_kernel<decltype(dt)::value>, grid, dim3(256), 0, s, a); });
     // big batches: two queries per thread (65536 queries at N = 5000: 1.32 -> 1.19 ms; four: 1.32 -- the registers
     // of four exp chains cost the occupancy what the sharing buys)
-    if (a.D <= 5 && (a.Tw ? a.Tw : a.Tp) >= 8192) {
-        const long tpad = a.Tw ? a.Tw : a.Tp;
+    if (a.D <= 5 && tpad >= 8192) {
         dim3 g2((unsigned)((tpad + 511) / 512), a.n_out, a.nsplit);
         // round 6: the two queries of a thread are neighbours and a row of K* leaves as ONE non-temporal 16-byte store per lane
         // (same box, 65536 queries at N = 5000: 1.49 ms with two 8-byte stores 2 KiB apart, 1.47 with plain 16-byte stores,
         // 1.28 non-temporal -- the 5.2 GB pass through the caches once; profiles/r06_headline_sweeps.txt)
-        if (a.D <= 3) hipLaunchKernelGGL((sr_kstar_kernel<3, 2, 2>), g2, dim3(256), 0, s, a);
-        else hipLaunchKernelGGL((sr_kstar_kernel<5, 2, 2>), g2, dim3(256), 0, s, a);
-        SR_HIP(hipGetLastError());
-        return SR_OK;
+        return sr_pick_le<3, 5>("kstar", a.D, [&](auto dt) {
+            return sr_launch(sr_kstar_kernel<decltype(dt)::value, 2, 2>, g2, dim3(256), 0, s, a); });
     }
-    if (a.D <= 3) SR_KSTAR_CASE(3);
-    else if (a.D <= 5) SR_KSTAR_CASE(5);
-    else if (a.D <= 8) SR_KSTAR_CASE(8);
-    else if (a.D <= 12) SR_KSTAR_CASE(12);
-    else { sr_set_error("kstar: D=%d > %d", a.D, SR_MAX_D); return SR_EUNSUPPORTED; }
-#undef SR_KSTAR_CASE
-    SR_HIP(hipGetLastError());
-    return SR_OK;
+    return sr_pick_le<3, 5, 8, 12>("kstar", a.D, [&](auto dt) {
+        return sr_launch(sr_kstar_kernel<decltype(dt)::value, 1>, grid, dim3(256), 0, s, a); });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -860,16 +842,13 @@ int sr_launch_var_small(const double* Wt, const double* Ks, double* Vp, double* 
     const int groups = T > SR_TS ? (T + SR_TS - 1) / SR_TS : 1;
     // plain (cached) loads: at N = 5000 the 210 MB of U^-1 stay in the 256 MB Infinity Cache between calls --
     // measured 6.8 TB/s effective; non-temporal loads were 14 % slower
-#define SR_SMALL_LAUNCH(TQ)                                                                              \
-    hipLaunchKernelGGL(sr_var_small_partial_kernel<TQ>, dim3(npairs, n_out), dim3(256), 0, s, Wt, Ks, Vp, Np, \
-                       Tp, npairs, k_lo)
-    if (T <= 1) SR_SMALL_LAUNCH(1);
-    else if (T <= 4) SR_SMALL_LAUNCH(4);
+    if (T <= 4)
+        SR_TRY((sr_pick_le<1, 4>("var_small", T, [&](auto tq) {
+            return sr_launch(sr_var_small_partial_kernel<decltype(tq)::value>, dim3(npairs, n_out), dim3(256), 0, s, Wt, Ks, Vp, Np,
+                             Tp, npairs, k_lo); })));
     else
-        hipLaunchKernelGGL(sr_var_small_partial_mfma_kernel, dim3(npairs, n_out, groups), dim3(1024), 0, s, Wt, Ks, Vp,
-                           Np, Tp, npairs, k_lo);
-#undef SR_SMALL_LAUNCH
-    SR_HIP(hipGetLastError());
+        SR_TRY(sr_launch(sr_var_small_partial_mfma_kernel, dim3(npairs, n_out, groups), dim3(1024), 0, s, Wt, Ks, Vp,
+                         Np, Tp, npairs, k_lo));
     if (!reduce) return SR_OK;                     // the caller gathers the partial products itself (sr_gp_append)
     const int tq = small_tq(T);
     hipLaunchKernelGGL(sr_var_small_reduce_kernel, dim3(ncb, n_out, tq * groups), dim3(256), 0, s, Vp, part, Tp,

@@ -233,18 +233,10 @@ static int launch_grad_g(const sr_grad_args& a, bool gen, int n_out, hipStream_t
     const long blocks = (long)n_out * ngrp * npair * a.group;
     SR_CHECK(blocks < 2147483647L, SR_EINVAL, "predict_grad: grid too large (%ld blocks)", blocks);
     const dim3 grid((unsigned)blocks);
-#define SR_GRAD_CASE(DT)                                                                                  \
-    do {                                                                                                 \
-        if (gen) hipLaunchKernelGGL((sr_grad_g_kernel<DT, true>), grid, dim3(256), 0, s, a);              \
-        else hipLaunchKernelGGL((sr_grad_g_kernel<DT, false>), grid, dim3(256), 0, s, a);                 \
-    } while (0)
-    if (a.D <= 3) SR_GRAD_CASE(3);
-    else if (a.D <= 5) SR_GRAD_CASE(5);
-    else if (a.D <= 8) SR_GRAD_CASE(8);
-    else { sr_set_error("predict_grad: D=%d > %d", a.D, SR_GRAD_MAX_D); return SR_EUNSUPPORTED; }
-#undef SR_GRAD_CASE
-    SR_HIP(hipGetLastError());
-    return SR_OK;
+    return sr_pick_le<3, 5, 8>("predict_grad", a.D, [&](auto dt) {
+        constexpr int DT = decltype(dt)::value;
+        return gen ? sr_launch(sr_grad_g_kernel<DT, true>, grid, dim3(256), 0, s, a)
+                   : sr_launch(sr_grad_g_kernel<DT, false>, grid, dim3(256), 0, s, a); });
 }
 
 // workspace of the gradient route: V (the shape of K*) and the row blocks' partial sums
@@ -480,17 +472,10 @@ static int hess_pass(sr_gp* h, long Tc, const double* Xq, double* hess_mu, hipSt
     a.hpart = h->hess_part.get();
     a.N = h->N; a.Np = h->Np; a.D = h->D; a.n_out = h->n_out; a.nsplit = nsplit; a.nhp = nhp; a.T = Tc; a.Tp = Tp;
     const dim3 grid((unsigned)((Tp + 255) / 256), h->n_out, nsplit);
-#define SR_HESS_CASE(DT)                                                                                  \
-    do {                                                                                                 \
-        if (h->general) hipLaunchKernelGGL((sr_hess_kernel<DT, true>), grid, dim3(256), 0, s, a);         \
-        else hipLaunchKernelGGL((sr_hess_kernel<DT, false>), grid, dim3(256), 0, s, a);                   \
-    } while (0)
-    if (h->D <= 3) SR_HESS_CASE(3);
-    else if (h->D <= 5) SR_HESS_CASE(5);
-    else if (h->D <= 8) SR_HESS_CASE(8);
-    else { sr_set_error("linearize_batch: D=%d > %d", h->D, SR_GRAD_MAX_D); return SR_EUNSUPPORTED; }
-#undef SR_HESS_CASE
-    SR_HIP(hipGetLastError());
+    SR_TRY((sr_pick_le<3, 5, 8>("linearize_batch", h->D, [&](auto dt) {
+        constexpr int DT = decltype(dt)::value;
+        return h->general ? sr_launch(sr_hess_kernel<DT, true>, grid, dim3(256), 0, s, a)
+                          : sr_launch(sr_hess_kernel<DT, false>, grid, dim3(256), 0, s, a); })));
     const long n = Tc * h->n_out * nhd;
     hipLaunchKernelGGL(sr_hess_finish_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, h->hess_part.get(), h->ls,
                        hess_mu, h->general, h->n_out, h->D, nsplit, nhp, Tc, Tp);

@@ -452,31 +452,15 @@ template <int NP>
 static int launch_server_np(const sr_kstar_args& a, const double* Wt, const sr_server_args& sv, hipStream_t s) {
     const sr_server_model m{a.Z, a.alpha, a.ls, a.sf2, Wt, a.kp, a.N, a.D, a.n_out};
     SR_CHECK(sr_gp_server_supported(NP, a.D), SR_EUNSUPPORTED, "gp_server: Np=%d D=%d not built", NP, a.D);
-    if (a.kp) {                                            // general kernel family: in parts at every size
-        static_assert(sr_gp_server_parts(NP, true) == NP / 64, "parts");
-        dim3 grid(NP / 64, a.n_out);
-        if (a.D <= 3) hipLaunchKernelGGL((sr_gp_server_parts_kernel<NP, 3, true>), grid, dim3(512), 0, s, m, sv);
-        else hipLaunchKernelGGL((sr_gp_server_parts_kernel<NP, 5, true>), grid, dim3(512), 0, s, m, sv);
-    } else if constexpr (NP >= 256) {
-        static_assert(sr_gp_server_parts(NP, false) == NP / 64, "parts");
-        dim3 grid(NP / 64, a.n_out);
-        if (a.D <= 3) hipLaunchKernelGGL((sr_gp_server_parts_kernel<NP, 3, false>), grid, dim3(512), 0, s, m, sv);
-        else hipLaunchKernelGGL((sr_gp_server_parts_kernel<NP, 5, false>), grid, dim3(512), 0, s, m, sv);
-    } else {
-        dim3 grid(1, a.n_out);
-        if (a.D <= 3) hipLaunchKernelGGL((sr_gp_server_kernel<NP, 3>), grid, dim3(1024), 0, s, m, sv);
-        else hipLaunchKernelGGL((sr_gp_server_kernel<NP, 5>), grid, dim3(1024), 0, s, m, sv);
-    }
-    SR_HIP(hipGetLastError());
-    return SR_OK;
+    return sr_pick_le<3, 5>("gp_server", a.D, [&](auto dt) {
+        constexpr int DT = decltype(dt)::value;
+        static_assert(sr_gp_server_parts(NP, true) == NP / 64 && (NP < 256 || sr_gp_server_parts(NP, false) == NP / 64), "parts");
+        const dim3 parts(NP / 64, a.n_out);
+        if (a.kp) return sr_launch(sr_gp_server_parts_kernel<NP, DT, true>, parts, dim3(512), 0, s, m, sv);   // general kernel family: in parts at every size
+        if constexpr (NP >= 256) return sr_launch(sr_gp_server_parts_kernel<NP, DT, false>, parts, dim3(512), 0, s, m, sv);
+        else return sr_launch(sr_gp_server_kernel<NP, DT>, dim3(1, a.n_out), dim3(1024), 0, s, m, sv); });
 }
 
 int sr_launch_gp_server(const sr_kstar_args& a, const double* Wt, const sr_server_args& sv, hipStream_t s) {
-    if (a.Np == 128) return launch_server_np<128>(a, Wt, sv, s);
-    if (a.Np == 256) return launch_server_np<256>(a, Wt, sv, s);
-    if (a.Np == 384) return launch_server_np<384>(a, Wt, sv, s);
-    if (a.Np == 512) return launch_server_np<512>(a, Wt, sv, s);
-    sr_set_error("gp_server: Np=%d not supported", a.Np);
-    return SR_EUNSUPPORTED;
+    return sr_pick_np("gp_server: Np=%d not supported", a.Np, [&](auto np) { return launch_server_np<decltype(np)::value>(a, Wt, sv, s); });
 }
-

@@ -222,58 +222,27 @@ template <int NP>
 static int launch_small_np(const sr_kstar_args& a, const double* Wt, double* mu, double* var, double* jac,
                            double* jac_var, double* hess, hipStream_t s) {
     if (hess && a.kp) {                                    // the same for the general kernel family (D <= 5)
-        dim3 grid(1, a.n_out);
         SR_CHECK(a.D <= 5, SR_EUNSUPPORTED, "gp_small: second order of a general kernel in one launch needs D <= 5 (D=%d)", a.D);
-        if (a.D <= 3) hipLaunchKernelGGL((sr_gp_small_gen_lin_kernel<NP, 3>), grid, dim3(1024), 0, s, a, Wt, mu, var, jac, jac_var, hess);
-        else hipLaunchKernelGGL((sr_gp_small_gen_lin_kernel<NP, 5>), grid, dim3(1024), 0, s, a, Wt, mu, var, jac, jac_var, hess);
-        SR_HIP(hipGetLastError());
-        return SR_OK;
+        return sr_pick_le<3, 5>("gp_small", a.D, [&](auto dt) {
+            return sr_launch(sr_gp_small_gen_lin_kernel<NP, decltype(dt)::value>, dim3(1, a.n_out), dim3(1024), 0, s, a, Wt, mu, var,
+                             jac, jac_var, hess); });
     }
-    if (hess) {                                            // single query with second-order outputs
-        dim3 grid(1, a.n_out);
-#define SR_SMALL_LIN(DT) hipLaunchKernelGGL((sr_gp_small_kernel<NP, DT, true>), grid, dim3(1024), 0, s, a, Wt, mu, var, jac, jac_var, hess)
-        if (a.D <= 3) SR_SMALL_LIN(3);
-        else if (a.D <= 5) SR_SMALL_LIN(5);
-        else SR_SMALL_LIN(8);
-#undef SR_SMALL_LIN
-        SR_HIP(hipGetLastError());
-        return SR_OK;
-    }
-    dim3 grid((unsigned)((a.T + SR_FQ - 1) / SR_FQ), a.n_out);
-    if (a.kp) {                                            // general kernel family
-#define SR_SMALL_GEN(DT) hipLaunchKernelGGL((sr_gp_small_general_kernel<NP, DT>), grid, dim3(1024), 0, s, a, Wt, mu, var, jac)
-        if (a.D <= 3) SR_SMALL_GEN(3);
-        else if (a.D <= 5) SR_SMALL_GEN(5);
-        else SR_SMALL_GEN(8);
-#undef SR_SMALL_GEN
-        SR_HIP(hipGetLastError());
-        return SR_OK;
-    }
-#define SR_SMALL_CASE(DT) hipLaunchKernelGGL((sr_gp_small_kernel<NP, DT, false>), grid, dim3(1024), 0, s, a, Wt, mu, var, jac, nullptr, nullptr)
-    if (a.D <= 3) SR_SMALL_CASE(3);
-    else if (a.D <= 5) SR_SMALL_CASE(5);
-    else SR_SMALL_CASE(8);
-#undef SR_SMALL_CASE
-    SR_HIP(hipGetLastError());
-    return SR_OK;
+    // single query with second-order outputs: one workgroup per output
+    const dim3 grid(hess ? 1u : (unsigned)((a.T + SR_FQ - 1) / SR_FQ), a.n_out);
+    return sr_pick_le<3, 5, 8>("gp_small", a.D, [&](auto dt) {
+        constexpr int DT = decltype(dt)::value;
+        if (hess) return sr_launch(sr_gp_small_kernel<NP, DT, true>, grid, dim3(1024), 0, s, a, Wt, mu, var, jac, jac_var, hess);
+        if (a.kp) return sr_launch(sr_gp_small_general_kernel<NP, DT>, grid, dim3(1024), 0, s, a, Wt, mu, var, jac);   // general kernel family
+        return sr_launch(sr_gp_small_kernel<NP, DT, false>, grid, dim3(1024), 0, s, a, Wt, mu, var, jac, nullptr, nullptr); });
 }
 
 int sr_launch_gp_small(const sr_kstar_args& a, const double* Wt, double* mu, double* var, double* jac,
                        hipStream_t s) {
-    if (a.Np == 128) return launch_small_np<128>(a, Wt, mu, var, jac, nullptr, nullptr, s);
-    if (a.Np == 256) return launch_small_np<256>(a, Wt, mu, var, jac, nullptr, nullptr, s);
-    if (a.Np == 384) return launch_small_np<384>(a, Wt, mu, var, jac, nullptr, nullptr, s);
-    if (a.Np == 512) return launch_small_np<512>(a, Wt, mu, var, jac, nullptr, nullptr, s);
-    sr_set_error("gp_small: Np=%d not supported", a.Np);
-    return SR_EUNSUPPORTED;
+    return sr_launch_gp_small_lin(a, Wt, mu, var, jac, nullptr, nullptr, s);
 }
 
 int sr_launch_gp_small_lin(const sr_kstar_args& a, const double* Wt, double* mu, double* var, double* jac_mu,
                            double* jac_var, double* hess_mu, hipStream_t s) {
-    if (a.Np == 128) return launch_small_np<128>(a, Wt, mu, var, jac_mu, jac_var, hess_mu, s);
-    if (a.Np == 256) return launch_small_np<256>(a, Wt, mu, var, jac_mu, jac_var, hess_mu, s);
-    if (a.Np == 384) return launch_small_np<384>(a, Wt, mu, var, jac_mu, jac_var, hess_mu, s);
-    if (a.Np == 512) return launch_small_np<512>(a, Wt, mu, var, jac_mu, jac_var, hess_mu, s);
-    sr_set_error("gp_small: Np=%d not supported", a.Np);
-    return SR_EUNSUPPORTED;
+    return sr_pick_np("gp_small: Np=%d not supported", a.Np, [&](auto np) {
+        return launch_small_np<decltype(np)::value>(a, Wt, mu, var, jac_mu, jac_var, hess_mu, s); });
 }

@@ -1019,15 +1019,12 @@ int sr_launch_stream(sr_stream_args a, int src, hipStream_t s) {
     dim3 grid(a.npairs, a.n_out);
     if (nc <= 4) {
         SR_CHECK(src == 0 || (a.D <= 5 && (src == 1 || a.D + 1 <= 4)), SR_EINVAL, "stream: src %d with D = %d", src, a.D);
-#define SR_ST1(TQ, SRC, DT) hipLaunchKernelGGL((sr_stream1_kernel<TQ, SRC, DT>), grid, dim3(SR_ST1_THREADS), 0, s, a)
-        if (src == 0) { if (nc == 1) SR_ST1(1, 0, 1); else SR_ST1(4, 0, 1); }
-        else if (src == 1) {
-            if (a.D <= 3) { if (nc == 1) SR_ST1(1, 1, 3); else SR_ST1(4, 1, 3); }
-            else { if (nc == 1) SR_ST1(1, 1, 5); else SR_ST1(4, 1, 5); }
-        } else SR_ST1(4, 2, 3);
-#undef SR_ST1
-        SR_HIP(hipGetLastError());
-        return SR_OK;
+        if (src == 2) return sr_launch(sr_stream1_kernel<4, 2, 3>, grid, dim3(SR_ST1_THREADS), 0, s, a);
+        return sr_pick_le<1, 4>("stream", nc, [&](auto tq) {           // columns per thread
+            constexpr int TQ = decltype(tq)::value;
+            if (src == 0) return sr_launch(sr_stream1_kernel<TQ, 0, 1>, grid, dim3(SR_ST1_THREADS), 0, s, a);
+            return sr_pick_le<3, 5>("stream", a.D, [&](auto dt) {
+                return sr_launch(sr_stream1_kernel<TQ, 1, decltype(dt)::value>, grid, dim3(SR_ST1_THREADS), 0, s, a); }); });
     }
     SR_CHECK(src == 0 || (src == 1 && a.D <= 5), SR_EINVAL, "stream: src %d with %d columns, D = %d", src, a.ncols, a.D);
     a.ncols_pad = a.ncols;
@@ -1039,17 +1036,13 @@ int sr_launch_stream(sr_stream_args a, int src, hipStream_t s) {
         // (columns evaluated in the kernel: 16 or 32 per workgroup only -- every column block re-evaluates the chunk's rows,
         //  and from 64 columns on that costs a workgroup more than the K* pass it saves: N = 3000, T = 64 76 -> 93 us)
         SR_CHECK(src == 0 || g <= 2, SR_EINVAL, "stream: %d columns per workgroup are not evaluated in the kernel", 16 * g);
-#define SR_M1(G_) do { if (src == 0) hipLaunchKernelGGL((sr_stream_mfma1_kernel<G_, 0, 1>), grid, dim3(1024), 0, s, a); \
-                       else if (a.D <= 3) hipLaunchKernelGGL((sr_stream_mfma1_kernel<G_, 1, 3>), grid, dim3(1024), 0, s, a); \
-                       else hipLaunchKernelGGL((sr_stream_mfma1_kernel<G_, 1, 5>), grid, dim3(1024), 0, s, a); } while (0)
-        switch (g) {
-            case 1: SR_M1(1); break;
-            case 2: SR_M1(2); break;
-            case 4: hipLaunchKernelGGL((sr_stream_mfma1_kernel<4, 0, 1>), grid, dim3(1024), 0, s, a); break;
-            default: hipLaunchKernelGGL((sr_stream_mfma1_kernel<8, 0, 1>), grid, dim3(1024), 0, s, a); break;
-        }
-#undef SR_M1
-        SR_HIP(hipGetLastError());
+        SR_TRY((sr_pick_eq<1, 2, 4, 8>("stream: %d groups of 16 columns per workgroup", g, [&](auto gc) {
+            constexpr int G = decltype(gc)::value;
+            if constexpr (G <= 2) {
+                if (src == 1) return sr_pick_le<3, 5>("stream", a.D, [&](auto dt) {
+                    return sr_launch(sr_stream_mfma1_kernel<G, 1, decltype(dt)::value>, grid, dim3(1024), 0, s, a); });
+            }
+            return sr_launch(sr_stream_mfma1_kernel<G, 0, 1>, grid, dim3(1024), 0, s, a); })));
         hipLaunchKernelGGL(sr_stream_reduce1_kernel, dim3(a.ncb, a.n_out, a.ncols), dim3(256), 0, s, a, nc);
         SR_HIP(hipGetLastError());
         return SR_OK;
@@ -1058,16 +1051,12 @@ int sr_launch_stream(sr_stream_args a, int src, hipStream_t s) {
              (a.nwg == a.nitems || g == 4), SR_EINVAL, "stream: no work-item table (sr_stream_items)");
     const int nitems = a.nitems;
     grid.x = a.nwg;
-    switch (g) {
-        case 1: hipLaunchKernelGGL(sr_stream_mfma_kernel<1>, grid, dim3(1024), 0, s, a); break;
-        case 2: hipLaunchKernelGGL(sr_stream_mfma_kernel<2>, grid, dim3(1024), 0, s, a); break;
-        case 4:
-            if (a.nwg < nitems) hipLaunchKernelGGL((sr_stream_mfma_kernel<4, true>), grid, dim3(1024), 0, s, a);
-            else hipLaunchKernelGGL(sr_stream_mfma_kernel<4>, grid, dim3(1024), 0, s, a);
-            break;
-        default: hipLaunchKernelGGL(sr_stream_mfma_kernel<8>, grid, dim3(1024), 0, s, a); break;
-    }
-    SR_HIP(hipGetLastError());
+    SR_TRY((sr_pick_eq<1, 2, 4, 8>("stream: %d groups of 16 columns per workgroup", g, [&](auto gc) {
+        constexpr int G = decltype(gc)::value;
+        if constexpr (G == 4) {
+            if (a.nwg < nitems) return sr_launch(sr_stream_mfma_kernel<4, true>, grid, dim3(1024), 0, s, a);
+        }
+        return sr_launch(sr_stream_mfma_kernel<G>, grid, dim3(1024), 0, s, a); })));
     hipLaunchKernelGGL(sr_stream_reduce_kernel, dim3(a.ncols, a.n_out), dim3(512), 0, s, a, nc, a.kr, nitems);
     SR_HIP(hipGetLastError());
     return SR_OK;

@@ -120,15 +120,9 @@ int sr_launch_mll(const double* Kinv, int Np, int N, const double* alpha, const 
                   hipStream_t s) {
     const int nb = (N + 15) / 16;
     dim3 grid(nb, nb);
-    int DT;
-#define SR_MLL_CASE(DTV) DT = DTV; hipLaunchKernelGGL(sr_mll_grad_kernel<DTV>, grid, dim3(256), 0, s, Kinv, Np, N, alpha, Z, kp, D, partial)
-    if (D <= 3) { SR_MLL_CASE(3); }
-    else if (D <= 5) { SR_MLL_CASE(5); }
-    else if (D <= 8) { SR_MLL_CASE(8); }
-    else if (D <= 12) { SR_MLL_CASE(12); }
-    else { sr_set_error("mll: D=%d > %d", D, SR_MAX_D); return SR_EUNSUPPORTED; }
-#undef SR_MLL_CASE
-    SR_HIP(hipGetLastError());
+    const int DT = sr_width_bucket(D);
+    SR_TRY((sr_pick_le<3, 5, 8, 12>("mll", D, [&](auto dt) {
+        return sr_launch(sr_mll_grad_kernel<decltype(dt)::value>, grid, dim3(256), 0, s, Kinv, Np, N, alpha, Z, kp, D, partial); })));
     const int nacc = 3 + 3 * DT;
     hipLaunchKernelGGL(sr_mll_reduce_kernel, dim3(nacc + 1), dim3(256), 0, s, partial, (long)nb * nb, nacc, DT, D,
                        yT, alpha, Np, N, logdet, nll, grad);

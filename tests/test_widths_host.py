@@ -1,5 +1,5 @@
 """The width lists of tests/test_gpu_widths.py follow the sources: the route thresholds and the padded-width ladder are
-read from the HIP sources, and every edge and edge + 1 must be in the lists of the group that tests that route.  If a
+read from the HIP sources (the ladder from its one definition in sr_dispatch.h), and every edge and edge + 1 must be in the lists of the group that tests that route.  If a
 threshold moves and the matrix does not, this fails on the CPU.  Runs without a GPU."""
 import os
 import re
@@ -21,14 +21,13 @@ def _define(src, name):
     return int(m.group(1))
 
 
-def _ladders():
-    """every padded-width ladder `D <= a ? a : (D <= b ? b : (... : z))` of the dispatch code, as (a, b, ..., z)"""
-    out = []
-    for name in ("sr_capi_posterior.hip", "sr_linearize.hip"):
-        for m in re.finditer(r"D\s*<=\s*(\d+)\s*\?\s*\1\s*:\s*\(?\s*[\w>.-]*D\s*<=\s*(\d+)\s*\?\s*\2\s*:\s*\(?\s*"
-                             r"[\w>.-]*D\s*<=\s*(\d+)\s*\?\s*\3\s*:\s*(\d+)", _read(name)):
-            out.append(tuple(int(g) for g in m.groups()))
-    return out
+LADDER = (r"D\s*<=\s*(\d+)\s*\?\s*\1\s*:\s*\(?\s*[\w>.-]*D\s*<=\s*(\d+)\s*\?\s*\2\s*:\s*\(?\s*"
+          r"[\w>.-]*D\s*<=\s*(\d+)\s*\?\s*\3\s*:\s*(\d+)")
+
+
+def _ladders(names):
+    """every padded-width ladder `D <= a ? a : (D <= b ? b : (... : z))` of these sources, as (a, b, ..., z)"""
+    return [tuple(int(g) for g in m.groups()) for name in names for m in re.finditer(LADDER, _read(name))]
 
 
 def test_thresholds_mirrored():
@@ -37,9 +36,15 @@ def test_thresholds_mirrored():
     assert W.SR_LIN_FUSED_MAX_D == _define(common, "SR_LIN_FUSED_MAX_D")
     assert W.SR_GRAD_MAX_D == _define(_read("sr_predict_grad.hip"), "SR_GRAD_MAX_D")
     assert max(W.DT_LADDER) == _define(common, "SR_MAX_D")
-    ladders = _ladders()
-    assert len(ladders) >= 3, "padded-width ladders not found in the dispatch code"
-    assert set(ladders) == {W.DT_LADDER}, ladders
+    # the padded width is defined once (sr_width_bucket in sr_dispatch.h); the second-order route takes it from there in three
+    # places (accumulator count, final kernel, streamed linearize) and picks its kernels from the same list
+    assert _ladders(["sr_dispatch.h"]) == [W.DT_LADDER]
+    assert "sr_width_bucket" in re.search(r"[^\n]*D <= 3 \?[^\n]*", _read("sr_dispatch.h")).group(0)
+    users = ("sr_capi_posterior.hip", "sr_linearize.hip")
+    assert _ladders(users) == [], "hand-written padded-width ladder beside sr_width_bucket"
+    assert sum(len(re.findall(r"\bsr_width_bucket\(", _read(n))) for n in users) >= 3, "padded width not taken from sr_width_bucket"
+    picks = [tuple(int(w) for w in m.group(1).split(",")) for m in re.finditer(r"sr_pick_le<([\d, ]+)>", _read("sr_linearize.hip"))]
+    assert len(picks) >= 2 and set(picks) == {W.DT_LADDER}, picks
     # K0 (the one-launch pass) and its second-order form
     m = re.search(r"sr_gp_small_wanted\(.*?\{(.*?)\n\}", common, re.S)
     assert m and re.search(r"D\s*<=\s*%d\s*;" % W.K0_MAX_D, m.group(1)), "K0 width limit moved"
