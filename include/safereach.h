@@ -93,9 +93,10 @@ int sr_gp_factorize(sr_gp_t h, void* stream, int* info);
  * not above Np eps k_max counts as non-positive); SR_EHIP no workspace.  Synchronises the stream. */
 int sr_gp_fit_sparse(sr_gp_t h, const double* X, const double* Y, long N, double jitter, void* stream, int* info);
 /* 1 after sr_gp_fit_sparse, 0 otherwise (sr_gp_factorize clears the mark), < 0 on error.  On a sparse handle sr_gp_append,
- * sr_gp_append1_host, sr_gp_mll, sr_gp_logdet and sr_gp_logdet_cached return SR_ESTATE (Wt is not the factor of K_y);
- * sr_gp_inv_k gives P P^T; export / import, predictions, reachability and the server work unchanged.  The exported state
- * does not carry the mark (the packed format is unchanged): the receiver of a sparse model must not append. */
+ * sr_gp_append1_host, sr_gp_remove, sr_gp_loo, sr_gp_mll, sr_gp_logdet and sr_gp_logdet_cached return SR_ESTATE (Wt is not the
+ * factor of K_y); sr_gp_inv_k gives P P^T; export / import, predictions, reachability and the server work unchanged.  The
+ * exported state does not carry the mark (the packed format is unchanged): the receiver of a sparse model must not append
+ * or remove. */
 int sr_gp_is_sparse(sr_gp_t h);
 
 /* Condition on m <= 128 ADDITIONAL training points (same hyper-parameters) without refactorising: block row append of
@@ -114,6 +115,30 @@ int sr_gp_append(sr_gp_t h, const double* Znew, const double* Ynew, int m, void*
  * Beyond 512 padded rows, while Np stays, the point is appended IN PLACE (the model's buffers become views one step further
  * into their allocations; calls that rewrite the model, and big batches after an odd number of steps, copy it back first). */
 int sr_gp_append1_host(sr_gp_t h, const double* x_host, const double* y_host, void* stream, int* info);
+
+/* Retire m training points (idx_host: m distinct indices into the CURRENT rows, any order, host memory) without
+ * refactorising: O(N^2) per point.  The mirror image of the row append: per point ONE bandwidth-bound pass over U^-1 (the
+ * product of the Givens rotations that delete a column of the factor of K_y^-1, in closed form), no matrix cores.
+ * replaces: update_model(x, y, replace_old=True) on the remaining rows  ssm_gpy/gaussian_process.py:347-419 (the reference
+ * can only refit).
+ * The points go one at a time, in descending index order.  Afterwards N is m smaller (Np shrinks when N passes a multiple
+ * of 128 downward) and sr_gp_padded_n, sr_gp_dims, export, export_packed, inv_k and logdet are those of a handle fitted on
+ * the remaining rows in their old order; the same call on the same state gives the same bits.  The new factor is written
+ * into the spare buffers of the small appends, so nothing big is allocated while Np stays; scratch (3 Np + 4 doubles per
+ * output + N D) is owned by the handle and freed by sr_gp_release_scratch.
+ * SR_EINVAL NULL, m < 1, m >= N (at least one point stays), an index outside [0, N) or given twice -- all checked on the
+ * host before anything is launched; SR_ESTATE not factorized, a sparse handle, between sr_gp_import_begin and
+ * sr_gp_import_end; SR_EHIP no scratch.  On these errors the model is unchanged; a device error in the middle of several
+ * removals leaves the points retired so far retired (sr_gp_dims tells).
+ * The resident server is taken off the device first and stays armed.  The host copy of log det is invalidated
+ * (sr_gp_logdet_cached: SR_ESTATE until the next small append; sr_gp_logdet computes it).  Synchronises the stream. */
+int sr_gp_remove(sr_gp_t h, const int* idx_host, int m, void* stream);
+
+/* Leave-one-out posterior of the training rows (Rasmussen & Williams 5.12) from the rows of U^-1, without the explicit
+ * inverse: mu_loo, var_loo n_out x N (device; either may be NULL).  var_loo[d][j] = 1 / (K_y^-1)_jj includes the noise term
+ * (the predictive variance of the OBSERVATION y_j given the other rows), mu_loo[d][j] = y_j - alpha_j / (K_y^-1)_jj.
+ * Factorized, non-sparse handles (SR_ESTATE otherwise).  Asynchronous on `stream`. */
+int sr_gp_loo(sr_gp_t h, double* mu_loo, double* var_loo, void* stream);
 
 /* padded leading dimension Np (multiple of 128) of the factor matrices.  The Np - N padding rows and
  * columns are at the FRONT (identity block): training point i has padded index i + (Np - N). */

@@ -49,6 +49,8 @@ SIGNATURES = {
     "sr_gp_is_sparse": (_I, [_H]),
     "sr_gp_append": (_I, [_H, _P, _P, _I, _P, _PI]),
     "sr_gp_append1_host": (_I, [_H, _P, _P, _P, _PI]),
+    "sr_gp_remove": (_I, [_H, _PI, _I, _P]),
+    "sr_gp_loo": (_I, [_H, _P, _P, _P]),
     "sr_gp_padded_n": (_I, [_H, _PL]),
     "sr_gp_dims": (_I, [_H, _PI, _PI, _PI, _PL]),
     "sr_gp_export": (_I, [_H, _P, _P, _P]),

@@ -228,13 +228,14 @@ void srh::drop_np_sized(sr_gp* h) {
     // grad_v, grad_part, hess_part: checked against their capacity on every use
     // sel_L, sel_ws: sized by the candidate pool, checked against their capacity on every use
     // mm_ws: sized by the queries of a chunk and N, checked against its capacity on every use
+    // rm_ws: sized by Np and N, checked against its capacity on every use
 }
 
-// what sr_gp_release_scratch gives back: the big scratch of the update, the appends, the gradient / Hessian passes and the
-// selection, and the spare model buffers of the appends
+// what sr_gp_release_scratch gives back: the big scratch of the update, the appends, the removals, the gradient / Hessian passes
+// and the selection, and the spare model buffers of the appends
 static void release_big(sr_gp* h) {
     h->fact_ws.drop(); h->app_ws.drop();
-    h->grad_v.drop(); h->grad_part.drop(); h->hess_part.drop(); h->sel_L.drop(); h->sel_ws.drop(); h->mm_ws.drop();
+    h->grad_v.drop(); h->grad_part.drop(); h->hess_part.drop(); h->sel_L.drop(); h->sel_ws.drop(); h->mm_ws.drop(); h->rm_ws.drop();
     drop_wt_alt(h);
     dev_free(h->yT_alt); dev_free(h->alpha_alt); h->yT_alt = h->alpha_alt = nullptr; h->vec_alt_np = 0;
 }

@@ -476,6 +476,20 @@ int sr_launch_append1_small(const double* Wt0, const double* alpha0, const doubl
 int sr_launch_append_small(const double* U12t, const double* Wt0, int Np0, int m, int stage, double* G,
                            const double* invS, double* Xt, double* Y2, hipStream_t s, int nbatch = 1);
 
+// retire one training point / leave-one-out posterior (sr_remove.hip).  coef: n_out x sr_remove_coef_stride(Np) doubles
+// [w | a | b | rho^2 ..]; zstash: room for the (N - 1 - j) D input values behind the retired row
+static inline SR_HOST_DEVICE long sr_remove_coef_stride(int Np) { return 3L * Np + 4; }
+int sr_launch_remove_rownorm(const double* Wt, int Np, int q, int n_out, double* coef, const double* Z, double* zstash, long zcount,
+                             long zfrom, hipStream_t s);
+int sr_launch_remove_compact(const double* yT0, int Np0, int N0, int q, double* yT1, double* alpha1, int Np1, int n_out,
+                             const double* zstash, double* Z, long zcount, long zto, hipStream_t s);
+int sr_launch_remove_rows(const double* Wt0, int Np0, int N0, int q, const double* alpha0, const double* coef, double* Wt1, int Np1,
+                          double* alpha1, int n_out, hipStream_t s);
+int sr_launch_remove_clean(double* Wt, double* alpha, double* yT, int Np, int n_out, int slide, long wt_slack, long vec_slack,
+                           hipStream_t s);
+int sr_launch_loo(const double* Wt, const double* alpha, const double* yT, int N, int Np, int n_out, double* mu_loo, double* var_loo,
+                  hipStream_t s);
+
 struct sr_final_args {
     const double* mu_part; const double* jac_part; const double* var_part; const double* sf2;
     const double* ls; const double* kxx;    // kxx != NULL: per-query prior variance instead of sf2

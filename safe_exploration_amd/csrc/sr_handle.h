@@ -4,6 +4,7 @@
 //                          switches, per-kernel timing
 //   sr_capi_update.hip     model update: Gram -> blocked Cholesky -> U^-1 -> alpha (sr_gp_factorize) and its diagnostics
 //   sr_capi_append.hip     block row append (sr_gp_append)
+//   sr_capi_remove.hip     retiring training points (sr_gp_remove), leave-one-out posterior (sr_gp_loo)
 //   sr_capi_posterior.hip  workspace, dispatch of the posterior pass (sr_gp_predict, sr_gp_linearize, sr_gp_call1),
 //                          input transform, completion mailbox
 //   sr_capi_reach.hip      reachability / moment / sampling entry points and the persistent-chain dispatch
@@ -132,6 +133,8 @@ struct sr_gp {
     // sr_gp_moment_match: per query of a chunk the D x D algebra of every output and pair of outputs, and the row tiles'
     // partial sums of the double sum (sr_mm_ws_per_query doubles each)
     srh::scratch<double> mm_ws;
+    // sr_gp_remove: per output the coefficient tables of the retired row (3 Np + 4), then the input rows behind it
+    srh::scratch<double> rm_ws;
     // log det(K + noise) per output as of the last <= 16-row append (read back with its status words): the blocking read of
     // sr_gp_logdet costs the exploration loop 30 us per step
     std::vector<double> logdet_host; int logdet_valid = 0;

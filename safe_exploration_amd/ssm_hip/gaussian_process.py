@@ -586,18 +586,46 @@ class SimpleGPModel(StateSpaceModel):
         self._mll_handle = None
         return self.hyp
 
-    def update_model(self, x, y, opt_hyp=False, replace_old=True, noise_diag=1e-5, choose_data=True):
-        """ssm_gpy/gaussian_process.py:347-419."""
+    RETIRE_RULES = ("oldest", "redundant")   # update_model(n_max=..., retire=...)
+
+    def update_model(self, x, y, opt_hyp=False, replace_old=True, noise_diag=1e-5, choose_data=True, n_max=None,
+                     retire="oldest"):
+        """ssm_gpy/gaussian_process.py:347-419.
+
+        ``n_max`` (extension; None = the reference's behaviour): with ``replace_old=False`` the model keeps at most ``n_max``
+        training rows -- after the new rows are in, rows are retired (``remove_data``: O(N^2) each, no refit) until
+        N <= n_max.  ``retire="oldest"`` retires row 0 (a sliding window); ``"redundant"`` retires the row whose removal
+        changes the posterior mean least, the first argmin over j of sum_d alpha_dj^2 var_loo[d, j] (the Csato-Opper score
+        summed over the outputs).  Where the call refits instead of appending, the same rows are dropped on the host first
+        (a sparse model, ``m`` or a fixed ``Z``: always the oldest ones -- the score is that of the exact model)."""
+        if retire not in self.RETIRE_RULES:
+            raise ValueError("retire must be one of {}, not {!r}".format(self.RETIRE_RULES, retire))
+        if n_max is not None and (int(n_max) != n_max or int(n_max) < 1):
+            raise ValueError("n_max must be a positive integer or None")
         x = np.asarray(x, dtype=np.float64)
         y = np.asarray(y, dtype=np.float64)
         if (not self.do_sparse_gp and not replace_old and not opt_hyp and self.gp_trained and self._handle is not None
                 and not self._handle.shared and self.m is None and self.x_train is not None and not self.z_fixed
                 and noise_diag == self._noise_diag and 0 < x.shape[0] <= self._append_limit_now()):
             self._append(x, y)                       # O(N^2 m) block row append instead of O(N^3)
+            while n_max is not None and self._handle.N > int(n_max):
+                self.remove_data(0 if retire == "oldest" else self._most_redundant())
             return
         if not replace_old and self.x_train is not None:
             x = np.vstack((self.x_train, x))
             y = np.vstack((self.y_train, y))
+            if n_max is not None and x.shape[0] > int(n_max):
+                # the refit route drops the same rows on the host: the oldest ones, or, one at a time, the most redundant
+                # row of an exact fit of what is left (as the append route scores them)
+                if retire == "oldest" or self.do_sparse_gp or self.m is not None or self.z_fixed:
+                    x, y = x[x.shape[0] - int(n_max):], y[y.shape[0] - int(n_max):]
+                else:
+                    self.train(x, y, None, opt_hyp=False, noise_diag=noise_diag, choose_data=choose_data)
+                    while self._handle.N > int(n_max):
+                        self.remove_data(self._most_redundant())
+                    if not opt_hyp:
+                        return
+                    x, y = self.x_train, self.y_train
         m = self.m
         if m is None and self.do_sparse_gp:
             m = getattr(self, "_m_sparse", None)         # a sparse model keeps its size: refit over the grown / replaced data
@@ -664,6 +692,86 @@ class SimpleGPModel(StateSpaceModel):
             self._beta = None
             self._inv_K = None
             self._inv_K_dev = None
+
+    def _check_remove_idx(self, idx):
+        """idx (int or sequence of ints) -> sorted unique array of row indices; ValueError before the device is touched."""
+        if self.x_train is None or not self.gp_trained:
+            raise ValueError("remove_data: the model holds no training data")
+        arr = np.atleast_1d(np.asarray(idx))
+        if arr.ndim != 1 or arr.size == 0 or arr.dtype.kind not in "iu":
+            raise ValueError("remove_data: idx must be an int or a non-empty sequence of ints")
+        n = int(self.x_train.shape[0])
+        arr = arr.astype(np.int64)
+        if arr.min() < 0 or arr.max() >= n:
+            raise ValueError("remove_data: index outside [0, {})".format(n))
+        if np.unique(arr).size != arr.size:
+            raise ValueError("remove_data: an index is given twice")
+        if arr.size >= n:
+            raise ValueError("remove_data: at least one training row must stay")
+        return np.sort(arr)
+
+    def remove_data(self, idx):
+        """Retire training rows ``idx`` (an int or a sequence of distinct indices into the current ``x_train``) without
+        refitting: ``sr_gp_remove``, O(N^2) per row.  The model is then the one a fit on the remaining rows, in their old
+        order, gives.  Where the row append would not apply either (sparse model, handle shared with a deep copy, ``m`` set,
+        fixed ``Z``) the remaining rows are refitted instead."""
+        arr = self._check_remove_idx(idx)
+        keep = np.ones(self.x_train.shape[0], dtype=bool)
+        keep[arr] = False
+        hd = self._handle
+        if (self.do_sparse_gp or hd is None or hd.shared or self.m is not None or self.z_fixed
+                or self.x_train.shape[0] != hd.N):
+            m = self.m
+            if m is None and self.do_sparse_gp:
+                m = getattr(self, "_m_sparse", None)
+            if m is not None:
+                m = min(int(m), int(keep.sum()))
+            self.train(self.x_train[keep], self.y_train[keep], m, opt_hyp=False,
+                       noise_diag=self._noise_diag if self._noise_diag is not None else 1e-5, Z=self.Z)
+            return
+        cidx = (ctypes.c_int * arr.size)(*[int(i) for i in arr])
+        check(lib.sr_gp_remove(hd.h, cidx, int(arr.size), B.stream_ptr(hd.device)))
+        hd.N -= int(arr.size)
+        hd.Np = hd.Np_now()
+        self.x_train, self.y_train = self._shrunk(keep)
+        self.z = self.x_train
+        self._z_fit, self._y_z = self.x_train, self.y_train
+        self._beta = None
+        self._inv_K = None
+        self._inv_K_dev = None
+
+    def _shrunk(self, keep):
+        """x_train[keep], y_train[keep] -- compacted inside the buffers of ``_grown`` where the training set lives there (the
+        next append then finds its room as before)"""
+        x0, y0 = self.x_train, self.y_train
+        bufs = getattr(self, "_train_bufs", None)
+        xk, yk = x0[keep], y0[keep]
+        if (bufs is not None and x0.base is bufs[0] and y0.base is bufs[1]
+                and x0.ctypes.data == bufs[0].ctypes.data and y0.ctypes.data == bufs[1].ctypes.data):
+            n1 = xk.shape[0]
+            bufs[0][:n1], bufs[1][:n1] = xk, yk
+            return bufs[0][:n1], bufs[1][:n1]
+        return xk, yk
+
+    def loo_device(self):
+        """Leave-one-out posterior of the training rows as device tensors (mu_loo, var_loo), each (N, n_s_out):
+        ``sr_gp_loo``.  var_loo includes the noise term (the predictive variance of the observation).  Asynchronous."""
+        self._need_trained()
+        hd = self._handle
+        mu, var = B.empty((hd.n_out, hd.N), hd.device), B.empty((hd.n_out, hd.N), hd.device)
+        check(lib.sr_gp_loo(hd.h, B.ptr(mu), B.ptr(var), B.stream_ptr(hd.device)))
+        return mu.T, var.T
+
+    def loo(self):
+        """``loo_device`` as NumPy arrays (mu_loo, var_loo), each (N, n_s_out)."""
+        mu, var = self.loo_device()
+        return np.ascontiguousarray(B.to_numpy(mu)), np.ascontiguousarray(B.to_numpy(var))
+
+    def _most_redundant(self):
+        """first argmin over j of sum_d alpha_dj^2 var_loo[d, j]: the squared change of the posterior mean at x_j, in units
+        of the prior, that retiring row j causes (Csato & Opper's score), summed over the outputs"""
+        _, var = self.loo()
+        return int(np.argmin((self.beta ** 2 * var).sum(axis=1)))
 
     def _grown(self, x0, xs, y0, ys):
         """[x0; xs], [y0; ys] as views of buffers with room to grow (a vstack per appended point copies the whole
