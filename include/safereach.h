@@ -49,7 +49,10 @@ typedef struct sr_gp* sr_gp_t;
 #define SR_K_SMALL     8   /* one-launch posterior of a small model (Np <= 512, T <= 1024)  */
 #define SR_K_SPARSE_PANEL 9  /* sr_gp_fit_sparse: cross-covariance panel K_fu of a chunk (+ its share of K_uf y) */
 #define SR_K_SPARSE_GEMM  10 /* sr_gp_fit_sparse: streamed G += K_fu^T K_fu on the fp64 MFMA tile                 */
-#define SR_K_COUNT     11
+#define SR_K_PATHS_DRAW   11 /* sr_gp_paths_draw: feature slab, residual, the two triangular products              */
+#define SR_K_PATHS_EVAL   12 /* sr_gp_paths_eval: feature slab of the chunk + the two-range MFMA tile (K* pass: SR_K_KSTAR) */
+#define SR_K_PATHS_STEP   13 /* sr_gp_paths_step: split pass + ordered sum                                         */
+#define SR_K_COUNT     14
 
 int         sr_version(void);
 const char* sr_last_error(void);
@@ -339,6 +342,43 @@ int sr_gp_logdet_cached(sr_gp_t h, double* logdet_host /* n_out, host */);
 int sr_gp_sample(int device, long T, int size, int n_out, int n_u, const double* mu, const double* var,
                  const double* eps, double* S, const double* k_fb, const double* k_ff, double* z_next,
                  void* stream);
+
+/* ---- posterior FUNCTION samples: pathwise conditioning (Matheron's rule on a random-Fourier-feature prior) ----------
+ * S whole posterior functions of an ARD-RBF model that can be evaluated anywhere, consistently, in O(N + M) per value:
+ * per output d and path s, with l_d, sf2_d the kernel's parameters and n_d the diagonal term as sr_gp_set_data received it,
+ *   phi_d(x)_i = sqrt(2 sf2_d / M) cos(sum_j omega[i][j] x_j / l_d[j] + tau[i])                         i < M
+ *   c_{d,s}    = K_y,d^-1 (y_d - Phi_d(Z) w_{d,s} - sqrt(n_d) eps_{d,s}) = U^-1 (U^-T r_{d,s})            (N)
+ *   f_{d,s}(x) = phi_d(x) . w_{d,s} + k_d(x, Z) c_{d,s}
+ * The reference has no counterpart: it draws marginal samples only (sample_from_gp  ssm_gpy/gaussian_process.py:598-619,
+ * used by sampling_models.py:66-80), so a particle of its Monte-Carlo rollout meets an unrelated function at every step.
+ * The caller supplies all randomness (device memory), as sr_gp_sample takes eps; the device code is deterministic and the
+ * same inputs give the same bits: omega M x D standard normal, tau M uniform in [0, 2 pi) (both shared by all outputs and
+ * paths), w n_out x S x M and eps n_out x S x N standard normal.  With w = 0, eps = 0 every path is the posterior mean.
+ *
+ * sr_gp_paths_draw builds w and c in the k-major layout of the MFMA tile (n_out x Mp x Sp and n_out x Np x Sp, Mp = M to 16,
+ * Sp = S to 128; padding exactly zero) and keeps them, omega and tau with the handle (a grow-only block; SR_EHIP if it cannot
+ * be had).  S == 0 drops the paths (the pointers may be NULL).  Asynchronous on `stream`.
+ * sr_gp_paths_count: S and M of the valid paths, 0, 0 when the handle holds none.
+ * sr_gp_paths_eval: every path at every query, Xq T x D -> F T x S x n_out (the layout of sr_gp_sample's output), in chunks
+ * of sr_gp_set_chunk queries.  T == 0 is a no-op.  Asynchronous on `stream`.
+ * sr_gp_paths_step: path s at its OWN input Xs[s] (S x D) -> F S x n_out; with k_fb (n_u x n_out) and k_ff (n_u) non-NULL
+ * z_next (S x D) receives the closed-loop next inputs [F[s], k_fb F[s] + k_ff] as sr_gp_sample's z_next does; that form needs
+ * D = n_out + n_u with n_u >= 1, otherwise SR_EINVAL.  Asynchronous on `stream`.
+ * The paths belong to the model they were drawn from: everything that rewrites the model (sr_gp_set_data*, sr_gp_factorize,
+ * sr_gp_fit_sparse, sr_gp_append, sr_gp_append1_host, sr_gp_remove, sr_gp_import*) invalidates them -- _eval and _step then
+ * return SR_ESTATE and _count gives 0, 0 until the next _draw.  sr_gp_release_scratch frees the workspaces of the three
+ * calls, not the paths.
+ * All errors are found on the host before any launch, and invalid arguments leave paths drawn earlier intact: SR_EINVAL NULL
+ * where not allowed, S < 0, M < 1 or M > 1048560 with S > 0, T < 0; SR_ESTATE not factorized, a sparse handle (Wt is not the factor of K_y),
+ * between sr_gp_import_begin and sr_gp_import_end, no valid paths; SR_EUNSUPPORTED a general-family model (the feature map
+ * is the Gaussian spectral density: mat52 / lin_* are out of scope) or D > 8, as the other batched entry points.
+ * Out of scope: the Jacobian of the paths, replication of paths to other ranks, general kernels. */
+int sr_gp_paths_draw(sr_gp_t h, int S, int M, const double* omega, const double* tau, const double* w, const double* eps,
+                     void* stream);
+int sr_gp_paths_count(sr_gp_t h, int* S, int* M);
+int sr_gp_paths_eval(sr_gp_t h, const double* Xq, long T, double* F, void* stream);
+int sr_gp_paths_step(sr_gp_t h, const double* Xs, double* F, const double* k_fb, const double* k_ff, double* z_next,
+                     void* stream);
 
 /* ---- tuning / measurement -------------------------------------------------------------------- */
 /* max queries processed per internal pass (workspace = n_out * Np * chunk * 8 B); default 65536. */

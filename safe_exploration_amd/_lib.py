@@ -15,6 +15,7 @@ from ._build import LIB_PATH
 
 SR_OK, SR_EINVAL, SR_EHIP, SR_ENOTPD, SR_ESTATE, SR_EUNSUPPORTED, SR_EBUSY = 0, -1, -2, -3, -4, -5, -6
 K_GRAM, K_POTRF, K_GEMM, K_KSTAR, K_VAR, K_FINAL, K_ELL, K_TRINV, K_SMALL, K_SPARSE_PANEL, K_SPARSE_GEMM = range(11)
+K_PATHS_DRAW, K_PATHS_EVAL, K_PATHS_STEP = 11, 12, 13
 KERNEL_NAMES = {K_GRAM: "sr_gram_kernel", K_POTRF: "sr_potrf_diag_kernel", K_GEMM: "sr_gemm_tn_kernel",
                 K_KSTAR: "sr_kstar_kernel", K_VAR: "sr_var_kernel", K_FINAL: "sr_finalize_kernel",
                 K_ELL: "sr_ellipsoid_kernel"}
@@ -81,6 +82,10 @@ SIGNATURES = {
     "sr_gp_logdet": (_I, [_H, _P, _P]),
     "sr_gp_logdet_cached": (_I, [_H, _P]),
     "sr_gp_sample": (_I, [_I, _L, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "sr_gp_paths_draw": (_I, [_H, _I, _I, _P, _P, _P, _P, _P]),
+    "sr_gp_paths_count": (_I, [_H, _PI, _PI]),
+    "sr_gp_paths_eval": (_I, [_H, _P, _L, _P, _P]),
+    "sr_gp_paths_step": (_I, [_H, _P, _P, _P, _P, _P, _P]),
     "sr_gp_set_chunk": (_I, [_H, _L]),
     "sr_gp_set_var_group": (_I, [_H, _I]),
     "sr_gp_set_var_variant": (_I, [_H, _I]),

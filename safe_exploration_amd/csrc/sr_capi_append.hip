@@ -411,6 +411,7 @@ extern "C" int sr_gp_append1_host(sr_gp_t h, const double* x_host, const double*
         return SR_EUNSUPPORTED;
     }
     SR_TRY(server_quiesce(h));
+    model_rewritten(h);                   // (every route below, the in-place one included, writes the model)
     return append_small(h, nullptr, nullptr, 1, (hipStream_t)stream, info, x_host, y_host);
 }
 
@@ -422,6 +423,7 @@ extern "C" int sr_gp_append(sr_gp_t h, const double* Znew, const double* Ynew, i
     hipStream_t s = (hipStream_t)stream;
     SR_DEVICE(h->device);
     SR_TRY(server_quiesce(h));            // (it stays armed: the next single query launches it on the grown model)
+    model_rewritten(h);                   // (every route below, the in-place one included, writes the model)
     if (m <= SR_SMALL_T) return append_small(h, Znew, Ynew, m, s, info);
     SR_TRY(unslide(h));
     // 17 .. 128 new points: the same algebra on the MFMA tile (64 x 64 workgroup tiles: the products are 128 columns wide).

@@ -229,12 +229,14 @@ void srh::drop_np_sized(sr_gp* h) {
     // sel_L, sel_ws: sized by the candidate pool, checked against their capacity on every use
     // mm_ws: sized by the queries of a chunk and N, checked against its capacity on every use
     // rm_ws: sized by Np and N, checked against its capacity on every use
+    // paths: valid for one model generation only (sr_gp::model_gen), sized again by the next draw; paths_ws: checked against
+    // its capacity on every use
 }
 
 // what sr_gp_release_scratch gives back: the big scratch of the update, the appends, the removals, the gradient / Hessian passes
-// and the selection, and the spare model buffers of the appends
+// and the selection, the workspace of the path calls (not the paths), and the spare model buffers of the appends
 static void release_big(sr_gp* h) {
-    h->fact_ws.drop(); h->app_ws.drop();
+    h->fact_ws.drop(); h->app_ws.drop(); h->paths_ws.drop();
     h->grad_v.drop(); h->grad_part.drop(); h->hess_part.drop(); h->sel_L.drop(); h->sel_ws.drop(); h->mm_ws.drop(); h->rm_ws.drop();
     drop_wt_alt(h);
     dev_free(h->yT_alt); dev_free(h->alpha_alt); h->yT_alt = h->alpha_alt = nullptr; h->vec_alt_np = 0;
@@ -247,7 +249,7 @@ extern "C" int sr_gp_destroy(sr_gp_t h) {
     (void)device_sync();
     drop_np_sized(h);
     release_big(h);
-    h->stream_slots.drop(); h->stream_tab.drop(); h->tz_x.drop(); h->tz_jac.drop();
+    h->stream_slots.drop(); h->stream_tab.drop(); h->tz_x.drop(); h->tz_jac.drop(); h->paths.drop();
     dev_free(h->Z); dev_free(yT_alloc_of(h)); dev_free(h->ls); dev_free(h->sf2); dev_free(h->noise);
     dev_free(alpha_alloc_of(h)); dev_free(wt_alloc_of(h)); dev_free(h->kp); dev_free(h->Tz);
     dev_free(h->chain_xch); dev_free(h->chain_tickets); dev_free(h->chain_done); dev_free(h->call_ticket);
@@ -278,6 +280,7 @@ extern "C" int sr_gp_set_data(sr_gp_t h, const double* Z, const double* Y, const
     SR_DEVICE(h->device);
     SR_TRY(server_quiesce(h));            // the resident server reads the model: off the device before it changes
     SR_TRY(unslide(h));
+    model_rewritten(h);
     SR_HIP(hipMemcpyAsync(h->Z, Z, sizeof(double) * h->N * h->D, hipMemcpyDeviceToDevice, s));
     SR_HIP(hipMemcpyAsync(h->ls, ls, sizeof(double) * h->n_out * h->D, hipMemcpyDeviceToDevice, s));
     SR_HIP(hipMemcpyAsync(h->sf2, sf2, sizeof(double) * h->n_out, hipMemcpyDeviceToDevice, s));
@@ -299,6 +302,7 @@ extern "C" int sr_gp_set_data_general(sr_gp_t h, const double* Z, const double* 
     SR_DEVICE(h->device);
     SR_TRY(server_quiesce(h));
     SR_TRY(unslide(h));
+    model_rewritten(h);
     if (!h->kp) SR_TRY(dev_alloc(&h->kp, (size_t)h->n_out * SR_KP(h->D)));
     SR_HIP(hipMemcpyAsync(h->Z, Z, sizeof(double) * h->N * h->D, hipMemcpyDeviceToDevice, s));
     SR_HIP(hipMemcpyAsync(h->kp, kparams, sizeof(double) * h->n_out * SR_KP(h->D), hipMemcpyDeviceToDevice, s));
@@ -397,6 +401,7 @@ extern "C" int sr_gp_import(sr_gp_t h, const double* alpha, const double* Wt, vo
     SR_TRY(server_quiesce(h));
     SR_TRY(unslide(h));
     SR_TRY(ensure_wt(h));
+    model_rewritten(h);
     SR_HIP(hipMemsetAsync(h->alpha, 0, sizeof(double) * h->n_out * h->Np, s));
     SR_HIP(hipMemcpy2DAsync(h->alpha + (h->Np - h->N), sizeof(double) * h->Np, alpha,
                             sizeof(double) * h->N, sizeof(double) * h->N, h->n_out,
@@ -459,6 +464,7 @@ extern "C" int sr_gp_import_begin(sr_gp_t h, const double* alpha, void* stream) 
     SR_TRY(server_quiesce(h));
     SR_TRY(unslide(h));
     SR_TRY(ensure_wt(h));             // zero below the diagonal from allocation on; nothing ever writes there
+    model_rewritten(h);
     h->factorized = 0; h->logdet_valid = 0; h->sparse = 0;
     h->import_open = 1;
     SR_HIP(hipMemsetAsync(h->alpha, 0, sizeof(double) * h->n_out * h->Np, s));
@@ -476,6 +482,7 @@ extern "C" int sr_gp_import_packed(sr_gp_t h, int d, long row0, long row1, const
              "sr_gp_import_packed: d=%d rows [%ld, %ld) outside the model (n_out=%d, N=%d)", d, row0, row1, h->n_out, h->N);
     if (row1 == row0) return SR_OK;
     SR_DEVICE(h->device);
+    model_rewritten(h);
     const int gy = std::max(1, std::min(8, (h->N - (int)row0 + 2047) / 2048));
     hipLaunchKernelGGL(sr_pack_rows_kernel<false>, dim3((unsigned)(row1 - row0), gy), dim3(256), 0, (hipStream_t)stream,
                        h->Wt + (size_t)d * h->Np * h->Np, const_cast<double*>(buf), h->N, h->Np, row0);
@@ -487,6 +494,7 @@ extern "C" int sr_gp_import_end(sr_gp_t h) {
     SR_CHECK(h != nullptr, SR_EINVAL, "sr_gp_import_end: NULL handle");
     SR_CHECK(h->import_open, SR_ESTATE, "sr_gp_import_end: no import in progress");
     h->import_open = 0;
+    model_rewritten(h);
     h->factorized = 1; h->logdet_valid = 0; h->sparse = 0;
     return SR_OK;
 }

@@ -1,0 +1,151 @@
+// sr_capi_paths.hip -- posterior function samples by pathwise conditioning: sr_gp_paths_draw / _count / _eval / _step.
+// The algebra: include/safereach.h; the kernels: sr_paths.hip.  Host-side orchestration only.
+#include "sr_handle.h"
+using namespace srh;
+
+namespace {
+
+// the handle's block of drawn paths: [omega M x D | tau M | w n_out x Mp x Sp | c n_out x Np x Sp], every part 16-byte aligned
+struct paths_layout {
+    int S, M, Sp, Mp; size_t o_tau, o_w, o_c, total;
+    paths_layout(const sr_gp* h, int S_, int M_) : S(S_), M(M_) {
+        Sp = (int)round_up(S, srt::BN); Mp = (int)round_up(M, srt::BK);
+        o_tau = (size_t)round_up((long)M * h->D, 2);
+        o_w = o_tau + (size_t)round_up(M, 2);
+        o_c = o_w + (size_t)h->n_out * Mp * Sp;
+        total = o_c + (size_t)h->n_out * h->Np * Sp;
+    }
+};
+
+bool paths_valid(const sr_gp* h) { return h->paths_S > 0 && h->paths_gen == h->model_gen && h->paths_Np == h->Np && h->paths.get(); }
+
+sr_paths_feat feat_args(const sr_gp* h, const paths_layout& L) {
+    sr_paths_feat m;
+    m.ls = h->ls; m.sf2 = h->sf2; m.omega = h->paths.get(); m.tau = h->paths.get() + L.o_tau;
+    m.D = h->D; m.n_out = h->n_out; m.M = L.M; m.Mp = L.Mp;
+    return m;
+}
+
+// what all three calls ask of the model (after their own arguments, before the question whether paths exist)
+int model_checks(const sr_gp* h, const char* who) {
+    SR_CHECK(h->factorized && !h->import_open, SR_ESTATE, "%s: model not factorized%s", who,
+             h->import_open ? " (between sr_gp_import_begin and sr_gp_import_end)" : "");
+    SR_CHECK(!h->sparse, SR_ESTATE, "%s: sparse model (U^-1 is not the factor of K_y)", who);
+    SR_CHECK(!h->general, SR_EUNSUPPORTED, "%s: general kernel family (the feature map is that of the ARD-RBF kernel)", who);
+    SR_CHECK(h->D <= SR_PATHS_MAX_D, SR_EUNSUPPORTED, "%s: D=%d > %d", who, h->D, SR_PATHS_MAX_D);
+    return SR_OK;
+}
+
+}  // namespace
+
+extern "C" int sr_gp_paths_count(sr_gp_t h, int* S, int* M) {
+    SR_CHECK(h != nullptr, SR_EINVAL, "sr_gp_paths_count: NULL handle");
+    const bool ok = paths_valid(h);
+    if (S) *S = ok ? h->paths_S : 0;
+    if (M) *M = ok ? h->paths_M : 0;
+    return SR_OK;
+}
+
+extern "C" int sr_gp_paths_draw(sr_gp_t h, int S, int M, const double* omega, const double* tau, const double* w,
+                                const double* eps, void* stream) {
+    SR_CHECK(h != nullptr, SR_EINVAL, "sr_gp_paths_draw: NULL handle");
+    SR_CHECK(S >= 0, SR_EINVAL, "sr_gp_paths_draw: S=%d", S);
+    if (S == 0) {                                        // drop the paths
+        SR_DEVICE(h->device);
+        h->paths_S = h->paths_M = 0;
+        // the block goes back to the block cache: an _eval or _step still in flight on any stream must have finished with it
+        if (h->paths.get()) SR_HIP(device_sync());
+        h->paths.drop();
+        return SR_OK;
+    }
+    // (the feature slab takes 16 features per workgroup along grid.y)
+    SR_CHECK(M >= 1 && M <= 65535 * SR_PATHS_FROWS, SR_EINVAL, "sr_gp_paths_draw: M=%d outside 1..%d", M, 65535 * SR_PATHS_FROWS);
+    SR_CHECK(omega && tau && w && eps, SR_EINVAL, "sr_gp_paths_draw: NULL argument");
+    SR_TRY(model_checks(h, "sr_gp_paths_draw"));
+    hipStream_t s = (hipStream_t)stream;
+    SR_DEVICE(h->device);
+    SR_TRY(tile_route_alignment(h));                     // (the two triangular products read U^-1 in 16-byte pieces)
+    const int N = h->N, Np = h->Np, off = Np - N, n_out = h->n_out;
+    const paths_layout L(h, S, M);
+    // workspace first: if it cannot be had, the paths drawn earlier stay
+    const size_t n_phi = (size_t)n_out * L.Mp * Np, n_rs = (size_t)n_out * Np * L.Sp;
+    SR_TRY(h->paths_ws.grow(n_phi + 2 * n_rs, wait::device()));
+    h->paths_S = h->paths_M = 0;                         // from here on the old paths are gone
+    SR_TRY(h->paths.grow(L.total, wait::device()));
+    double *P = h->paths.get(), *Wk = P + L.o_w, *C = P + L.o_c;
+    double *Phi = h->paths_ws.get(), *R = Phi + n_phi, *V = R + n_rs;
+    sr_prof_scope ps(&h->prof, SR_K_PATHS_DRAW, s);
+    SR_HIP(hipMemcpyAsync(P, omega, sizeof(double) * M * h->D, hipMemcpyDeviceToDevice, s));
+    SR_HIP(hipMemcpyAsync(P + L.o_tau, tau, sizeof(double) * M, hipMemcpyDeviceToDevice, s));
+    SR_TRY(sr_launch_paths_pack(w, Wk, nullptr, nullptr, M, 0, L.Mp, S, L.Sp, n_out, s));
+    const sr_paths_feat fm = feat_args(h, L);
+    SR_TRY(sr_launch_paths_features(fm, h->Z, h->D, N, off, Np, Phi, s));
+    // the prior at the training rows, P = Phi(Z)^T w (Np x Sp per output), then R = y - P - sqrt(n_d) eps^T in its place
+    sr_batch bp; bp.n = n_out; bp.sA = (long)L.Mp * Np; bp.sB = (long)L.Mp * L.Sp; bp.sC = (long)Np * L.Sp;
+    SR_TRY(sr_launch_gemm_tn(Phi, Np, Wk, L.Sp, R, L.Sp, Np, L.Sp, L.Mp, 1.0, 0.0, 0, s, 0, &bp));
+    SR_TRY(sr_launch_paths_pack(eps, R, h->yT, h->noise, N, off, Np, S, L.Sp, n_out, s));
+    // V = U^-T R: U^-1 is upper triangular, the k range of a row block of V ends with the block (mode 3); C = U^-1 V
+    sr_batch bv; bv.n = n_out; bv.sA = (long)Np * Np; bv.sB = (long)Np * L.Sp; bv.sC = (long)Np * L.Sp;
+    SR_TRY(sr_launch_gemm_tn(h->Wt, Np, R, L.Sp, V, L.Sp, Np, L.Sp, Np, 1.0, 0.0, 3, s, 0, &bv));
+    SR_TRY(sr_launch_paths_solve(h->Wt, V, C, N, Np, L.Sp, n_out, s));
+    h->paths_S = S; h->paths_M = M; h->paths_Np = Np; h->paths_gen = h->model_gen;
+    return SR_OK;
+}
+
+extern "C" int sr_gp_paths_eval(sr_gp_t h, const double* Xq, long T, double* F, void* stream) {
+    SR_CHECK(h != nullptr, SR_EINVAL, "sr_gp_paths_eval: NULL handle");
+    SR_CHECK(T >= 0, SR_EINVAL, "sr_gp_paths_eval: T=%ld", T);
+    SR_CHECK(T == 0 || (Xq && F), SR_EINVAL, "sr_gp_paths_eval: NULL argument");
+    SR_TRY(model_checks(h, "sr_gp_paths_eval"));
+    SR_CHECK(paths_valid(h), SR_ESTATE, "sr_gp_paths_eval: no valid paths (sr_gp_paths_draw after the last model update)");
+    if (T == 0) return SR_OK;
+    hipStream_t s = (hipStream_t)stream;
+    SR_DEVICE(h->device);
+    const paths_layout L(h, h->paths_S, h->paths_M);
+    const double *P = h->paths.get(), *Wk = P + L.o_w, *C = P + L.o_c;
+    const sr_paths_feat fm = feat_args(h, L);
+    for (long t0 = 0; t0 < T; t0 += h->chunk) {
+        const long Tc = std::min(h->chunk, T - t0);
+        const long Tp = round_up(Tc, srt::BN);
+        const int nsplit = pick_nsplit(h, Tp);
+        SR_TRY(ensure_ws(h, Tp, nsplit));
+        SR_TRY(h->paths_ws.grow((size_t)h->n_out * L.Mp * Tp, wait::device()));
+        const double* Xc = Xq + t0 * h->D;
+        sr_kstar_args ka = kstar_ws(h, nsplit, Tc, Tp);
+        ka.xa = Xc; ka.lda = h->D; ka.na = h->D;
+        {
+            sr_prof_scope ps(&h->prof, SR_K_KSTAR, s);
+            SR_TRY(sr_launch_kstar(ka, s));
+        }
+        sr_prof_scope ps(&h->prof, SR_K_PATHS_EVAL, s);
+        SR_TRY(sr_launch_paths_features(fm, Xc, h->D, Tc, 0, Tp, h->paths_ws.get(), s));
+        SR_TRY(sr_launch_paths_eval(h->paths_ws.get(), Wk, h->Ks, C, F + t0 * L.S * h->n_out, h->N, h->Np, L.Mp, Tc, Tp, L.S, L.Sp,
+                                    h->n_out, s));
+    }
+    return SR_OK;
+}
+
+extern "C" int sr_gp_paths_step(sr_gp_t h, const double* Xs, double* F, const double* k_fb, const double* k_ff,
+                                double* z_next, void* stream) {
+    SR_CHECK(h != nullptr, SR_EINVAL, "sr_gp_paths_step: NULL handle");
+    SR_CHECK(Xs && F, SR_EINVAL, "sr_gp_paths_step: NULL argument");
+    SR_CHECK((k_fb != nullptr) == (k_ff != nullptr) && (z_next != nullptr) == (k_fb != nullptr), SR_EINVAL,
+             "sr_gp_paths_step: k_fb, k_ff and z_next come together");
+    SR_CHECK(!k_fb || h->D > h->n_out, SR_EINVAL, "sr_gp_paths_step: the closed loop needs D = n_out + n_u (D=%d, n_out=%d)", h->D,
+             h->n_out);
+    SR_TRY(model_checks(h, "sr_gp_paths_step"));
+    SR_CHECK(paths_valid(h), SR_ESTATE, "sr_gp_paths_step: no valid paths (sr_gp_paths_draw after the last model update)");
+    hipStream_t s = (hipStream_t)stream;
+    SR_DEVICE(h->device);
+    const paths_layout L(h, h->paths_S, h->paths_M);
+    sr_paths_step_args a;
+    a.m = feat_args(h, L);
+    a.Z = h->Z; a.Wk = h->paths.get() + L.o_w; a.C = h->paths.get() + L.o_c; a.Xs = Xs;
+    a.F = F; a.k_fb = k_fb; a.k_ff = k_ff; a.z_next = z_next; a.n_u = k_fb ? h->D - h->n_out : 0;
+    a.N = h->N; a.Np = h->Np; a.S = L.S; a.Sp = L.Sp;
+    a.nsplit = sr_hess_nsplit(h->N + L.M, h->n_out, L.S);     // (the split rule of the Hessian pass over the N + M terms)
+    SR_TRY(h->paths_ws.grow((size_t)a.nsplit * h->n_out * L.Sp, wait::device()));
+    a.part = h->paths_ws.get();
+    sr_prof_scope ps(&h->prof, SR_K_PATHS_STEP, s);
+    return sr_launch_paths_step(a, s);
+}

@@ -112,6 +112,7 @@ extern "C" int sr_gp_remove(sr_gp_t h, const int* idx_host, int m, void* stream)
     hipStream_t s = (hipStream_t)stream;
     SR_DEVICE(h->device);
     SR_TRY(server_quiesce(h));            // (it stays armed: the next single query launches it on the shrunken model)
+    model_rewritten(h);
     // the scratch of every removal of this call up front (the first one is the biggest): none of them can run out of it
     SR_TRY(h->rm_ws.grow((size_t)h->n_out * sr_remove_coef_stride(h->Np) + (size_t)h->N * h->D, wait::device()));
     for (int k = 0; k < m; ++k) SR_TRY(remove_one(h, idx[k], s));

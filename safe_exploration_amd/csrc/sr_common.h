@@ -356,6 +356,13 @@ int sr_launch_var_bal(const double* Wt, const double* Ks, double* Vt, double* pa
 //                                            blocks; a trailing update SR_FACT_FREE_RATIO (2) times longer than the next chain takes
 //                                            the whole chip: N = 50000 66.8 -> 67.2 TF, r04_timeline50000); early inversion from
 //                                            nb >= 8; GEMM tile: sr_use_tile64* (sr_gemm.hip)
+//  posterior function samples               draw: the prior at the training rows and V = U^-T R through sr_launch_gemm_tn (its own tile
+//   (sr_capi_paths.hip, sr_paths.hip)        choice: sr_use_tile64), C = U^-1 V on the NT loop of the gradient pass, all outputs per launch;
+//                                            eval: 128 x 128 tiles, grid Sp / 128 x Tp / 128 x n_out, feature slab in strips of
+//                                            SR_PATHS_FROWS (16) features x 256 columns; step: one lane per path, the N + M terms
+//                                            split by sr_hess_nsplit(N + M, n_out, S) (SR_HESS_WGS workgroups, SR_HESS_MIN_ROWS terms
+//                                            at least), partial sums added in ascending order.  Sizes taken from the Hessian pass and
+//                                            the variance tile, not swept (profiles/r12_paths.txt holds the times they give)
 //  row append (sr_capi_append.hip)           one launch for +1 point with Np <= 512 (SR_APPEND1_MAX_NP0, r03_exploration_step), <= 16
 //                                            points matrix-vector shaped, 17 .. 128 on the MFMA tile (r03_append_bench); the Python layer
 //                                            appends up to N / 5 points and refactorises beyond (break-even r03_growing_model)
@@ -489,6 +496,34 @@ int sr_launch_remove_clean(double* Wt, double* alpha, double* yT, int Np, int n_
                            hipStream_t s);
 int sr_launch_loo(const double* Wt, const double* alpha, const double* yT, int N, int Np, int n_out, double* mu_loo, double* var_loo,
                   hipStream_t s);
+
+// ---- posterior function samples by pathwise conditioning (sr_paths.hip; the algebra: include/safereach.h) -------------------
+#define SR_PATHS_MAX_D 8             /* input widths the feature and step kernels are compiled for (3 / 5 / 8), as the gradient pass */
+#define SR_PATHS_FROWS 16            /* features per workgroup of the feature slab (one k-tile of the MFMA loop); not swept */
+struct sr_paths_feat {
+    const double* ls; const double* sf2; const double* omega; const double* tau;   // n_out x D, n_out, M x D, M
+    int D, n_out, M, Mp;
+};
+// Phi[d][i][c] = sqrt(2 sf2_d / M) cos(omega_i . (x_t / l_d) + tau_i), t = c - col0, for i < M and 0 <= t < T; zero elsewhere
+// (i < Mp, c < ncols): a k-major operand of the MFMA tile, n_out x Mp x ncols
+int sr_launch_paths_features(const sr_paths_feat& m, const double* X, long ldx, long T, long col0, long ncols, double* Phi,
+                             hipStream_t s);
+// path-major draws src (n_out x S x n) -> k-major dst (n_out x Rp x Sp) rows off .. off + n, the rest zero.  yT == NULL:
+// dst = src^T; else dst = yT - dst - sqrt(noise_d) src^T on the real rows and columns (dst holds the prior on entry; Rp = Np)
+int sr_launch_paths_pack(const double* src, double* dst, const double* yT, const double* noise, int n, int off, int Rp, int S,
+                         int Sp, int n_out, hipStream_t s);
+// C = U^-1 V (n_out x Np x Sp, rows of the front padding exactly zero) on srt::mainloop_nt_glds
+int sr_launch_paths_solve(const double* Wt, const double* V, double* C, int N, int Np, int Sp, int n_out, hipStream_t s);
+// F[t][s][d] = sum_{k < Mp} Phi[d][k][t] Wk[d][k][s] + sum_{k >= front padding} Ks[d][k][t] C[d][k][s], t < T, s < S
+int sr_launch_paths_eval(const double* Phi, const double* Wk, const double* Ks, const double* C, double* F, int N, int Np,
+                         int Mp, long T, long Tp, int S, int Sp, int n_out, hipStream_t s);
+struct sr_paths_step_args {
+    sr_paths_feat m; const double* Z; const double* Wk; const double* C; const double* Xs;
+    double* part;                     // nsplit x n_out x Sp
+    double* F; const double* k_fb; const double* k_ff; double* z_next; int n_u;
+    int N, Np, S, Sp, nsplit;
+};
+int sr_launch_paths_step(const sr_paths_step_args& a, hipStream_t s);
 
 struct sr_final_args {
     const double* mu_part; const double* jac_part; const double* var_part; const double* sf2;

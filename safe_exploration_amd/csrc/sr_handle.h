@@ -9,6 +9,7 @@
 //                          input transform, completion mailbox
 //   sr_capi_reach.hip      reachability / moment / sampling entry points and the persistent-chain dispatch
 //   sr_capi_server.hip     resident single-query server: start / stop / blocking call
+//   sr_capi_paths.hip      posterior function samples by pathwise conditioning (sr_gp_paths_draw / _count / _eval / _step)
 #pragma once
 #include "sr_mfma_tile.h"
 #include <atomic>
@@ -109,6 +110,9 @@ struct sr_gp {
     int have_data = 0, factorized = 0;
     int sparse = 0;          // the posterior is that of sr_gp_fit_sparse: Wt Wt^T = K_uu^-1 - Sigma^-1, not K_y^-1
     int import_open = 0;     // between sr_gp_import_begin and sr_gp_import_end
+    // Model generation: bumped (srh::model_rewritten) by every entry point that rewrites Z, the hyper-parameters, yT, alpha or
+    // U^-1.  State derived from the model remembers the generation it was made from (the paths below).
+    unsigned long long model_gen = 1;
     // per-chunk workspace (ensure_ws / free_ws: one group, two capacities)
     long chunk = 65536, ws_Tp = 0, ws_part = 0;     // ws_part: capacity of mu_part in units of n_out doubles
     int ws_locked = 0;       // internal buffers (mu / var / jac) are referenced by an entry point: growing now is a bug
@@ -135,6 +139,11 @@ struct sr_gp {
     srh::scratch<double> mm_ws;
     // sr_gp_remove: per output the coefficient tables of the retired row (3 Np + 4), then the input rows behind it
     srh::scratch<double> rm_ws;
+    // sr_gp_paths_*: the drawn paths [omega M x D | tau M | w n_out x Mp x Sp | c n_out x Np x Sp] (k-major operands of the MFMA
+    // tile), valid while paths_gen == model_gen; and the workspace of the three calls (draw: Phi(Z), R, V; eval: Phi of a chunk;
+    // step: the splits' partial sums), which sr_gp_release_scratch gives back
+    srh::scratch<double> paths, paths_ws;
+    int paths_S = 0, paths_M = 0, paths_Np = 0; unsigned long long paths_gen = 0;
     // log det(K + noise) per output as of the last <= 16-row append (read back with its status words): the blocking read of
     // sr_gp_logdet costs the exploration loop 30 us per step
     std::vector<double> logdet_host; int logdet_valid = 0;
@@ -246,6 +255,7 @@ static inline size_t vec_doubles(int n_out, int Np) { return (size_t)n_out * Np 
 static inline double* wt_alloc_of(const sr_gp* h) { return h->Wt ? h->Wt - (size_t)h->slide * (h->Np + 1) : nullptr; }
 static inline double* alpha_alloc_of(const sr_gp* h) { return h->alpha ? h->alpha - h->slide : nullptr; }
 static inline double* yT_alloc_of(const sr_gp* h) { return h->yT ? h->yT - h->slide : nullptr; }
+static inline void model_rewritten(sr_gp* h) { ++h->model_gen; }     // (see sr_gp::model_gen)
 int unslide(sr_gp* h);               // back to plain buffers (fresh allocations, two contiguous copies); no-op when slide == 0
 
 // The chain of launches of sr_gp_factorize on the caller's matrices (sr_capi_update.hip; the sparse fit, sr_sparse.hip):

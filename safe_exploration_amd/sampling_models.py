@@ -18,11 +18,15 @@ class MonteCarloSafetyVerification(object):
         self.n_s = getattr(GP, "n_s", None) or GP.n_s_out    # the reference reads GP.n_s (:30); SimpleGPModel has n_s_out
         self.n_u = GP.n_u
 
-    def sample_n_step(self, x0, K, k, n=1, n_samples=1000, eps=None, generator=None, as_tensor=False):
+    def sample_n_step(self, x0, K, k, n=1, n_samples=1000, eps=None, generator=None, as_tensor=False, consistent=False,
+                      n_features=1024):
         """Sample from the n-step-ahead distribution of the closed loop u_i = K[i] x_i + k[i].
 
         x0 (n_s, 1) deterministic start; K (n, n_u, n_s); k (n, n_u)  (sampling_models.py:33-80).
         eps (n, n_samples, n_s): optional standard-normal draws (default: the device generator).
+        consistent=True: every particle is rolled through ITS OWN posterior function (SimpleGPModel.draw_paths: pathwise
+        conditioning on n_features random features) instead of meeting an unrelated marginal draw at every step; the
+        model's valid paths are used if there are n_samples of them, otherwise they are drawn here (eps is not read).
         Returns S (n_samples, n_s) and S_all (n, n_samples, n_s)."""
         n_s, n_u = self.n_s, self.n_u
         assert n > 0, "The time horizon n for the multi-step sampling must be positive!"
@@ -35,6 +39,20 @@ class MonteCarloSafetyVerification(object):
         inp = np.vstack((x0, u0)).T
         dev = self.GP.device
         S_all = B.empty((n, n_samples, n_s), dev)
+        if consistent:
+            if self.GP.paths_count()[0] != n_samples:
+                self.GP.draw_paths(n_samples, n_features, generator)
+            inp = B.as_dev(inp, dev, (1, n_s + n_u)).expand(n_samples, n_s + n_u).contiguous()
+            for i in range(n):
+                if i + 1 < n:
+                    S, inp = self.GP.paths_step_device(inp, K[i + 1], k[i + 1])
+                else:
+                    S = self.GP.paths_step_device(inp)
+                S_all[i].copy_(S)
+            if as_tensor:
+                return S_all[n - 1], S_all
+            out = B.to_numpy(S_all)
+            return out[n - 1].squeeze(), out
         for i in range(n):
             e = None
             if eps is not None:

@@ -1412,6 +1412,86 @@ class SimpleGPModel(StateSpaceModel):
         S = self.sample_device(inp, size, eps, generator)
         return S if B.is_tensor(inp) else B.to_numpy(S)
 
+    # ------------------------------------------------------------------ posterior function samples (pathwise conditioning)
+    def draw_paths(self, size, n_features=1024, generator=None, omega=None, tau=None, w=None, eps=None):
+        """Draw `size` whole posterior FUNCTIONS (Matheron's rule on n_features random Fourier features of the ARD-RBF
+        kernel; include/safereach.h) and keep them with the model until its next update.  The reference has no
+        counterpart: sample_from_gp draws marginal samples only.  The draws -- omega (M, D) and w (n_s_out, size, M) and
+        eps (n_s_out, size, N) standard normal, tau (M,) uniform in [0, 2 pi) -- come from torch's device generator where
+        not supplied."""
+        self._need_trained()
+        hd = self._handle
+        S, M = int(size), int(n_features)
+        if S < 1 or M < 1:
+            raise ValueError("draw_paths: size and n_features must be positive (got {}, {})".format(size, n_features))
+        dev, n_out, N = hd.device, hd.n_out, hd.N
+
+        def draw(given, shape, uniform=False):
+            if given is not None:
+                return B.as_dev(given, dev, shape)
+            if uniform:
+                return torch.rand(shape, dtype=torch.float64, device=dev, generator=generator) * (2.0 * np.pi)
+            return torch.randn(shape, dtype=torch.float64, device=dev, generator=generator)
+
+        t_om, t_tau = draw(omega, (M, hd.D)), draw(tau, (M,), uniform=True)
+        t_w, t_eps = draw(w, (n_out, S, M)), draw(eps, (n_out, S, N))
+        check(lib.sr_gp_paths_draw(hd.h, S, M, B.ptr(t_om), B.ptr(t_tau), B.ptr(t_w), B.ptr(t_eps), B.stream_ptr(dev)))
+
+    def drop_paths(self):
+        """Give the memory of the drawn paths back."""
+        self._need_trained()
+        check(lib.sr_gp_paths_draw(self._handle.h, 0, 0, None, None, None, None, B.stream_ptr(self._handle.device)))
+
+    def _need_paths(self):
+        S, _ = self.paths_count()
+        if S == 0:
+            raise RuntimeError("SimpleGPModel: no valid paths (call draw_paths() after the last model update)")
+        return S
+
+    def paths_count(self):
+        """(size, n_features) of the valid paths; (0, 0) when there are none (never drawn, or the model changed since)."""
+        self._need_trained()
+        S, M = ctypes.c_int(0), ctypes.c_int(0)
+        check(lib.sr_gp_paths_count(self._handle.h, ctypes.byref(S), ctypes.byref(M)))
+        return S.value, M.value
+
+    def sample_paths_device(self, x):
+        """Every drawn path at every input: x (n, D) -> (n, size, n_s_out), the shape of sample_from_gp; the values of one
+        path at several inputs are those of ONE function."""
+        self._need_trained()
+        hd = self._handle
+        x = B.as_dev(x, hd.device)
+        if x.dim() != 2 or x.shape[1] != hd.D:
+            raise ValueError("x must be (n, {})".format(hd.D))
+        S = self._need_paths()
+        F = B.empty((x.shape[0], S, hd.n_out), hd.device)
+        check(lib.sr_gp_paths_eval(hd.h, B.ptr(x), x.shape[0], B.ptr(F), B.stream_ptr(hd.device)))
+        return F
+
+    def sample_paths(self, x):
+        """sample_paths_device, NumPy in / NumPy out (a tensor in: a tensor out)."""
+        F = self.sample_paths_device(x)
+        return F if B.is_tensor(x) else B.to_numpy(F)
+
+    def paths_step_device(self, x_s, k_fb=None, k_ff=None):
+        """Path s at its OWN input: x_s (size, D) -> F (size, n_s_out).  With k_fb (n_u, n_s_out) and k_ff (n_u,) the
+        closed-loop next inputs [F, k_fb F + k_ff] (size, D) are returned as well, as sample_device returns them."""
+        self._need_trained()
+        hd = self._handle
+        S = self._need_paths()
+        x = B.as_dev(x_s, hd.device, (S, hd.D))
+        F = B.empty((S, hd.n_out), hd.device)
+        z = tk = tf = None
+        if k_fb is not None:
+            n_u = hd.D - hd.n_out
+            if n_u < 1:
+                raise ValueError("next inputs need D = n_s_out + n_u")
+            tk = B.as_dev(k_fb, hd.device, (n_u, hd.n_out))
+            tf = B.as_dev(k_ff, hd.device, (n_u,))
+            z = B.empty((S, hd.D), hd.device)
+        check(lib.sr_gp_paths_step(hd.h, B.ptr(x), B.ptr(F), B.ptr(tk), B.ptr(tf), B.ptr(z), B.stream_ptr(hd.device)))
+        return F if z is None else (F, z)
+
     def information_gain(self, x=None):
         """Mutual information between the training samples and the system  gaussian_process.py:621-634:
         per output log det(I + K/sigma_n^2) = log det(K + sigma_n^2 I) - N log sigma_n^2, sigma_n^2 being the
