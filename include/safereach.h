@@ -50,8 +50,8 @@ typedef struct sr_gp* sr_gp_t;
 #define SR_K_SPARSE_PANEL 9  /* sr_gp_fit_sparse: cross-covariance panel K_fu of a chunk (+ its share of K_uf y) */
 #define SR_K_SPARSE_GEMM  10 /* sr_gp_fit_sparse: streamed G += K_fu^T K_fu on the fp64 MFMA tile                 */
 #define SR_K_PATHS_DRAW   11 /* sr_gp_paths_draw: feature slab, residual, the two triangular products              */
-#define SR_K_PATHS_EVAL   12 /* sr_gp_paths_eval: feature slab of the chunk + the two-range MFMA tile (K* pass: SR_K_KSTAR) */
-#define SR_K_PATHS_STEP   13 /* sr_gp_paths_step: split pass + ordered sum                                         */
+#define SR_K_PATHS_EVAL   12 /* sr_gp_paths_eval[_grad]: feature (and derivative) slabs of the chunk + the two-range MFMA tile (K* pass: SR_K_KSTAR) */
+#define SR_K_PATHS_STEP   13 /* sr_gp_paths_step[_grad]: split pass + ordered sum                                  */
 #define SR_K_COUNT     14
 
 int         sr_version(void);
@@ -372,13 +372,24 @@ int sr_gp_sample(int device, long T, int size, int n_out, int n_u, const double*
  * where not allowed, S < 0, M < 1 or M > 1048560 with S > 0, T < 0; SR_ESTATE not factorized, a sparse handle (Wt is not the factor of K_y),
  * between sr_gp_import_begin and sr_gp_import_end, no valid paths; SR_EUNSUPPORTED a general-family model (the feature map
  * is the Gaussian spectral density: mat52 / lin_* are out of scope) or D > 8, as the other batched entry points.
- * Out of scope: the Jacobian of the paths, replication of paths to other ranks, general kernels. */
+ * sr_gp_paths_eval_grad / _step_grad: the same calls with the Jacobian of every value in the input,
+ *   d f_{d,s}(x) / d x_j = -sqrt(2 sf2_d / M) / l_d[j] sum_i sin(omega_i . x / l_d + tau_i) omega[i][j] w_{d,s,i}
+ *                          + sf2_d / l_d[j]^2 sum_i exp(-r_i^2 / 2) (z_ij - x_j) c_{d,s,i}
+ * over the w and c the draw keeps (nothing is drawn or solved): J T x S x n_out x D resp. S x n_out x D.  F is bit for bit F
+ * of _eval / _step on the same inputs (_eval_grad: F may be NULL); k_fb, k_ff, z_next, the chunks, T == 0, the errors (J NULL:
+ * SR_EINVAL), the states and the invalidation are theirs.  Deterministic, no atomics.  Workspace (grow-only, freed by
+ * sr_gp_release_scratch): _eval_grad one more feature slab and one K*-sized slab per chunk, n_out (2 Mp + Np) Tp doubles in
+ * all; _step_grad 1 + D times the partial sums of _step.
+ * Out of scope: Hessians of the paths, replication of paths to other ranks, general kernels. */
 int sr_gp_paths_draw(sr_gp_t h, int S, int M, const double* omega, const double* tau, const double* w, const double* eps,
                      void* stream);
 int sr_gp_paths_count(sr_gp_t h, int* S, int* M);
 int sr_gp_paths_eval(sr_gp_t h, const double* Xq, long T, double* F, void* stream);
 int sr_gp_paths_step(sr_gp_t h, const double* Xs, double* F, const double* k_fb, const double* k_ff, double* z_next,
                      void* stream);
+int sr_gp_paths_eval_grad(sr_gp_t h, const double* Xq, long T, double* F, double* J, void* stream);
+int sr_gp_paths_step_grad(sr_gp_t h, const double* Xs, double* F, double* J, const double* k_fb, const double* k_ff,
+                          double* z_next, void* stream);
 
 /* ---- tuning / measurement -------------------------------------------------------------------- */
 /* max queries processed per internal pass (workspace = n_out * Np * chunk * 8 B); default 65536. */

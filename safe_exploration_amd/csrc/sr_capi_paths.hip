@@ -1,4 +1,5 @@
-// sr_capi_paths.hip -- posterior function samples by pathwise conditioning: sr_gp_paths_draw / _count / _eval / _step.
+// sr_capi_paths.hip -- posterior function samples by pathwise conditioning: sr_gp_paths_draw / _count / _eval / _step and
+// their Jacobians sr_gp_paths_eval_grad / _step_grad (the same plans with J: one body each).
 // The algebra: include/safereach.h; the kernels: sr_paths.hip.  Host-side orchestration only.
 #include "sr_handle.h"
 using namespace srh;
@@ -92,12 +93,18 @@ extern "C" int sr_gp_paths_draw(sr_gp_t h, int S, int M, const double* omega, co
     return SR_OK;
 }
 
-extern "C" int sr_gp_paths_eval(sr_gp_t h, const double* Xq, long T, double* F, void* stream) {
-    SR_CHECK(h != nullptr, SR_EINVAL, "sr_gp_paths_eval: NULL handle");
-    SR_CHECK(T >= 0, SR_EINVAL, "sr_gp_paths_eval: T=%ld", T);
-    SR_CHECK(T == 0 || (Xq && F), SR_EINVAL, "sr_gp_paths_eval: NULL argument");
-    SR_TRY(model_checks(h, "sr_gp_paths_eval"));
-    SR_CHECK(paths_valid(h), SR_ESTATE, "sr_gp_paths_eval: no valid paths (sr_gp_paths_draw after the last model update)");
+namespace {
+
+// _eval (grad == false: F required, J unused) and _eval_grad (J required, F optional).  Per chunk: K*, the feature slab and the
+// two-range tile for F; then per input dimension j the derivative slabs of both ranges (behind the feature slab in paths_ws:
+// one more feature-sized and one K*-sized slab, reused by every j) and the same tile into column j of J.
+int paths_eval(sr_gp_t h, const double* Xq, long T, double* F, double* J, bool grad, void* stream, const char* who) {
+    SR_CHECK(h != nullptr, SR_EINVAL, "%s: NULL handle", who);
+    SR_CHECK(T >= 0, SR_EINVAL, "%s: T=%ld", who, T);
+    SR_CHECK(grad ? J != nullptr : true, SR_EINVAL, "%s: NULL J", who);
+    SR_CHECK(T == 0 || (Xq && (F || grad)), SR_EINVAL, "%s: NULL argument", who);
+    SR_TRY(model_checks(h, who));
+    SR_CHECK(paths_valid(h), SR_ESTATE, "%s: no valid paths (sr_gp_paths_draw after the last model update)", who);
     if (T == 0) return SR_OK;
     hipStream_t s = (hipStream_t)stream;
     SR_DEVICE(h->device);
@@ -109,7 +116,8 @@ extern "C" int sr_gp_paths_eval(sr_gp_t h, const double* Xq, long T, double* F, 
         const long Tp = round_up(Tc, srt::BN);
         const int nsplit = pick_nsplit(h, Tp);
         SR_TRY(ensure_ws(h, Tp, nsplit));
-        SR_TRY(h->paths_ws.grow((size_t)h->n_out * L.Mp * Tp, wait::device()));
+        const size_t n_phi = (size_t)h->n_out * L.Mp * Tp, n_ks = (size_t)h->n_out * h->Np * Tp;
+        SR_TRY(h->paths_ws.grow(grad ? 2 * n_phi + n_ks : n_phi, wait::device()));
         const double* Xc = Xq + t0 * h->D;
         sr_kstar_args ka = kstar_ws(h, nsplit, Tc, Tp);
         ka.xa = Xc; ka.lda = h->D; ka.na = h->D;
@@ -118,34 +126,69 @@ extern "C" int sr_gp_paths_eval(sr_gp_t h, const double* Xq, long T, double* F, 
             SR_TRY(sr_launch_kstar(ka, s));
         }
         sr_prof_scope ps(&h->prof, SR_K_PATHS_EVAL, s);
-        SR_TRY(sr_launch_paths_features(fm, Xc, h->D, Tc, 0, Tp, h->paths_ws.get(), s));
-        SR_TRY(sr_launch_paths_eval(h->paths_ws.get(), Wk, h->Ks, C, F + t0 * L.S * h->n_out, h->N, h->Np, L.Mp, Tc, Tp, L.S, L.Sp,
-                                    h->n_out, s));
+        if (F) {
+            SR_TRY(sr_launch_paths_features(fm, Xc, h->D, Tc, 0, Tp, h->paths_ws.get(), s));
+            SR_TRY(sr_launch_paths_eval(h->paths_ws.get(), Wk, h->Ks, C, F + t0 * L.S * h->n_out, h->N, h->Np, L.Mp, Tc, Tp, L.S,
+                                        L.Sp, h->n_out, s));
+        }
+        if (!grad) continue;
+        double *dPhi = h->paths_ws.get() + n_phi, *dKs = dPhi + n_phi;
+        for (int j = 0; j < h->D; ++j) {
+            SR_TRY(sr_launch_paths_features(fm, Xc, h->D, Tc, 0, Tp, dPhi, s, j));
+            SR_TRY(sr_launch_paths_dkstar(h->Ks, dKs, h->Z, Xc, h->ls, h->N, h->Np, h->D, h->n_out, Tc, Tp, j, s));
+            SR_TRY(sr_launch_paths_eval(dPhi, Wk, dKs, C, J + t0 * L.S * h->n_out * h->D + j, h->N, h->Np, L.Mp, Tc, Tp, L.S, L.Sp,
+                                        h->n_out, s, h->n_out * h->D, h->D));
+        }
     }
     return SR_OK;
 }
 
-extern "C" int sr_gp_paths_step(sr_gp_t h, const double* Xs, double* F, const double* k_fb, const double* k_ff,
-                                double* z_next, void* stream) {
-    SR_CHECK(h != nullptr, SR_EINVAL, "sr_gp_paths_step: NULL handle");
-    SR_CHECK(Xs && F, SR_EINVAL, "sr_gp_paths_step: NULL argument");
+}  // namespace
+
+extern "C" int sr_gp_paths_eval(sr_gp_t h, const double* Xq, long T, double* F, void* stream) {
+    return paths_eval(h, Xq, T, F, nullptr, false, stream, "sr_gp_paths_eval");
+}
+
+extern "C" int sr_gp_paths_eval_grad(sr_gp_t h, const double* Xq, long T, double* F, double* J, void* stream) {
+    return paths_eval(h, Xq, T, F, J, true, stream, "sr_gp_paths_eval_grad");
+}
+
+namespace {
+
+// _step (grad == false) and _step_grad (J required): the same split count, 1 + D rows of partial sums per split with J
+int paths_step(sr_gp_t h, const double* Xs, double* F, double* J, bool grad, const double* k_fb, const double* k_ff,
+               double* z_next, void* stream, const char* who) {
+    SR_CHECK(h != nullptr, SR_EINVAL, "%s: NULL handle", who);
+    SR_CHECK(Xs && F && (J || !grad), SR_EINVAL, "%s: NULL argument", who);
     SR_CHECK((k_fb != nullptr) == (k_ff != nullptr) && (z_next != nullptr) == (k_fb != nullptr), SR_EINVAL,
-             "sr_gp_paths_step: k_fb, k_ff and z_next come together");
-    SR_CHECK(!k_fb || h->D > h->n_out, SR_EINVAL, "sr_gp_paths_step: the closed loop needs D = n_out + n_u (D=%d, n_out=%d)", h->D,
+             "%s: k_fb, k_ff and z_next come together", who);
+    SR_CHECK(!k_fb || h->D > h->n_out, SR_EINVAL, "%s: the closed loop needs D = n_out + n_u (D=%d, n_out=%d)", who, h->D,
              h->n_out);
-    SR_TRY(model_checks(h, "sr_gp_paths_step"));
-    SR_CHECK(paths_valid(h), SR_ESTATE, "sr_gp_paths_step: no valid paths (sr_gp_paths_draw after the last model update)");
+    SR_TRY(model_checks(h, who));
+    SR_CHECK(paths_valid(h), SR_ESTATE, "%s: no valid paths (sr_gp_paths_draw after the last model update)", who);
     hipStream_t s = (hipStream_t)stream;
     SR_DEVICE(h->device);
     const paths_layout L(h, h->paths_S, h->paths_M);
     sr_paths_step_args a;
     a.m = feat_args(h, L);
     a.Z = h->Z; a.Wk = h->paths.get() + L.o_w; a.C = h->paths.get() + L.o_c; a.Xs = Xs;
-    a.F = F; a.k_fb = k_fb; a.k_ff = k_ff; a.z_next = z_next; a.n_u = k_fb ? h->D - h->n_out : 0;
+    a.F = F; a.J = grad ? J : nullptr; a.k_fb = k_fb; a.k_ff = k_ff; a.z_next = z_next; a.n_u = k_fb ? h->D - h->n_out : 0;
     a.N = h->N; a.Np = h->Np; a.S = L.S; a.Sp = L.Sp;
     a.nsplit = sr_hess_nsplit(h->N + L.M, h->n_out, L.S);     // (the split rule of the Hessian pass over the N + M terms)
-    SR_TRY(h->paths_ws.grow((size_t)a.nsplit * h->n_out * L.Sp, wait::device()));
+    SR_TRY(h->paths_ws.grow((size_t)a.nsplit * h->n_out * (grad ? 1 + h->D : 1) * L.Sp, wait::device()));
     a.part = h->paths_ws.get();
     sr_prof_scope ps(&h->prof, SR_K_PATHS_STEP, s);
     return sr_launch_paths_step(a, s);
+}
+
+}  // namespace
+
+extern "C" int sr_gp_paths_step(sr_gp_t h, const double* Xs, double* F, const double* k_fb, const double* k_ff,
+                                double* z_next, void* stream) {
+    return paths_step(h, Xs, F, nullptr, false, k_fb, k_ff, z_next, stream, "sr_gp_paths_step");
+}
+
+extern "C" int sr_gp_paths_step_grad(sr_gp_t h, const double* Xs, double* F, double* J, const double* k_fb, const double* k_ff,
+                                     double* z_next, void* stream) {
+    return paths_step(h, Xs, F, J, true, k_fb, k_ff, z_next, stream, "sr_gp_paths_step_grad");
 }

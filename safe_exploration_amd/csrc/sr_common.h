@@ -362,7 +362,10 @@ int sr_launch_var_bal(const double* Wt, const double* Ks, double* Vt, double* pa
 //                                            SR_PATHS_FROWS (16) features x 256 columns; step: one lane per path, the N + M terms
 //                                            split by sr_hess_nsplit(N + M, n_out, S) (SR_HESS_WGS workgroups, SR_HESS_MIN_ROWS terms
 //                                            at least), partial sums added in ascending order.  Sizes taken from the Hessian pass and
-//                                            the variance tile, not swept (profiles/r12_paths.txt holds the times they give)
+//                                            the variance tile, not swept (profiles/r12_paths.txt holds the times they give);
+//                                            Jacobians: the same tile, strips and split count (F keeps its bits), derivative slabs
+//                                            in strips of 16 rows x 256 columns, the ordered sum one thread per (path, element of
+//                                            J) (profiles/r13_paths_grad.txt)
 //  row append (sr_capi_append.hip)           one launch for +1 point with Np <= 512 (SR_APPEND1_MAX_NP0, r03_exploration_step), <= 16
 //                                            points matrix-vector shaped, 17 .. 128 on the MFMA tile (r03_append_bench); the Python layer
 //                                            appends up to N / 5 points and refactorises beyond (break-even r03_growing_model)
@@ -506,8 +509,13 @@ struct sr_paths_feat {
 };
 // Phi[d][i][c] = sqrt(2 sf2_d / M) cos(omega_i . (x_t / l_d) + tau_i), t = c - col0, for i < M and 0 <= t < T; zero elsewhere
 // (i < Mp, c < ncols): a k-major operand of the MFMA tile, n_out x Mp x ncols
+// jg >= 0: the derivative in input dimension jg in its place, -sqrt(2 sf2_d / M) sin(..) omega[i][jg] / l_d[jg]
 int sr_launch_paths_features(const sr_paths_feat& m, const double* X, long ldx, long T, long col0, long ncols, double* Phi,
-                             hipStream_t s);
+                             hipStream_t s, int jg = -1);
+// dKs[d][k][c] = Ks[d][k][c] (z_{k - (Np - N), jg} - x_{c, jg}) / l_d[jg]^2 on the real rows and the columns c < T, zero
+// elsewhere (n_out x Np x Tp, as Ks; X is T x D)
+int sr_launch_paths_dkstar(const double* Ks, double* dKs, const double* Z, const double* X, const double* ls, int N, int Np,
+                           int D, int n_out, long T, long Tp, int jg, hipStream_t s);
 // path-major draws src (n_out x S x n) -> k-major dst (n_out x Rp x Sp) rows off .. off + n, the rest zero.  yT == NULL:
 // dst = src^T; else dst = yT - dst - sqrt(noise_d) src^T on the real rows and columns (dst holds the prior on entry; Rp = Np)
 int sr_launch_paths_pack(const double* src, double* dst, const double* yT, const double* noise, int n, int off, int Rp, int S,
@@ -515,12 +523,14 @@ int sr_launch_paths_pack(const double* src, double* dst, const double* yT, const
 // C = U^-1 V (n_out x Np x Sp, rows of the front padding exactly zero) on srt::mainloop_nt_glds
 int sr_launch_paths_solve(const double* Wt, const double* V, double* C, int N, int Np, int Sp, int n_out, hipStream_t s);
 // F[t][s][d] = sum_{k < Mp} Phi[d][k][t] Wk[d][k][s] + sum_{k >= front padding} Ks[d][k][t] C[d][k][s], t < T, s < S
+// es > 0: the element goes to F[(t S + s) es + d ds] instead (a column of J: F = J + j, es = n_out D, ds = D)
 int sr_launch_paths_eval(const double* Phi, const double* Wk, const double* Ks, const double* C, double* F, int N, int Np,
-                         int Mp, long T, long Tp, int S, int Sp, int n_out, hipStream_t s);
+                         int Mp, long T, long Tp, int S, int Sp, int n_out, hipStream_t s, int es = 0, int ds = 1);
 struct sr_paths_step_args {
     sr_paths_feat m; const double* Z; const double* Wk; const double* C; const double* Xs;
-    double* part;                     // nsplit x n_out x Sp
+    double* part;                     // nsplit x n_out x Sp; with J: nsplit x n_out x (1 + D) x Sp
     double* F; const double* k_fb; const double* k_ff; double* z_next; int n_u;
+    double* J;                        // S x n_out x D, or NULL: the value alone
     int N, Np, S, Sp, nsplit;
 };
 int sr_launch_paths_step(const sr_paths_step_args& a, hipStream_t s);

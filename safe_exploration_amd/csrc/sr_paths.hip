@@ -13,6 +13,11 @@
 //                                 rows through LDS (broadcast reads), the N + M terms split over workgroups   [exp / cos bound]
 //   KPR sr_paths_step_sum_kernel: the splits in ascending order (no atomics: the same inputs give the same bits), F and the
 //                                 closed-loop next inputs
+// The Jacobian of the paths (sr_gp_paths_eval_grad / _step_grad) runs through the same kernels: KPF<GRAD> writes the
+// derivative of the feature slab in one input dimension, KPD sr_paths_dkstar_kernel that of K* (K* times the explicit
+// difference z_ij - x_tj: nothing is expanded around a centre) [HBM bound], KPE contracts them with its output base and
+// stride as arguments; KPT<GRAD> / KPR<GRAD> carry D more accumulators per range next to the value's, whose operations
+// and order they leave as they are (F of the GRAD forms is F of the plain forms, bit for bit).
 // The first product of the draw (V = U^-T R) and the prior at the training rows are plain TN products: sr_launch_gemm_tn.
 #include "sr_mfma_tile.h"
 #include "sr_kernel_dev.h"
@@ -21,9 +26,10 @@
 // KPF: SR_PATHS_FROWS features x 256 columns per workgroup; the lane's row of X (divided by the lengthscales, as the
 // formula is written) sits in registers, the omega rows of the strip in LDS.
 // ------------------------------------------------------------------------------------------------
-template <int DT>
+// GRAD: d Phi / d x_jg = -amp sin(arg) omega[i][jg] / l_d[jg] in its place.
+template <int DT, bool GRAD = false>
 __global__ __launch_bounds__(256) void sr_paths_feature_kernel(sr_paths_feat m, const double* __restrict__ X, long ldx, long T,
-                                                               long col0, long ncols, double* __restrict__ Phi) {
+                                                               long col0, long ncols, double* __restrict__ Phi, int jg) {
     __shared__ double om[SR_PATHS_FROWS * DT];
     __shared__ double ta[SR_PATHS_FROWS];
     const int d = blockIdx.z, i0 = blockIdx.y * SR_PATHS_FROWS;
@@ -41,24 +47,66 @@ __global__ __launch_bounds__(256) void sr_paths_feature_kernel(sr_paths_feat m, 
     }
     __syncthreads();
     if (c >= ncols) return;
-    const double amp = sqrt(2.0 * m.sf2[d] / (double)m.M);
+    double amp = sqrt(2.0 * m.sf2[d] / (double)m.M);
+    if (GRAD) amp = -amp / m.ls[d * m.D + jg];
     double* out = Phi + ((long)d * m.Mp + i0) * ncols + c;
 #pragma unroll 4
     for (int r = 0; r < SR_PATHS_FROWS; ++r) {
         double arg = 0.0;
 #pragma unroll
         for (int j = 0; j < DT; ++j) arg = fma(om[r * DT + j], xs[j], arg);
-        out[(long)r * ncols] = (live && i0 + r < m.M) ? amp * cos(arg + ta[r]) : 0.0;
+        if (GRAD)
+            out[(long)r * ncols] = (live && i0 + r < m.M) ? amp * sin(arg + ta[r]) * m.omega[(long)(i0 + r) * m.D + jg] : 0.0;
+        else
+            out[(long)r * ncols] = (live && i0 + r < m.M) ? amp * cos(arg + ta[r]) : 0.0;
     }
 }
 
 int sr_launch_paths_features(const sr_paths_feat& m, const double* X, long ldx, long T, long col0, long ncols, double* Phi,
-                             hipStream_t s) {
-    SR_CHECK(m.Mp % SR_PATHS_FROWS == 0 && m.Mp >= m.M && ncols > 0, SR_EINVAL, "paths_features: M=%d Mp=%d ncols=%ld", m.M, m.Mp,
-             ncols);
+                             hipStream_t s, int jg) {
+    SR_CHECK(m.Mp % SR_PATHS_FROWS == 0 && m.Mp >= m.M && ncols > 0 && jg < m.D, SR_EINVAL,
+             "paths_features: M=%d Mp=%d ncols=%ld jg=%d", m.M, m.Mp, ncols, jg);
     const dim3 grid((unsigned)((ncols + 255) / 256), m.Mp / SR_PATHS_FROWS, m.n_out);
     return sr_pick_le<3, 5, 8>("paths_features", m.D, [&](auto dt) {
-        return sr_launch(sr_paths_feature_kernel<decltype(dt)::value>, grid, dim3(256), 0, s, m, X, ldx, T, col0, ncols, Phi); });
+        constexpr int DT = decltype(dt)::value;
+        if (jg >= 0)
+            return sr_launch(sr_paths_feature_kernel<DT, true>, grid, dim3(256), 0, s, m, X, ldx, T, col0, ncols, Phi, jg);
+        return sr_launch(sr_paths_feature_kernel<DT, false>, grid, dim3(256), 0, s, m, X, ldx, T, col0, ncols, Phi, 0); });
+}
+
+// ------------------------------------------------------------------------------------------------
+// KPD: dKs[d][k][c] = Ks[d][k][c] (z_{k - off, jg} - x_{c, jg}) / l_d[jg]^2 for the real rows and the queries c < T, exactly
+// zero elsewhere (k < Np, c < Tp): one element per lane, 256 columns x 16 rows per workgroup, the rows' z through LDS.
+// ------------------------------------------------------------------------------------------------
+#define SR_PATHS_DROWS 16
+__global__ __launch_bounds__(256) void sr_paths_dkstar_kernel(const double* __restrict__ Ks, double* __restrict__ dKs,
+                                                              const double* __restrict__ Z, const double* __restrict__ X,
+                                                              const double* __restrict__ ls, int N, int Np, int D, long T,
+                                                              long Tp, int jg) {
+    __shared__ double zj[SR_PATHS_DROWS];
+    const int d = blockIdx.z, k0 = blockIdx.y * SR_PATHS_DROWS, off = Np - N;
+    const long c = (long)blockIdx.x * 256 + threadIdx.x;
+    if (threadIdx.x < SR_PATHS_DROWS) {
+        const int i = k0 + threadIdx.x - off;
+        zj[threadIdx.x] = (i >= 0 && i < N) ? Z[(long)i * D + jg] : 0.0;
+    }
+    __syncthreads();
+    if (c >= Tp) return;
+    const bool live = c < T;
+    const double l = ls[d * D + jg], il2 = 1.0 / (l * l);
+    const double xj = live ? X[c * D + jg] : 0.0;
+    const long e = ((long)d * Np + k0) * Tp + c;
+#pragma unroll 4
+    for (int r = 0; r < SR_PATHS_DROWS; ++r)
+        dKs[e + (long)r * Tp] = (live && k0 + r >= off) ? Ks[e + (long)r * Tp] * ((zj[r] - xj) * il2) : 0.0;
+}
+
+int sr_launch_paths_dkstar(const double* Ks, double* dKs, const double* Z, const double* X, const double* ls, int N, int Np,
+                           int D, int n_out, long T, long Tp, int jg, hipStream_t s) {
+    SR_CHECK(Np % SR_PATHS_DROWS == 0 && N >= 1 && N <= Np && T <= Tp && jg >= 0 && jg < D, SR_EINVAL,
+             "paths_dkstar: N=%d Np=%d T=%ld Tp=%ld jg=%d", N, Np, T, Tp, jg);
+    return sr_launch(sr_paths_dkstar_kernel, dim3((unsigned)((Tp + 255) / 256), Np / SR_PATHS_DROWS, n_out), dim3(256), 0, s, Ks,
+                     dKs, Z, X, ls, N, Np, D, T, Tp, jg);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -133,12 +181,13 @@ int sr_launch_paths_solve(const double* Wt, const double* V, double* C, int N, i
 // ------------------------------------------------------------------------------------------------
 // KPE: tile (queries t0 .., paths s0 ..) of output d.  Both ranges run through the LDS-DMA TN loop into the same
 // accumulator; path tiles are the fast grid index, so that the workgroups resident together share a tile of Phi and K*.
-// The stores of a lane are n_out doubles apart (the API's layout has the output index innermost).
+// The stores of a lane are `es` doubles apart (the API's layouts have the path index outside the output's): element (t, s)
+// of output d is out[(t S + s) es + d ds] -- es = n_out, ds = 1 for F; out = J + j, es = n_out D, ds = D for column j of J.
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256, 2) void sr_paths_eval_kernel(const double* __restrict__ Phi, const double* __restrict__ Wk,
                                                                const double* __restrict__ Ks, const double* __restrict__ C,
                                                                double* __restrict__ F, int Np, int Mp, int k_lo, long T, long Tp,
-                                                               int S, int Sp, int n_out) {
+                                                               int S, int Sp, int es, int ds) {
     __shared__ double smem[srt::SMEM_DOUBLES];
     const int d = blockIdx.z;
     const long t0 = (long)blockIdx.y * srt::BM;
@@ -156,8 +205,8 @@ __global__ __launch_bounds__(256, 2) void sr_paths_eval_kernel(const double* __r
     // (per-element addresses, computed ahead of the stores, spilled the accumulators)
     const long tl = t0 + wm * 64 + (lane >> 4);
     const int sl = s0 + wn * 64 + (lane & 15);
-    double* f0 = F + (tl * S + sl) * n_out + d;
-    const long st = (long)S * n_out;
+    double* f0 = F + (tl * S + sl) * es + d * ds;
+    const long st = (long)S * es;
 #pragma unroll
     for (int mi = 0; mi < 4; ++mi)
 #pragma unroll
@@ -166,27 +215,32 @@ __global__ __launch_bounds__(256, 2) void sr_paths_eval_kernel(const double* __r
             if (tl + mi * 16 + 4 * r >= T) continue;
 #pragma unroll
             for (int ni = 0; ni < 4; ++ni)
-                if (sl + ni * 16 < S) f0[(mi * 16 + 4 * r) * st + ni * 16 * n_out] = acc.v[mi][ni][r];
+                if (sl + ni * 16 < S) f0[(mi * 16 + 4 * r) * st + ni * 16 * es] = acc.v[mi][ni][r];
         }
 }
 
 int sr_launch_paths_eval(const double* Phi, const double* Wk, const double* Ks, const double* C, double* F, int N, int Np,
-                         int Mp, long T, long Tp, int S, int Sp, int n_out, hipStream_t s) {
+                         int Mp, long T, long Tp, int S, int Sp, int n_out, hipStream_t s, int es, int ds) {
     SR_CHECK(Np % srt::BK == 0 && Mp % srt::BK == 0 && Mp > 0 && Tp % srt::BM == 0 && Sp % srt::BN == 0 && T <= Tp && S <= Sp,
              SR_EINVAL, "paths_eval: Np=%d Mp=%d Tp=%ld Sp=%d", Np, Mp, Tp, Sp);
     SR_CHECK(Tp / srt::BM <= 65535, SR_EINVAL, "paths_eval: %ld queries in one chunk (sr_gp_set_chunk)", T);
     const int k_lo = ((Np - N) / srt::BK) * srt::BK;     // rows k < Np - N are padding: K* and c are zero there
+    if (es <= 0) { es = n_out; ds = 1; }
     return sr_launch(sr_paths_eval_kernel, dim3(Sp / srt::BN, (unsigned)(Tp / srt::BM), n_out), dim3(256), 0, s, Phi, Wk, Ks, C, F,
-                     Np, Mp, k_lo, T, Tp, S, Sp, n_out);
+                     Np, Mp, k_lo, T, Tp, S, Sp, es, ds);
 }
 
 // ------------------------------------------------------------------------------------------------
 // KPT: the N + M terms of f_{d,s}(x_s) as one index range [0, N + M): training rows first, features behind; split
 // blockIdx.z takes the terms [sp per, (sp + 1) per).  256 rows of Z (scaled by 1 / l_d, as the K* pass scales them) resp. of
 // omega at a time through LDS.
+// GRAD: next to each range's sum, D sums of its terms' derivatives in the scaled coordinates the loop holds --
+// kappa c_i (z_ij - x_j) / l_j resp. sin(arg) w_i omega_ij -- with the prefactors sf2 / l_j and -sqrt(2 sf2 / M) / l_j at the
+// end; a split's partial sums are then 1 + D rows of Sp (the value first).  The plain form keeps its own statements where the
+// two differ: written through shared temporaries it compiled to 102 instead of 94 VGPRs at DT = 3 (five waves per SIMD -> four).
 // ------------------------------------------------------------------------------------------------
 #define SR_PATHS_ZT 256
-template <int DT>
+template <int DT, bool GRAD>
 __global__ __launch_bounds__(256) void sr_paths_step_kernel(sr_paths_step_args a) {
     __shared__ double rows[SR_PATHS_ZT * DT];
     __shared__ double ta[SR_PATHS_ZT];
@@ -205,6 +259,11 @@ __global__ __launch_bounds__(256) void sr_paths_step_kernel(sr_paths_step_args a
     const int e_beg = sp * per, e_end = min(total, e_beg + per);
     // training rows [e_beg, min(e_end, N)): sum_i exp(-r2 / 2) c_i, times sf2 at the end
     double acck = 0.0;
+    double gk[GRAD ? DT : 1], gf[GRAD ? DT : 1];
+    if (GRAD) {
+#pragma unroll
+        for (int j = 0; j < DT; ++j) gk[j] = gf[j] = 0.0;
+    }
     {
         double xs[DT];
 #pragma unroll
@@ -229,7 +288,15 @@ __global__ __launch_bounds__(256) void sr_paths_step_kernel(sr_paths_step_args a
                     const double df = xs[j] - rows[r * DT + j];
                     r2 = fma(df, df, r2);
                 }
-                acck = fma(sr_kappa(0, r2), cc[(long)(i0 + r) * a.Sp], acck);
+                if (!GRAD) {
+                    acck = fma(sr_kappa(0, r2), cc[(long)(i0 + r) * a.Sp], acck);
+                } else {
+                    const double kap = sr_kappa(0, r2), ci = cc[(long)(i0 + r) * a.Sp];
+                    acck = fma(kap, ci, acck);
+                    const double kc = kap * ci;
+#pragma unroll
+                    for (int j = 0; j < DT; ++j) gk[j] = fma(kc, rows[r * DT + j] - xs[j], gk[j]);
+                }
             }
         }
     }
@@ -257,28 +324,59 @@ __global__ __launch_bounds__(256) void sr_paths_step_kernel(sr_paths_step_args a
                 double arg = 0.0;
 #pragma unroll
                 for (int j = 0; j < DT; ++j) arg = fma(rows[r * DT + j], xs[j], arg);
-                accf = fma(cos(arg + ta[r]), ww[(long)(i0 + r) * a.Sp], accf);
+                if (!GRAD) {
+                    accf = fma(cos(arg + ta[r]), ww[(long)(i0 + r) * a.Sp], accf);
+                } else {                                 // (cos stays the value's cos: sin is taken on its own)
+                    const double wi = ww[(long)(i0 + r) * a.Sp];
+                    accf = fma(cos(arg + ta[r]), wi, accf);
+                    const double sw = sin(arg + ta[r]) * wi;
+#pragma unroll
+                    for (int j = 0; j < DT; ++j) gf[j] = fma(sw, rows[r * DT + j], gf[j]);
+                }
             }
         }
     }
-    if (live)
-        a.part[((long)sp * a.m.n_out + d) * a.Sp + sq] =
-            fma(a.m.sf2[d], acck, sqrt(2.0 * a.m.sf2[d] / (double)a.m.M) * accf);
+    if (!GRAD) {
+        if (live)
+            a.part[((long)sp * a.m.n_out + d) * a.Sp + sq] =
+                fma(a.m.sf2[d], acck, sqrt(2.0 * a.m.sf2[d] / (double)a.m.M) * accf);
+    } else if (live) {
+        const double sf2 = a.m.sf2[d], amp = sqrt(2.0 * sf2 / (double)a.m.M);
+        double* p = a.part + ((long)sp * a.m.n_out + d) * (1 + D) * a.Sp + sq;
+        p[0] = fma(sf2, acck, amp * accf);
+#pragma unroll
+        for (int j = 0; j < DT; ++j)
+            if (j < D) p[(long)(1 + j) * a.Sp] = fma(sf2 * inv_l[j], gk[j], -(amp * inv_l[j]) * gf[j]);
+    }
 }
 
 // KPR: one thread per path: per output the splits in ascending order, then the inputs of the next step as sr_sample_kernel
-// forms them
+// forms them.  GRAD: the partial sums in the layout of KPT<GRAD>; blockIdx.y == 0 does the above, blockIdx.y = 1 + d D + j
+// one element of J (S x n_out x D) per thread the same way -- the pass is bound by the latency of its nsplit dependent
+// additions per sum, so the rows of J go beside the value's instead of behind them
+template <bool GRAD>
 __global__ __launch_bounds__(256) void sr_paths_step_sum_kernel(sr_paths_step_args a) {
     const int sq = blockIdx.x * 256 + threadIdx.x;
     if (sq >= a.S) return;
     const int n_out = a.m.n_out;
+    if (GRAD && blockIdx.y > 0) {
+        const int row = blockIdx.y - 1, d = row / a.m.D, j = row % a.m.D;
+        const long rows = 1 + a.m.D;
+        const double* p = a.part + ((long)d * rows + 1 + j) * a.Sp + sq;
+        double g = 0.0;
+#pragma unroll 8
+        for (int sp = 0; sp < a.nsplit; ++sp) g += p[(long)sp * n_out * rows * a.Sp];
+        a.J[((long)sq * n_out + d) * a.m.D + j] = g;
+        return;
+    }
     double u[SR_PATHS_MAX_D];
     if (a.z_next)
         for (int q = 0; q < a.n_u; ++q) u[q] = a.k_ff[q];
     for (int d = 0; d < n_out; ++d) {
-        const double* p = a.part + (long)d * a.Sp + sq;
+        const long rows = GRAD ? 1 + a.m.D : 1;          // rows of Sp per (split, output)
+        const double* p = a.part + (long)d * rows * a.Sp + sq;
         double f = 0.0;
-        for (int sp = 0; sp < a.nsplit; ++sp) f += p[(long)sp * n_out * a.Sp];
+        for (int sp = 0; sp < a.nsplit; ++sp) f += p[(long)sp * n_out * rows * a.Sp];
         a.F[(long)sq * n_out + d] = f;
         if (a.z_next) {
             a.z_next[(long)sq * a.m.D + d] = f;
@@ -294,6 +392,10 @@ int sr_launch_paths_step(const sr_paths_step_args& a, hipStream_t s) {
              "paths_step: S=%d Sp=%d nsplit=%d n_u=%d", a.S, a.Sp, a.nsplit, a.n_u);
     const dim3 grid((a.S + 255) / 256, a.m.n_out, a.nsplit);
     SR_TRY((sr_pick_le<3, 5, 8>("paths_step", a.m.D, [&](auto dt) {
-        return sr_launch(sr_paths_step_kernel<decltype(dt)::value>, grid, dim3(256), 0, s, a); })));
-    return sr_launch(sr_paths_step_sum_kernel, dim3((a.S + 255) / 256), dim3(256), 0, s, a);
+        constexpr int DT = decltype(dt)::value;
+        if (a.J) return sr_launch(sr_paths_step_kernel<DT, true>, grid, dim3(256), 0, s, a);
+        return sr_launch(sr_paths_step_kernel<DT, false>, grid, dim3(256), 0, s, a); })));
+    if (a.J)
+        return sr_launch(sr_paths_step_sum_kernel<true>, dim3((a.S + 255) / 256, 1 + a.m.n_out * a.m.D), dim3(256), 0, s, a);
+    return sr_launch(sr_paths_step_sum_kernel<false>, dim3((a.S + 255) / 256), dim3(256), 0, s, a);
 }

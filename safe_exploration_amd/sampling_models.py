@@ -27,32 +27,14 @@ class MonteCarloSafetyVerification(object):
         consistent=True: every particle is rolled through ITS OWN posterior function (SimpleGPModel.draw_paths: pathwise
         conditioning on n_features random features) instead of meeting an unrelated marginal draw at every step; the
         model's valid paths are used if there are n_samples of them, otherwise they are drawn here (eps is not read).
-        Returns S (n_samples, n_s) and S_all (n, n_samples, n_s)."""
+        Returns S (n_samples, n_s) and S_all (n, n_samples, n_s).  With the transition Jacobians of the consistent rollout:
+        sample_n_step_jacobians."""
+        if consistent:
+            return self._consistent_rollout(x0, K, k, n, n_samples, generator, as_tensor, n_features, False)
         n_s, n_u = self.n_s, self.n_u
-        assert n > 0, "The time horizon n for the multi-step sampling must be positive!"
-        assert np.shape(K) == (n, n_u, n_s), "Required shape of K is ({},{},{})".format(n, n_u, n_s)
-        assert np.shape(k) == (n, n_u), "Required shape of k is ({},{})".format(n, n_u)
-        K = np.asarray(K, dtype=np.float64)
-        k = np.asarray(k, dtype=np.float64)
-        x0 = np.asarray(x0, dtype=np.float64).reshape(n_s, 1)
-        u0 = K[0].dot(x0) + k[0, :, None]
-        inp = np.vstack((x0, u0)).T
+        K, k, inp = self._closed_loop_start(x0, K, k, n)
         dev = self.GP.device
         S_all = B.empty((n, n_samples, n_s), dev)
-        if consistent:
-            if self.GP.paths_count()[0] != n_samples:
-                self.GP.draw_paths(n_samples, n_features, generator)
-            inp = B.as_dev(inp, dev, (1, n_s + n_u)).expand(n_samples, n_s + n_u).contiguous()
-            for i in range(n):
-                if i + 1 < n:
-                    S, inp = self.GP.paths_step_device(inp, K[i + 1], k[i + 1])
-                else:
-                    S = self.GP.paths_step_device(inp)
-                S_all[i].copy_(S)
-            if as_tensor:
-                return S_all[n - 1], S_all
-            out = B.to_numpy(S_all)
-            return out[n - 1].squeeze(), out
         for i in range(n):
             e = None
             if eps is not None:
@@ -69,6 +51,58 @@ class MonteCarloSafetyVerification(object):
             return S_all[n - 1], S_all
         out = B.to_numpy(S_all)
         return out[n - 1].squeeze(), out
+
+    def sample_n_step_jacobians(self, x0, K, k, n=1, n_samples=1000, generator=None, as_tensor=False, consistent=True,
+                                n_features=1024):
+        """sample_n_step(consistent=True) with the closed-loop transition Jacobian of every step and particle: returns
+        S (n_samples, n_s), S_all (n, n_samples, n_s) -- bit for bit those of sample_n_step(consistent=True) on the same
+        paths -- and A_all (n, n_samples, n_s, n_s), A_all[i] = J_i[..., :n_s] + J_i[..., n_s:] K[i] = d x_{i+1} / d x_i with
+        J_i the Jacobian of the particle's own path at step i's input (paths_step_device(jacobians=True)); d x_n / d x_0 is
+        their ordered product.  consistent=False raises ValueError: a marginal draw has no function to differentiate."""
+        if not consistent:
+            raise ValueError("sample_n_step_jacobians needs consistent=True (a marginal draw has no function to differentiate)")
+        return self._consistent_rollout(x0, K, k, n, n_samples, generator, as_tensor, n_features, True)
+
+    def _closed_loop_start(self, x0, K, k, n):
+        n_s, n_u = self.n_s, self.n_u
+        assert n > 0, "The time horizon n for the multi-step sampling must be positive!"
+        assert np.shape(K) == (n, n_u, n_s), "Required shape of K is ({},{},{})".format(n, n_u, n_s)
+        assert np.shape(k) == (n, n_u), "Required shape of k is ({},{})".format(n, n_u)
+        K = np.asarray(K, dtype=np.float64)
+        k = np.asarray(k, dtype=np.float64)
+        x0 = np.asarray(x0, dtype=np.float64).reshape(n_s, 1)
+        u0 = K[0].dot(x0) + k[0, :, None]
+        return K, k, np.vstack((x0, u0)).T
+
+    def _consistent_rollout(self, x0, K, k, n, n_samples, generator, as_tensor, n_features, jacobians):
+        """every particle through its own path (drawn here unless the model holds n_samples valid ones); with jacobians the
+        batched product J_x + J_u K[i] per step on the device"""
+        n_s, n_u = self.n_s, self.n_u
+        K, k, inp = self._closed_loop_start(x0, K, k, n)
+        dev = self.GP.device
+        S_all = B.empty((n, n_samples, n_s), dev)
+        if self.GP.paths_count()[0] != n_samples:
+            self.GP.draw_paths(n_samples, n_features, generator)
+        inp = B.as_dev(inp, dev, (1, n_s + n_u)).expand(n_samples, n_s + n_u).contiguous()
+        if jacobians:
+            A_all = B.empty((n, n_samples, n_s, n_s), dev)
+            Kt = B.as_dev(K, dev, (n, n_u, n_s))
+        for i in range(n):
+            if i + 1 < n:
+                out = self.GP.paths_step_device(inp, K[i + 1], k[i + 1], jacobians=jacobians)
+                S, inp = out[0], out[1]
+            else:
+                out = self.GP.paths_step_device(inp, jacobians=jacobians)
+                S = out[0] if jacobians else out
+            S_all[i].copy_(S)
+            if jacobians:
+                J = out[-1]
+                A_all[i].copy_(J[..., :n_s] + J[..., n_s:].matmul(Kt[i]))
+        res = (S_all[n - 1], S_all) + ((A_all,) if jacobians else ())
+        if as_tensor:
+            return res
+        out = tuple(B.to_numpy(t) for t in res[1:])
+        return (out[0][n - 1].squeeze(),) + out
 
     def inside_ellipsoid_ratio(self, S, Q, p):
         """Ratio of samples inside the ellipsoid of each time step  (sampling_models.py:82-107).

@@ -1455,9 +1455,10 @@ class SimpleGPModel(StateSpaceModel):
         check(lib.sr_gp_paths_count(self._handle.h, ctypes.byref(S), ctypes.byref(M)))
         return S.value, M.value
 
-    def sample_paths_device(self, x):
+    def sample_paths_device(self, x, jacobians=False):
         """Every drawn path at every input: x (n, D) -> (n, size, n_s_out), the shape of sample_from_gp; the values of one
-        path at several inputs are those of ONE function."""
+        path at several inputs are those of ONE function.  jacobians=True: (F, J) with J (n, size, n_s_out, D) the
+        derivative of every value in its input (closed form over the same draws; F is bit for bit the F without)."""
         self._need_trained()
         hd = self._handle
         x = B.as_dev(x, hd.device)
@@ -1465,17 +1466,24 @@ class SimpleGPModel(StateSpaceModel):
             raise ValueError("x must be (n, {})".format(hd.D))
         S = self._need_paths()
         F = B.empty((x.shape[0], S, hd.n_out), hd.device)
+        if jacobians:
+            J = B.empty((x.shape[0], S, hd.n_out, hd.D), hd.device)
+            check(lib.sr_gp_paths_eval_grad(hd.h, B.ptr(x), x.shape[0], B.ptr(F), B.ptr(J), B.stream_ptr(hd.device)))
+            return F, J
         check(lib.sr_gp_paths_eval(hd.h, B.ptr(x), x.shape[0], B.ptr(F), B.stream_ptr(hd.device)))
         return F
 
-    def sample_paths(self, x):
+    def sample_paths(self, x, jacobians=False):
         """sample_paths_device, NumPy in / NumPy out (a tensor in: a tensor out)."""
-        F = self.sample_paths_device(x)
-        return F if B.is_tensor(x) else B.to_numpy(F)
+        out = self.sample_paths_device(x, jacobians)
+        if B.is_tensor(x):
+            return out
+        return tuple(B.to_numpy(o) for o in out) if jacobians else B.to_numpy(out)
 
-    def paths_step_device(self, x_s, k_fb=None, k_ff=None):
+    def paths_step_device(self, x_s, k_fb=None, k_ff=None, jacobians=False):
         """Path s at its OWN input: x_s (size, D) -> F (size, n_s_out).  With k_fb (n_u, n_s_out) and k_ff (n_u,) the
-        closed-loop next inputs [F, k_fb F + k_ff] (size, D) are returned as well, as sample_device returns them."""
+        closed-loop next inputs [F, k_fb F + k_ff] (size, D) are returned as well, as sample_device returns them.
+        jacobians=True: J (size, n_s_out, D), the derivative of F[s] in x_s[s], comes last: (F, J) or (F, z_next, J)."""
         self._need_trained()
         hd = self._handle
         S = self._need_paths()
@@ -1489,6 +1497,11 @@ class SimpleGPModel(StateSpaceModel):
             tk = B.as_dev(k_fb, hd.device, (n_u, hd.n_out))
             tf = B.as_dev(k_ff, hd.device, (n_u,))
             z = B.empty((S, hd.D), hd.device)
+        if jacobians:
+            J = B.empty((S, hd.n_out, hd.D), hd.device)
+            check(lib.sr_gp_paths_step_grad(hd.h, B.ptr(x), B.ptr(F), B.ptr(J), B.ptr(tk), B.ptr(tf), B.ptr(z),
+                                            B.stream_ptr(hd.device)))
+            return (F, J) if z is None else (F, z, J)
         check(lib.sr_gp_paths_step(hd.h, B.ptr(x), B.ptr(F), B.ptr(tk), B.ptr(tf), B.ptr(z), B.stream_ptr(hd.device)))
         return F if z is None else (F, z)
 
