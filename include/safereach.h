@@ -496,6 +496,33 @@ int sr_test_gemm_tn(int device, const double* A, long lda, const double* B, long
  * super-tiles, -1 chosen by size. */
 int sr_test_gemm_tn_upper(int device, const double* A, long lda, const double* B, long ldb, double* C, long ldc,
                           int M, int N, int K, double alpha, double beta, int order, void* stream);
+/* diagnostics: the TN products of csrc/sr_gemm.hip one at a time, for tests that compare a single product with a reference.
+ * Every entry checks its arguments BEFORE it touches a device and answers SR_EINVAL (sr_last_error says why) instead of
+ * launching: NULL pointers, M / N no multiples of 128, K no multiple of 16, a leading dimension below the width or -- for the
+ * operands A and B, whose tiles travel in 16-byte pieces -- odd, operands not 16-byte aligned, odd operand strides of a batch.
+ * mode as sr_test_gemm_tn plus 3 (A block-upper-triangular: k ends at m0 + 128) and 4 (A block-lower-triangular: k starts at
+ * m0).  Batch: n equally shaped products, member z at A + z sA, B + z sB, C + z sC (doubles); n = 1 is the plain call.
+ * prio != 0: the workgroups raise their wavefront priority (same results).
+ * _ex: sr_test_gemm_tn / sr_test_gemm_tn_upper with prio and a batch. */
+int sr_test_gemm_tn_ex(int device, const double* A, long lda, const double* B, long ldb, double* C, long ldc, int M, int N,
+                       int K, double alpha, double beta, int mode, int prio, int n, long sA, long sB, long sC, void* stream);
+int sr_test_gemm_tn_upper_ex(int device, const double* A, long lda, const double* B, long ldb, double* C, long ldc, int M,
+                             int N, int K, double alpha, double beta, int order, int prio, int n, long sA, long sB, long sC,
+                             void* stream);
+/* split-K form: C (M x N, contiguous) = alpha A^T B restricted by mode, summed in order from K-slices of ks rows (a
+ * multiple of 128) that are written to part first; part_len (doubles) must be at least ceil(K / ks) M N. */
+int sr_test_gemm_tn_splitk(int device, const double* A, long lda, const double* B, long ldb, double* C, int M, int N, int K,
+                           int ks, double alpha, int mode, double* part, long part_len, void* stream);
+/* a list of products in one launch: C_j (M_j x N_j) = alpha A_j^T B_j and, with CTb != NULL, CT_j = C_j^T, at the offsets
+ * a, b, c, ct (doubles) of the base pointers, common leading dimension ld.  mode 2: B lower-triangular (k starts at the
+ * tile's first column), mode 3: A upper-triangular (k ends behind the tile's last row) -- at the granularity of the
+ * workgroup tile, 64 if tiles128 < 1024 and 128 otherwise.  jobs_host is a HOST array (copied to the device for the call);
+ * lenA .. lenCT are the lengths of the base buffers in doubles, and every job's rectangles -- of every batch member, sCT
+ * being the stride of CTb -- must lie inside them; maxM, maxN: at least every job's M, N (they size the grid). */
+typedef struct sr_gemm_job { long a, b, c, ct; int M, N, K, pad; } sr_gemm_job;
+int sr_test_gemm_tn_jobs(int device, const double* Ab, long lenA, const double* Bb, long lenB, double* Cb, long lenC,
+                         double* CTb, long lenCT, long ld, const sr_gemm_job* jobs_host, int njobs, int maxM, int maxN,
+                         long tiles128, double alpha, int mode, int n, long sA, long sB, long sC, long sCT, void* stream);
 /* diagnostic: the diagonal-block kernel of the factorisation alone: A (128 x 128 SPD, upper triangle read, leading
  * dimension lda) -> upper Cholesky factor in place, wt = its inverse, w = the inverse transposed (leading dimension
  * ldw); info: device int, 0 or the 1-based first non-positive pivot.  skip: 0 in production; 64 leaves A untouched

@@ -114,6 +114,10 @@ SIGNATURES = {
     "sr_test_flow_fail": (_I, [_I]),
     "sr_test_gemm_tn": (_I, [_I, _P, _L, _P, _L, _P, _L, _I, _I, _I, _D, _D, _I, _P]),
     "sr_test_gemm_tn_upper": (_I, [_I, _P, _L, _P, _L, _P, _L, _I, _I, _I, _D, _D, _I, _P]),
+    "sr_test_gemm_tn_ex": (_I, [_I, _P, _L, _P, _L, _P, _L, _I, _I, _I, _D, _D, _I, _I, _I, _L, _L, _L, _P]),
+    "sr_test_gemm_tn_upper_ex": (_I, [_I, _P, _L, _P, _L, _P, _L, _I, _I, _I, _D, _D, _I, _I, _I, _L, _L, _L, _P]),
+    "sr_test_gemm_tn_splitk": (_I, [_I, _P, _L, _P, _L, _P, _I, _I, _I, _I, _D, _I, _P, _L, _P]),
+    "sr_test_gemm_tn_jobs": (_I, [_I, _P, _L, _P, _L, _P, _L, _P, _L, _L, _P, _I, _I, _I, _L, _D, _I, _I, _L, _L, _L, _L, _P]),
     "sr_test_potrf_diag": (_I, [_I, _P, _L, _P, _P, _L, _P, _I, _P]),
     "sr_test_chain_drop": (_I, [_H, _I]),
     "sr_test_grid_append_abort": (_I, [_I]),

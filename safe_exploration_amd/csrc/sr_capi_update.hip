@@ -1017,6 +1017,100 @@ extern "C" int sr_test_gemm_tn_upper(int device, const double* A, long lda, cons
     return sr_launch_gemm_tn_upper(A, lda, B, ldb, C, ldc, M, N, K, alpha, beta, (hipStream_t)stream, 0, order);
 }
 
+// ---- the TN GEMM family in isolation (tests/test_gpu_gemm_family.py): the product launchers, unchanged, behind argument checks
+// that turn a mistake of the caller into SR_EINVAL before anything is launched (and before a device is touched)
+static bool gemm_test_operand_ok(const void* p, long ld, long width) {
+    return p != nullptr && ((size_t)p & 15) == 0 && ld >= width && ld % 2 == 0;     // (the LDS-DMA moves 16-byte pieces)
+}
+static int gemm_test_args_ok(const char* who, const double* A, long lda, const double* B, long ldb, const double* C, long ldc,
+                             int M, int N, int K, int mode, int n, long sA, long sB, long sC) {
+    SR_CHECK(A && B && C, SR_EINVAL, "%s: NULL argument", who);
+    SR_CHECK(M > 0 && N > 0 && K > 0 && M % 128 == 0 && N % 128 == 0 && K % 16 == 0, SR_EINVAL,
+             "%s: M=%d N=%d K=%d must be multiples of 128, 128 and 16", who, M, N, K);
+    SR_CHECK(gemm_test_operand_ok(A, lda, M) && gemm_test_operand_ok(B, ldb, N) && ldc >= N, SR_EINVAL,
+             "%s: lda=%ld ldb=%ld ldc=%ld (at least M, N, N; lda, ldb even, A and B 16-byte aligned)", who, lda, ldb, ldc);
+    SR_CHECK(mode >= 0 && mode <= 4, SR_EINVAL, "%s: mode=%d", who, mode);
+    SR_CHECK(n >= 1 && n <= 65535 && sA >= 0 && sB >= 0 && sC >= 0 && sA % 2 == 0 && sB % 2 == 0, SR_EINVAL,
+             "%s: batch n=%d strides %ld %ld %ld (not negative; A's and B's even)", who, n, sA, sB, sC);
+    SR_CHECK(n == 1 || sC >= (long)(M - 1) * ldc + N, SR_EINVAL, "%s: the results of the batch overlap (sC=%ld)", who, sC);
+    return SR_OK;
+}
+
+extern "C" int sr_test_gemm_tn_ex(int device, const double* A, long lda, const double* B, long ldb, double* C, long ldc,
+                                  int M, int N, int K, double alpha, double beta, int mode, int prio, int n, long sA,
+                                  long sB, long sC, void* stream) {
+    SR_TRY(gemm_test_args_ok("sr_test_gemm_tn_ex", A, lda, B, ldb, C, ldc, M, N, K, mode, n, sA, sB, sC));
+    SR_DEVICE(device);
+    sr_batch bt; bt.n = n; bt.sA = sA; bt.sB = sB; bt.sC = sC;
+    return sr_launch_gemm_tn(A, lda, B, ldb, C, ldc, M, N, K, alpha, beta, mode, (hipStream_t)stream, prio, &bt);
+}
+
+extern "C" int sr_test_gemm_tn_upper_ex(int device, const double* A, long lda, const double* B, long ldb, double* C,
+                                        long ldc, int M, int N, int K, double alpha, double beta, int order, int prio,
+                                        int n, long sA, long sB, long sC, void* stream) {
+    SR_TRY(gemm_test_args_ok("sr_test_gemm_tn_upper_ex", A, lda, B, ldb, C, ldc, M, N, K, 1, n, sA, sB, sC));
+    SR_CHECK(M <= N && order >= -1 && order <= 1, SR_EINVAL, "sr_test_gemm_tn_upper_ex: M=%d N=%d order=%d", M, N, order);
+    SR_DEVICE(device);
+    sr_batch bt; bt.n = n; bt.sA = sA; bt.sB = sB; bt.sC = sC;
+    return sr_launch_gemm_tn_upper(A, lda, B, ldb, C, ldc, M, N, K, alpha, beta, (hipStream_t)stream, prio, order, &bt);
+}
+
+extern "C" int sr_test_gemm_tn_splitk(int device, const double* A, long lda, const double* B, long ldb, double* C, int M,
+                                      int N, int K, int ks, double alpha, int mode, double* part, long part_len,
+                                      void* stream) {
+    SR_TRY(gemm_test_args_ok("sr_test_gemm_tn_splitk", A, lda, B, ldb, C, N, M, N, K, mode, 1, 0, 0, 0));
+    SR_CHECK(part != nullptr && ks > 0 && ks % 128 == 0, SR_EINVAL, "sr_test_gemm_tn_splitk: ks=%d (a multiple of 128) or part NULL", ks);
+    const long nsl = ((long)K + ks - 1) / ks;
+    SR_CHECK(part_len >= nsl * M * N, SR_EINVAL, "sr_test_gemm_tn_splitk: part holds %ld doubles, %ld slices of %d x %d need %ld",
+             part_len, nsl, M, N, nsl * M * N);
+    SR_DEVICE(device);
+    return sr_launch_gemm_tn_splitk(A, lda, B, ldb, C, M, N, K, ks, alpha, mode, part, (hipStream_t)stream);
+}
+
+extern "C" int sr_test_gemm_tn_jobs(int device, const double* Ab, long lenA, const double* Bb, long lenB, double* Cb, long lenC,
+                                    double* CTb, long lenCT, long ld, const sr_gemm_job* jobs_host, int njobs, int maxM,
+                                    int maxN, long tiles128, double alpha, int mode, int n, long sA, long sB, long sC,
+                                    long sCT, void* stream) {
+    const char* who = "sr_test_gemm_tn_jobs";
+    SR_CHECK(Ab && Bb && Cb && jobs_host, SR_EINVAL, "%s: NULL argument", who);
+    SR_CHECK(((size_t)Ab & 15) == 0 && ((size_t)Bb & 15) == 0 && ld > 0 && ld % 2 == 0, SR_EINVAL,
+             "%s: ld=%ld must be even, A and B 16-byte aligned", who, ld);
+    SR_CHECK(njobs > 0 && n >= 1 && (long)njobs * n <= 65535 && maxM > 0 && maxN > 0 && maxM % 128 == 0 && maxN % 128 == 0 &&
+             (mode == 2 || mode == 3) && tiles128 > 0, SR_EINVAL, "%s: njobs=%d n=%d maxM=%d maxN=%d mode=%d tiles128=%ld", who,
+             njobs, n, maxM, maxN, mode, tiles128);
+    SR_CHECK(sA >= 0 && sB >= 0 && sC >= 0 && sCT >= 0 && sA % 2 == 0 && sB % 2 == 0, SR_EINVAL,
+             "%s: batch strides %ld %ld %ld %ld (not negative; A's and B's even)", who, sA, sB, sC, sCT);
+    // extent of a rows x cols rectangle at offset off of the last batch member, against the buffer's length
+    auto inside = [&](long off, int rows, int cols, long stride, long len) {
+        return off >= 0 && cols <= ld && off + (long)(n - 1) * stride + (long)(rows - 1) * ld + cols <= len;
+    };
+    for (int j = 0; j < njobs; ++j) {
+        const sr_gemm_job& jb = jobs_host[j];
+        SR_CHECK(jb.M > 0 && jb.N > 0 && jb.K > 0 && jb.M % 128 == 0 && jb.N % 128 == 0 && jb.K % 16 == 0 && jb.M <= maxM &&
+                 jb.N <= maxN, SR_EINVAL, "%s: job %d: M=%d N=%d K=%d (multiples of 128, 128, 16, within maxM, maxN)", who, j,
+                 jb.M, jb.N, jb.K);
+        SR_CHECK(jb.a % 2 == 0 && jb.b % 2 == 0, SR_EINVAL, "%s: job %d: operand offsets %ld %ld must be even", who, j, jb.a, jb.b);
+        SR_CHECK(inside(jb.a, jb.K, jb.M, sA, lenA) && inside(jb.b, jb.K, jb.N, sB, lenB) && inside(jb.c, jb.M, jb.N, sC, lenC) &&
+                 (CTb == nullptr || inside(jb.ct, jb.N, jb.M, sCT, lenCT)), SR_EINVAL,
+                 "%s: job %d reaches past its buffers (lengths %ld %ld %ld %ld)", who, j, lenA, lenB, lenC, lenCT);
+    }
+    SR_DEVICE(device);
+    hipStream_t s = (hipStream_t)stream;
+    sr_gemm_job* jobs_dev = nullptr;
+    SR_TRY(dev_alloc(&jobs_dev, (size_t)njobs));
+    sr_batch bt; bt.n = n; bt.sA = sA; bt.sB = sB; bt.sC = sC; bt.sCT = sCT;
+    hipError_t e = hipMemcpyAsync(jobs_dev, jobs_host, sizeof(sr_gemm_job) * njobs, hipMemcpyHostToDevice, s);
+    int rc = SR_OK;
+    if (e == hipSuccess)
+        rc = sr_launch_gemm_tn_jobs(Ab, Bb, Cb, CTb, ld, jobs_dev, njobs, maxM, maxN, tiles128, alpha, mode, s, &bt);
+    const hipError_t e2 = hipStreamSynchronize(s);          // the table must outlive the launch
+    dev_free(jobs_dev);
+    if (rc != SR_OK) return rc;
+    SR_HIP(e);
+    SR_HIP(e2);
+    return SR_OK;
+}
+
 extern "C" int sr_test_potrf_diag(int device, double* A, long lda, double* wt, double* w, long ldw, int* info,
                                   int skip, void* stream) {
     SR_CHECK(A && wt && w && info, SR_EINVAL, "sr_test_potrf_diag: NULL argument");

@@ -136,7 +136,7 @@ int sr_launch_gemm_tn_splitk(const double* A, long lda, const double* B, long ld
 // a list of independent TN products in one launch (one level of the recursive triangular inversion):
 // C_j = alpha A_j^T B_j, optionally also CT_j = C_j^T; operands at offsets (doubles) of common base pointers,
 // common leading dimension.  mode 2 / 3 as above.
-struct sr_gemm_job { long a, b, c, ct; int M, N, K, pad; };
+// struct sr_gemm_job { long a, b, c, ct; int M, N, K, pad; }: include/safereach.h (the test entry of the list takes it)
 // tiles128: 128 x 128 tiles of the whole list (picks the workgroup tile)
 int sr_launch_gemm_tn_jobs(const double* Ab, const double* Bb, double* Cb, double* CTb, long ld,
                            const sr_gemm_job* jobs_dev, int njobs, int maxM, int maxN, long tiles128, double alpha,
