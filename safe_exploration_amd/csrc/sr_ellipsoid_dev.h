@@ -83,6 +83,10 @@ __device__ __forceinline__ double sr_lambda_max_qb(const double (&q)[NS][NS],
     //          M_pp -= t a,  M_rr += t a,  M_pr = 0,  (M_kp, M_kr) <- (c M_kp - s M_kr, s M_kp + c M_kr)  for k != p, r
     // (the textbook form through theta = d / 2a takes two square roots and three divisions; on one lane per query the
     // rotations are the whole cost of the step for n_s >= 3).
+    // Range of validity: off and dia are sums of SQUARES, so for |M_ij| below about 1e-154 they underflow, off == 0.0 ends the
+    // loop and the diagonal is returned unrotated.  Whenever |Q| is that small the remainder box n_s (l_mu r^2)^2 of the
+    // caller has underflowed as well and the step is non-finite anyway: nothing is rescaled here.  (tests/
+    // test_gpu_ellipsoid_family.py sweeps the scale of Q from 1e-100 to 1e+100.)
 #define SR_SYM(i, j) M[(i) < (j) ? (i) : (j)][(i) < (j) ? (j) : (i)]
     for (int sweep = 0; sweep < 24; ++sweep) {
         double off = 0.0, dia = 0.0;
