@@ -552,6 +552,36 @@ int sr_gp_grid_append_aborts(sr_gp_t h, long* n);
 /* diagnostic: in-place one-point appends the model's buffers have taken since they were last plain (0: U^-1, alpha and the
  * targets start at their allocations; k: they are views k steps in).  Read-only; tests use it to know which state they met. */
 int sr_gp_slide_steps(sr_gp_t h, int* steps);
+/* diagnostic: which kernels the last posterior pass of h launched (the last chunk of an sr_gp_predict; the pass inside a
+ * reachability step or an append counts too).  Fills out[0 .. min(cap, SR_ROUTE_WORDS)) and returns the words written:
+ *   [SR_ROUTE_ID]      SR_ROUTE_K0 one launch, _STREAM1 the VALU streaming kernel (<= 4 columns), _MFMA1 one-chunk MFMA work
+ *                      items, _RUNS the MFMA run kernel on the planned work-item table, _K2S streamed groups of 16, _K2B balanced
+ *                      shares, _K2M 64 x 64 tiles, _K2 plain tiles; 0 = no pass yet
+ *   [SR_ROUTE_SRC]     streamed kernels: 0 columns read from the K* pass, 1 evaluated inside the kernel
+ *   [SR_ROUTE_WIDTH]   _STREAM1: columns per thread (1 / 4); _MFMA1 / _RUNS: groups of 16 columns per workgroup (1 / 2 / 4 / 8)
+ *   [SR_ROUTE_NC]      columns the streamed kernels work on (1, 4, 16, 32, 64)
+ *   [SR_ROUTE_KC]      k-chunks per work item of the plan (1: one-chunk items)
+ *   [SR_ROUTE_KR .. _NWG]  _RUNS: rows per run, work items and workgroups per (output, column group)
+ *   [SR_ROUTE_MULTI]   _RUNS: 1 = workgroups that run several items one after the other
+ *   [SR_ROUTE_REDUCE]  _RUNS: items of the last column block (the reduce kernel's register form holds up to 12)
+ *   [SR_ROUTE_POLLED]  _STREAM1: 1 = the polling finaliser on its self-validating slots
+ *   [SR_ROUTE_NSPLIT]  splits of the training rows in the mean / Jacobian partial sums
+ *   [SR_ROUTE_BAL_WGS] _K2B: workgroups of the balanced launch
+ *   [SR_ROUTE_FINAL]   0 final stage inside the posterior kernels, 1 one wavefront per (query, output), 2 one thread per query
+ *   [SR_ROUTE_UNSLID]  1 = the pass met an odd slide and put the model back into plain buffers first
+ *   [SR_ROUTE_T]       queries of the pass */
+#define SR_ROUTE_WORDS 16
+enum { SR_ROUTE_ID = 0, SR_ROUTE_SRC, SR_ROUTE_WIDTH, SR_ROUTE_NC, SR_ROUTE_KC, SR_ROUTE_KR, SR_ROUTE_NITEMS, SR_ROUTE_NWG,
+       SR_ROUTE_MULTI, SR_ROUTE_REDUCE, SR_ROUTE_POLLED, SR_ROUTE_NSPLIT, SR_ROUTE_BAL_WGS, SR_ROUTE_FINAL, SR_ROUTE_UNSLID,
+       SR_ROUTE_T };
+enum { SR_ROUTE_K0 = 1, SR_ROUTE_STREAM1, SR_ROUTE_MFMA1, SR_ROUTE_RUNS, SR_ROUTE_K2S, SR_ROUTE_K2B, SR_ROUTE_K2M, SR_ROUTE_K2 };
+int sr_gp_last_route(sr_gp_t h, int* out, int cap);
+/* host only: the plan of the streamed MFMA route (csrc/sr_stream.hip) for a model of Np padded rows and n_out outputs, ncols
+ * queries (5 .. 128, or 1 .. 4 widened to 16 as the 2 .. 4-query route does: pass 16) on a device of n_cu compute units;
+ * can_fuse != 0: the kernel may evaluate its own K* rows (ARD-RBF, D <= 5).  out[0..5] = groups of 16 columns per workgroup,
+ * k-chunks per item of the plan, rows per run (0: one-chunk items, no table), work items, workgroups, items of the last column
+ * block. */
+int sr_test_stream_plan(int Np, int n_out, int ncols, int n_cu, int can_fuse, int* out);
 /* per-kernel hipEvent timing inside the library (adds an event pair per launch while enabled). */
 int sr_prof_enable(sr_gp_t h, int on);
 int sr_prof_reset (sr_gp_t h);

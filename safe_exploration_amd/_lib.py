@@ -123,6 +123,8 @@ SIGNATURES = {
     "sr_test_grid_append_abort": (_I, [_I]),
     "sr_gp_grid_append_aborts": (_I, [_H, _PL]),
     "sr_gp_slide_steps": (_I, [_H, _PI]),
+    "sr_gp_last_route": (_I, [_H, _PI, _I]),
+    "sr_test_stream_plan": (_I, [_I, _I, _I, _I, _I, _PI]),
     "sr_prof_enable": (_I, [_H, _I]),
     "sr_prof_reset": (_I, [_H]),
     "sr_prof_get": (_I, [_H, _I, _PD, _PL]),

@@ -119,6 +119,8 @@ static int stream_predict(sr_gp* h, long Tc, const double* xa, long lda, int na,
                           double* mu, double* var, double* jac, hipStream_t s) {
     const long Tp = srt::BN;
     const int ncb = (h->Np + 255) / 256;
+    std::fill(h->last_route, h->last_route + SR_ROUTE_WORDS, 0);     // (sr_gp_call1 comes here without gp_pass)
+    h->last_route[SR_ROUTE_T] = (int)Tc;
     // 2 .. 4 queries on a moderate model: the one-launch VALU kernel has only ncb (ncb + 1) n_out workgroups of 256
     // threads there and loses to K1 + MFMA kernel + reduce (N = 700: 27 against 21 us; N = 3000: 34 against 40 us)
     const bool mfma_small = Tc >= 2 && Tc <= 4 && h->Np <= SR_MFMA_SMALL_MAX_NP;
@@ -165,8 +167,9 @@ static int stream_predict(sr_gp* h, long Tc, const double* xa, long lda, int na,
     }
     SR_TRY(stream_items(h, a, (int)Tc, a.width_min, fused, s));
     h->last_streamed = 0;
+    h->last_route[SR_ROUTE_NSPLIT] = nsplit;
     sr_prof_scope ps(&h->prof, SR_K_VAR, s);
-    return sr_launch_stream(a, fused ? 1 : 0, s);
+    return sr_launch_stream(a, fused ? 1 : 0, s, h->last_route);
 }
 
 static int stream_linearize(sr_gp* h, const double* x, double* mu, double* var, double* jac_mu, double* jac_var,
@@ -209,6 +212,7 @@ static int stream_linearize(sr_gp* h, const double* x, double* mu, double* var, 
 int srh::tile_route_alignment(sr_gp* h) {
     if (!(h->slide & 1)) return SR_OK;
     SR_TRY(unslide(h));
+    h->last_route[SR_ROUTE_UNSLID] = 1;
     const int shift = std::min(h->slide_forced, 14);
     h->slide_hold = 64 << shift;
     ++h->slide_forced;
@@ -221,12 +225,16 @@ int srh::gp_pass(sr_gp* h, long Tc, const double* xa, long lda, int na, const do
     //  own, 18.8 us; the streamed route spreads them over 6 workgroups per output: 12.4 us.  From 4 queries on the two
     //  are level, and 16 queries share one fetch in the one-launch pass.)
     const bool one_streamed = h->Np == SR_ONE_STREAMED_NP && Tc == 1 && !h->general && h->D <= SR_STREAM_FUSED_MAX_D;
+    int* const route = h->last_route;
+    std::fill(route, route + SR_ROUTE_WORDS, 0);
+    route[SR_ROUTE_T] = (int)std::min(Tc, 2147483647L);
     if (h->small_path == 1 && !h->force_stream && !one_streamed && sr_gp_small_wanted(h->Np, Tc, h->D, h->general != 0)) {
         // small model, few queries: one launch, no workspace (sr_small.hip)
         sr_kstar_args ka = kstar_model(h);
         ka.xa = xa; ka.lda = lda; ka.na = na; ka.xb = xb; ka.ldb = ldb; ka.nb = nb;
         ka.T = Tc; ka.Tp = Tc;
         h->last_streamed = 0;
+        route[SR_ROUTE_ID] = SR_ROUTE_K0;
         sr_prof_scope ps(&h->prof, SR_K_SMALL, s);
         return sr_launch_gp_small(ka, h->Wt, mu, var, jac, s);
     }
@@ -252,8 +260,11 @@ int srh::gp_pass(sr_gp* h, long Tc, const double* xa, long lda, int na, const do
     int nrb = h->Np / SR_NB;
     const double* var_part = h->var_part;
     h->last_streamed = 0;
+    route[SR_ROUTE_NSPLIT] = nsplit;
+    route[SR_ROUTE_FINAL] = Tc <= SR_FINAL_WAVE_T ? 1 : 2;
     if (small_var) {
         h->last_streamed = 1;
+        route[SR_ROUTE_ID] = SR_ROUTE_K2S;
         // latency regime: stream U^-1 once (HBM-bound) instead of the MFMA tiles
         if (!h->small_vp) SR_TRY(dev_alloc(&h->small_vp, (size_t)sr_var_small_ws(h->Np, h->n_out)));
         sr_prof_scope ps(&h->prof, SR_K_VAR, s);
@@ -265,6 +276,8 @@ int srh::gp_pass(sr_gp* h, long Tc, const double* xa, long lda, int na, const do
         if (!h->splitk_part) SR_TRY(dev_alloc(&h->splitk_part, (size_t)4 * 1024 * srt::BN));
         var_part = h->splitk_part;
         nrb = 4 * (h->Np / SR_NB);
+        route[SR_ROUTE_ID] = SR_ROUTE_K2B;
+        route[SR_ROUTE_BAL_WGS] = (int)sr_var_bal_wgs((long)h->n_out * (Tp / srt::BN) * (h->Np / SR_NB) * (h->Np / SR_NB + 1) / 2);
         sr_prof_scope ps(&h->prof, SR_K_VAR, s);
         SR_TRY(tile_route_alignment(h));
         SR_TRY(sr_launch_var_bal(h->Wt, h->Ks, h->splitk_vt.get(), h->splitk_part, h->N, h->Np, Tp, h->n_out, s));
@@ -273,10 +286,12 @@ int srh::gp_pass(sr_gp* h, long Tc, const double* xa, long lda, int na, const do
         if (!h->splitk_part) SR_TRY(dev_alloc(&h->splitk_part, (size_t)4 * 1024 * srt::BN));
         var_part = h->splitk_part;             // n_out * (Np/64) * Tp <= 2 * 256 * 128 * 16 doubles
         nrb = h->Np / 64;
+        route[SR_ROUTE_ID] = SR_ROUTE_K2M;
         sr_prof_scope ps(&h->prof, SR_K_VAR, s);
         SR_TRY(tile_route_alignment(h));
         SR_TRY(sr_launch_var64(h->Wt, h->Ks, h->splitk_part, h->N, h->Np, Tp, h->n_out, s));
     } else {
+        route[SR_ROUTE_ID] = SR_ROUTE_K2;
         sr_prof_scope ps(&h->prof, SR_K_VAR, s);
         SR_TRY(tile_route_alignment(h));
         SR_TRY(sr_launch_var(h->Wt, h->Ks, h->var_part, h->N, h->Np, Tp, h->n_out, h->var_group, h->var_variant, s));
@@ -287,6 +302,13 @@ int srh::gp_pass(sr_gp* h, long Tc, const double* xa, long lda, int na, const do
         SR_TRY(sr_launch_finalize(fa, s));
     }
     return SR_OK;
+}
+
+extern "C" int sr_gp_last_route(sr_gp_t h, int* out, int cap) {
+    SR_CHECK(h && out && cap >= 1, SR_EINVAL, "sr_gp_last_route: bad argument");
+    const int n = std::min(cap, (int)SR_ROUTE_WORDS);
+    std::copy(h->last_route, h->last_route + n, out);
+    return n;
 }
 
 extern "C" int sr_gp_predict(sr_gp_t h, const double* Xq, long T, double* mu, double* var,

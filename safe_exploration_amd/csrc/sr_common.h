@@ -623,7 +623,8 @@ void sr_stream_plan(int Np, int n_out, int nc, int* g, int* kc, bool can_fuse = 
 #include <vector>
 int sr_stream_items(int Np, int n_out, int nc, int n_cu, bool can_fuse, std::vector<int>& tab, int* nitems, int* nwg);   // rows per run (0: no run kernel)
 #endif
-int sr_launch_stream(sr_stream_args a, int src, hipStream_t s);
+// route != NULL: the launcher notes the kernel form it picked there (SR_ROUTE_* words of include/safereach.h; host side only)
+int sr_launch_stream(sr_stream_args a, int src, hipStream_t s, int* route = nullptr);
 int sr_launch_linearize(const sr_lin_args& a, hipStream_t s);
 int sr_lin_nacc(int D);
 int sr_launch_lin_columns(const sr_lin_args& a, int tq, double* Ks, double* lin_part, hipStream_t s);

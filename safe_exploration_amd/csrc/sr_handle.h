@@ -154,6 +154,7 @@ struct sr_gp {
     int small_path = 1;      // latency paths (streaming T <= 16, 64-tiles, split-K) instead of the plain MFMA tiles
     int last_streamed = 0;   // the last gp_pass went through the streaming kernels (their partials hold U^-T k*)
     int force_stream = 0;    // sr_gp_linearize wants those partials whatever the model size
+    int last_route[SR_ROUTE_WORDS] = {0};   // what the last gp_pass launched (sr_gp_last_route; diagnostics / tests)
     int var_variant = 4;     // 1: the loop of rounds 1 - 4 (LDS-DMA, barrier on top of a k-tile: 70 TF; the A/B reference), 3: the
                              // pipelined loop of round 5 (barrier under the MFMA stream: 73.1 TF), 4: 3 + diagonal blocks without
                              // their structural zeros (default: 74.5 TF)

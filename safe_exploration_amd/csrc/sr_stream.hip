@@ -1006,8 +1006,22 @@ int sr_stream_items(int Np, int n_out, int nc, int n_cu, bool can_fuse, std::vec
     return best_kr;
 }
 
+// host only (tests): the plan a model of these sizes gets on a device of n_cu compute units
+extern "C" int sr_test_stream_plan(int Np, int n_out, int ncols, int n_cu, int can_fuse, int* out) {
+    SR_CHECK(out && Np >= SR_ST_ROWS && Np % SR_ST_ROWS == 0 && n_out >= 1 && ncols >= 5 && ncols <= 128 && n_cu >= 1, SR_EINVAL,
+             "sr_test_stream_plan: bad argument");
+    const int nc = sr_stream_width(ncols);
+    int g = 0, kc = 0, n = 0, nwg = 0;
+    sr_stream_plan(Np, n_out, nc, &g, &kc, can_fuse != 0);
+    std::vector<int> tab;
+    const int kr = sr_stream_items(Np, n_out, nc, n_cu, can_fuse != 0, tab, &n, &nwg);
+    out[0] = g; out[1] = kc; out[2] = kr; out[3] = n; out[4] = nwg;
+    out[5] = kr > 0 ? sr_st_items_rows((Np + SR_ST_COLS - 1) / SR_ST_COLS - 1, kr) : 0;
+    return SR_OK;
+}
+
 // src: 0 columns from a.Ks, 1 ARD-RBF predict columns evaluated in the kernel, 2 ARD-RBF linearize columns
-int sr_launch_stream(sr_stream_args a, int src, hipStream_t s) {
+int sr_launch_stream(sr_stream_args a, int src, hipStream_t s, int* route) {
     a.ncb = (a.Np + SR_ST_COLS - 1) / SR_ST_COLS;
     a.npairs = a.ncb * (a.ncb + 1);
     const int nc = max(sr_stream_width(a.ncols), a.width_min);
@@ -1017,7 +1031,12 @@ int sr_launch_stream(sr_stream_args a, int src, hipStream_t s) {
     static const int epi_env = (int)sr_lab_env("SR_ST_EPI", 1);           // (lab build: A/B of the partial-product stores)
     a.epi = epi_env;
     dim3 grid(a.npairs, a.n_out);
+    if (route) { route[SR_ROUTE_SRC] = src; route[SR_ROUTE_NC] = nc; }
     if (nc <= 4) {
+        if (route) {
+            route[SR_ROUTE_ID] = SR_ROUTE_STREAM1; route[SR_ROUTE_WIDTH] = src == 2 ? 4 : nc;
+            route[SR_ROUTE_POLLED] = a.slots != nullptr;
+        }
         SR_CHECK(src == 0 || (a.D <= 5 && (src == 1 || a.D + 1 <= 4)), SR_EINVAL, "stream: src %d with D = %d", src, a.D);
         if (src == 2) return sr_launch(sr_stream1_kernel<4, 2, 3>, grid, dim3(SR_ST1_THREADS), 0, s, a);
         return sr_pick_le<1, 4>("stream", nc, [&](auto tq) {           // columns per thread
@@ -1031,6 +1050,7 @@ int sr_launch_stream(sr_stream_args a, int src, hipStream_t s) {
     int g, kc;
     sr_stream_plan(a.Np, a.n_out, nc, &g, &kc, src == 1);
     grid.z = nc / (16 * g);
+    if (route) { route[SR_ROUTE_ID] = kc == 1 ? SR_ROUTE_MFMA1 : SR_ROUTE_RUNS; route[SR_ROUTE_WIDTH] = g; route[SR_ROUTE_KC] = kc; }
     SR_CHECK(src == 0 || kc == 1, SR_EINVAL, "stream: columns evaluated in the kernel only for one-chunk work items (runs of %d)", kc);
     if (kc == 1) {
         // (columns evaluated in the kernel: 16 or 32 per workgroup only -- every column block re-evaluates the chunk's rows,
@@ -1051,6 +1071,11 @@ int sr_launch_stream(sr_stream_args a, int src, hipStream_t s) {
              (a.nwg == a.nitems || g == 4), SR_EINVAL, "stream: no work-item table (sr_stream_items)");
     const int nitems = a.nitems;
     grid.x = a.nwg;
+    if (route) {
+        route[SR_ROUTE_KR] = a.kr; route[SR_ROUTE_NITEMS] = nitems; route[SR_ROUTE_NWG] = a.nwg;
+        route[SR_ROUTE_MULTI] = g == 4 && a.nwg < nitems;
+        route[SR_ROUTE_REDUCE] = sr_st_items_rows(a.ncb - 1, a.kr);
+    }
     SR_TRY((sr_pick_eq<1, 2, 4, 8>("stream: %d groups of 16 columns per workgroup", g, [&](auto gc) {
         constexpr int G = decltype(gc)::value;
         if constexpr (G == 4) {

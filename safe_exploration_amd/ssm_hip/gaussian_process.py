@@ -1569,6 +1569,22 @@ class SimpleGPModel(StateSpaceModel):
         self._need_trained()
         return int(lib.sr_gp_fact_pipelined(self._handle.h))
 
+    ROUTE_WORDS = ("route", "src", "width", "nc", "kc", "kr", "nitems", "nwg", "multi", "reduce_items", "polled", "nsplit",
+                   "bal_wgs", "final", "unslid", "T")
+    ROUTE_NAMES = (None, "K0", "stream1", "mfma1", "runs", "K2s", "K2b", "K2m", "K2")
+
+    def last_route(self):
+        """which kernels the last posterior pass launched (sr_gp_last_route): a dict of ROUTE_WORDS, "route" by name
+        (ROUTE_NAMES; None before the first pass).  Diagnostics: tests use it to know which kernel form they met."""
+        self._need_trained()
+        out = (ctypes.c_int * len(self.ROUTE_WORDS))()
+        n = lib.sr_gp_last_route(self._handle.h, out, len(out))
+        if n != len(out):
+            check(n if n < 0 else -1)
+        d = dict(zip(self.ROUTE_WORDS, (int(v) for v in out)))
+        d["route"] = self.ROUTE_NAMES[d["route"]]
+        return d
+
     def get_forward_model_casadi(self, linearize_mu=True):
         """state_space_models.py:140-166.  The evaluator calls the model once per IPOPT callback and blocks: the resident
         single-query server is armed for it (``start_server``; SR_NO_SERVER=1 in the environment keeps the launched
