@@ -576,6 +576,34 @@ enum { SR_ROUTE_ID = 0, SR_ROUTE_SRC, SR_ROUTE_WIDTH, SR_ROUTE_NC, SR_ROUTE_KC, 
        SR_ROUTE_T };
 enum { SR_ROUTE_K0 = 1, SR_ROUTE_STREAM1, SR_ROUTE_MFMA1, SR_ROUTE_RUNS, SR_ROUTE_K2S, SR_ROUTE_K2B, SR_ROUTE_K2M, SR_ROUTE_K2 };
 int sr_gp_last_route(sr_gp_t h, int* out, int cap);
+/* diagnostic: how the last model update of h ran -- the last sr_gp_factorize (a sparse fit's factorisation counts too) or the
+ * last sr_gp_append / sr_gp_append1_host that succeeded.  Host state only: plain ints the two drivers fill; no kernel, launch or
+ * stream depends on them.  Fills out[0 .. min(cap, SR_UPDATE_WORDS)) and returns the words written (SR_EINVAL for a NULL
+ * argument or cap < 1):
+ *   [SR_UPD_KIND]        0 no update yet, SR_UPD_FIT, SR_UPD_APPEND
+ *  after a fit:
+ *   [SR_UPD_NB]          blocks of 128 padded rows
+ *   [SR_UPD_PANEL]       blocks per Cholesky panel
+ *   [SR_UPD_REGIME]      stream regime: 1 chain-bound, 2 two bulk streams
+ *   [SR_UPD_OWN_STREAMS] 1 = the update's own streams beside the caller's, 0 = every launch on the caller's stream
+ *   [SR_UPD_NPAR]        outputs factorised at once
+ *   [SR_UPD_ROUNDS]      rounds of SR_UPD_NPAR outputs
+ *   [SR_UPD_INV_STAGES]  stages of the triangular inversion launched beside the chain (per round)
+ *   [SR_UPD_FORM]        SR_UPD_PLAIN one chain of launches, SR_UPD_PIPELINED, SR_UPD_FLOW
+ *  after an append (the same word positions, other meanings):
+ *   [SR_UPD_ROUTE]       SR_UPD_SMALL the matrix-vector route (<= 16 points), SR_UPD_ONE_WG one launch of one workgroup per
+ *                        output, SR_UPD_GRID one launch of a grid of workgroups, SR_UPD_TILE the MFMA-tile route (17 .. 128)
+ *   [SR_UPD_IN_PLACE]    1 = written into the model's own buffers (the views slide one step)
+ *   [SR_UPD_NP0], [SR_UPD_NP1]  padded size before and after
+ *   [SR_UPD_SPARE]       1 = the new U^-1 went into the spare buffer kept from an earlier append */
+#define SR_UPDATE_WORDS 9
+enum { SR_UPD_KIND = 0, SR_UPD_NB, SR_UPD_PANEL, SR_UPD_REGIME, SR_UPD_OWN_STREAMS, SR_UPD_NPAR, SR_UPD_ROUNDS,
+       SR_UPD_INV_STAGES, SR_UPD_FORM };
+enum { SR_UPD_ROUTE = 1, SR_UPD_IN_PLACE, SR_UPD_NP0, SR_UPD_NP1, SR_UPD_SPARE };
+enum { SR_UPD_FIT = 1, SR_UPD_APPEND };
+enum { SR_UPD_PLAIN = 0, SR_UPD_PIPELINED, SR_UPD_FLOW };
+enum { SR_UPD_SMALL = 0, SR_UPD_ONE_WG, SR_UPD_GRID, SR_UPD_TILE };
+int sr_gp_last_update(sr_gp_t h, int* out, int cap);
 /* host only: the plan of the streamed MFMA route (csrc/sr_stream.hip) for a model of Np padded rows and n_out outputs, ncols
  * queries (5 .. 128, or 1 .. 4 widened to 16 as the 2 .. 4-query route does: pass 16) on a device of n_cu compute units;
  * can_fuse != 0: the kernel may evaluate its own K* rows (ARD-RBF, D <= 5).  out[0..5] = groups of 16 columns per workgroup,

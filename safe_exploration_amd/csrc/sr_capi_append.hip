@@ -65,6 +65,13 @@ static void grid_append_aborted(sr_gp* h) {
     ++h->grid_aborts_row;
 }
 static bool append1_fused(const sr_gp* h, int m) { return append1_route(h, m) != 0; }
+// sr_gp_last_update: how an append that has just been committed ran (host state only)
+static void note_append(sr_gp* h, int route, bool in_place, int Np0, int Np1, bool spare) {
+    int* lu = h->last_update;
+    std::fill(lu, lu + SR_UPDATE_WORDS, 0);
+    lu[SR_UPD_KIND] = SR_UPD_APPEND; lu[SR_UPD_ROUTE] = route; lu[SR_UPD_IN_PLACE] = in_place ? 1 : 0;
+    lu[SR_UPD_NP0] = Np0; lu[SR_UPD_NP1] = Np1; lu[SR_UPD_SPARE] = spare ? 1 : 0;
+}
 // workgroups per output of the grid route: all of them must be resident at once (they wait for each other) and one fits a
 // CU, so the grid leaves an eighth of the CUs to whatever else is resident on the device (the single-query servers of other
 // models: a few workgroups); and no more workgroups than there is work for
@@ -163,6 +170,7 @@ static int append1_slide(sr_gp* h, const double* Znew, const double* Ynew, hipSt
     ++h->slide;
     h->N = N0 + 1;
     h->logdet_host = ld; h->logdet_valid = 1;
+    note_append(h, SR_UPD_GRID, true, Np0, Np0, false);
     return SR_OK;
 }
 
@@ -382,6 +390,7 @@ static int append_small(sr_gp* h, const double* Znew, const double* Ynew, int m,
         h->Np = Np1;
         drop_np_sized(h);
     }
+    note_append(h, route == 2 ? SR_UPD_GRID : (route == 1 ? SR_UPD_ONE_WG : SR_UPD_SMALL), false, Np0, Np1, reuse_alt);
     return SR_OK;
 }
 
@@ -542,5 +551,6 @@ extern "C" int sr_gp_append(sr_gp_t h, const double* Znew, const double* Ynew, i
         h->Np = Np1;
         drop_np_sized(h);
     }
+    note_append(h, SR_UPD_TILE, false, Np0, Np1, reuse_alt);
     return SR_OK;
 }

@@ -409,6 +409,13 @@ static int factorize_impl(sr_gp* h, void* stream, int* info, const sr_fact_src* 
         SR_FH(hipStreamWaitEvent(sr, h->fact_fork, 0));
     }
     h->last_fact_pipe = pipe ? 1 : (flow ? 4 : 0);
+    {   // sr_gp_last_update: how this update runs (host state only)
+        int* lu = h->last_update;
+        std::fill(lu, lu + SR_UPDATE_WORDS, 0);
+        lu[SR_UPD_KIND] = SR_UPD_FIT; lu[SR_UPD_NB] = nb; lu[SR_UPD_PANEL] = P; lu[SR_UPD_REGIME] = regime;
+        lu[SR_UPD_OWN_STREAMS] = own_streams ? 1 : 0; lu[SR_UPD_NPAR] = n_par; lu[SR_UPD_ROUNDS] = (h->n_out + n_par - 1) / n_par;
+        lu[SR_UPD_FORM] = pipe ? SR_UPD_PIPELINED : (flow ? SR_UPD_FLOW : SR_UPD_PLAIN);
+    }
     unsigned flow_ep = 0;
     // a wait of the tile flow that lasts longer gives up.  It grows with the size of the update: the FIRST update on fresh
     // scratch memory of many gigabytes can stand still for seconds (page-table work inside the first kernels: 4.0 - 4.8 s for
@@ -468,6 +475,7 @@ static int factorize_impl(sr_gp* h, void* stream, int* info, const sr_fact_src* 
         const sr_batch b_inv1{nd, sP, sP, sP, 0};         // inversion, product 1: (W, W) -> U
         const sr_batch b_inv2{nd, sN, sP, sP, sN};        // inversion, product 2: (Wt, U) -> W, Wt
         int n_bulk = 0;                                   // bulk updates issued so far (event ping-pong)
+        int inv_stages = 0;                               // stages of the inversion launched beside the chain (sr_gp_last_update)
         // Early inversion (chain-bound sizes): once the chain has passed the middle block, the root's LEFT subtree of the
         // inversion and the root's first product need nothing the Cholesky still writes (factor rows above the middle,
         // their diagonal-block inverses; results go to W / Wt inside the left half and to U's unused lower-left block).
@@ -586,6 +594,7 @@ static int factorize_impl(sr_gp* h, void* stream, int* info, const sr_fact_src* 
                 for (int X = nb / 2; X < nb;) {
                     SR_F(sr_launch_flow_gate(h->flow_flags, flow_ep, nd, nb, X, flow_timeout_s, finv));
                     SR_F(inv_stage(X, finv, false));
+                    ++inv_stages;
                     const int nxt = (X + nb) / 2;
                     if (nb - nxt < 3 || nxt <= X) break;
                     X = nxt;
@@ -637,6 +646,7 @@ static int factorize_impl(sr_gp* h, void* stream, int* info, const sr_fact_src* 
                     SR_FH(hipEventRecord(h->ev_inv[0], sc));
                     SR_FH(hipStreamWaitEvent(si, h->ev_inv[0], 0));
                     SR_F(inv_stage(kb, si, false));
+                    ++inv_stages;
                     SR_FH(hipEventRecord(h->ev_inv[1], si));
                     inv_trigger = nb + 1;                              // (the prototype keeps to one stage)
                 }
@@ -742,6 +752,7 @@ static int factorize_impl(sr_gp* h, void* stream, int* info, const sr_fact_src* 
                 SR_FH(hipEventRecord(h->ev_inv[0], sc));
                 SR_FH(hipStreamWaitEvent(si, h->ev_inv[0], 0));
                 SR_F(inv_stage(p1, si, false));
+                ++inv_stages;
                 SR_FH(hipEventRecord(h->ev_inv[1], si));
                 while (inv_trigger <= p1) {
                     const int nxt_t = (inv_trigger + nb) / 2;
@@ -798,6 +809,7 @@ static int factorize_impl(sr_gp* h, void* stream, int* info, const sr_fact_src* 
         // (ensure_inv_jobs).  The diagonal blocks of W / Wt were written by sr_potrf_diag_kernel.
         if (early_done) SR_FH(hipStreamWaitEvent(sc, h->ev_inv[1], 0));
         SR_F(inv_stage(nb, sc, true));                    // whatever the stages have left
+        h->last_update[SR_UPD_INV_STAGES] = inv_stages;
         // alpha = Wt (W y)   (v behind W in the scratch)
         const double* rhs = src ? src->rhs : h->yT;
         if (rhs) {
@@ -880,6 +892,13 @@ extern "C" int sr_gp_set_fact_pipeline(sr_gp_t h, int on) {
 }
 
 extern "C" int sr_gp_fact_pipelined(sr_gp_t h) { return h ? h->last_fact_pipe : 0; }
+
+extern "C" int sr_gp_last_update(sr_gp_t h, int* out, int cap) {
+    SR_CHECK(h && out && cap >= 1, SR_EINVAL, "sr_gp_last_update: bad argument");
+    const int n = std::min(cap, (int)SR_UPDATE_WORDS);
+    std::copy(h->last_update, h->last_update + n, out);
+    return n;
+}
 
 extern "C" int sr_test_flow_fail(int n) {
     // n > 0: the next n tile-flow updates of this process fail on the device (see sr_gp_factorize); n = 0: forget that one did

@@ -1585,6 +1585,30 @@ class SimpleGPModel(StateSpaceModel):
         d["route"] = self.ROUTE_NAMES[d["route"]]
         return d
 
+    UPDATE_FIT_WORDS = ("kind", "nb", "panel", "regime", "own_streams", "n_par", "rounds", "inv_stages", "form")
+    UPDATE_APPEND_WORDS = ("kind", "route", "in_place", "Np0", "Np1", "spare")
+    UPDATE_KINDS = (None, "fit", "append")
+    UPDATE_FORMS = ("plain", "pipelined", "flow")
+    UPDATE_ROUTES = ("small", "one_wg", "grid", "tile")
+
+    def last_update(self):
+        """how the last model update ran (sr_gp_last_update): a dict of UPDATE_FIT_WORDS after a fit ("form" by name), of
+        UPDATE_APPEND_WORDS after an append ("route" by name); "kind" is "fit" / "append".  Diagnostics."""
+        self._need_trained()
+        out = (ctypes.c_int * len(self.UPDATE_FIT_WORDS))()
+        n = lib.sr_gp_last_update(self._handle.h, out, len(out))
+        if n != len(out):
+            check(n if n < 0 else -1)
+        kind = self.UPDATE_KINDS[int(out[0])]
+        if kind == "append":
+            d = dict(zip(self.UPDATE_APPEND_WORDS, (int(v) for v in out)))
+            d["route"] = self.UPDATE_ROUTES[d["route"]]
+        else:
+            d = dict(zip(self.UPDATE_FIT_WORDS, (int(v) for v in out)))
+            d["form"] = self.UPDATE_FORMS[d["form"]]
+        d["kind"] = kind
+        return d
+
     def get_forward_model_casadi(self, linearize_mu=True):
         """state_space_models.py:140-166.  The evaluator calls the model once per IPOPT callback and blocks: the resident
         single-query server is armed for it (``start_server``; SR_NO_SERVER=1 in the environment keeps the launched

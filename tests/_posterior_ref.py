@@ -74,11 +74,11 @@ class Problem(object):
     every point, centres (c, D), base (D,) base lengthscales, ls (n_out, D), sf2 (n_out,), kern, nugget (n_out,), hyp
     (the list SimpleGPModel takes)."""
 
-    def __init__(self, seed, N, D, n_out, kern="rbf"):
+    def __init__(self, seed, N, D, n_out, kern="rbf", max_clusters=128):
         assert kern in ("rbf", "mat52")
         rng = np.random.default_rng(seed)
         c = -(-N // CLUSTER)
-        assert 1 <= c <= 128, "N = %d needs %d clusters (> 128)" % (N, c)
+        assert 1 <= c <= max_clusters, "N = %d needs %d clusters (> %d)" % (N, c, max_clusters)
         self.seed, self.N, self.D, self.n_out, self.kern, self.c = seed, N, D, n_out, kern, c
         self.base = rng.uniform(0.6, 1.6, D)
         self.ls = self.base[None, :] * rng.uniform(0.85, 1.2, (n_out, D))
