@@ -294,6 +294,19 @@ int sr_moment_step(int device, long T, int n_s, int n_u, int mode, const double*
  * SR_EINVAL NULL argument or T < 0; T == 0 is a no-op. */
 int sr_gp_moment_match(sr_gp_t h, const double* m, const double* S, long T, const double* inv_k,
                        double* mu, double* cov, double* V, void* stream);
+/* Its reverse pass (vector-Jacobian product): for seeds mu_bar T x n_out, cov_bar T x n_out x n_out, V_bar T x n_out x D (any of
+ * them NULL = zero, with the same bits as a zero array) the derivatives of
+ *   L = sum_t mu_bar[t] . mu[t] + sum_ab cov_bar[t]_ab cov[t]_ab + sum_a V_bar[t]_a . V[t]_a
+ * in the inputs:  m_bar T x D = dL/dm ; S_bar T x D x D = dL/dS (either may be NULL, not both).  m, S (NULL = zero) and inv_k as
+ * above.  Only the symmetric part of cov_bar counts.  S_bar is exactly symmetric: the gradient of the function extended to
+ * unsymmetric arguments by S -> (S + S^T) / 2 (what autograd gives when the forward symmetrises).  The clip of the covariance
+ * diagonal at 1e-15 is ignored by the derivative, and so is the exact zero the forward writes off the diagonal at S == 0:
+ * d cov_ab / dS is not zero there, so the pair sums run for every pair.  Nothing inverts S: singular and zero S are fine.
+ * Cost: T n_out^2 N^2 evaluations of exp (about four forward calls); chunks, scratch, determinism (the same bits for any
+ * chunk size) and refusals as sr_gp_moment_match; SR_EINVAL also when both outputs are NULL.  Asynchronous on `stream`. */
+int sr_gp_moment_match_vjp(sr_gp_t h, const double* m, const double* S, long T, const double* inv_k,
+                           const double* mu_bar, const double* cov_bar, const double* V_bar,
+                           double* m_bar, double* S_bar, void* stream);
 
 /* replaces: utils.compute_remainder_overapproximations  utils.py:108-144 (batched)
  * q T x n_s x n_s, k_fb T x n_u x n_s -> u_mu T x n_s, u_sigma T x n_s */

@@ -337,6 +337,36 @@ extern "C" int sr_gp_moment_match(sr_gp_t h, const double* m, const double* S, l
     return SR_OK;
 }
 
+// the reverse pass of sr_gp_moment_match: the same refusals in the same order, the same scratch (its own per-query size)
+extern "C" int sr_gp_moment_match_vjp(sr_gp_t h, const double* m, const double* S, long T, const double* inv_k,
+                                      const double* mu_bar, const double* cov_bar, const double* V_bar, double* m_bar,
+                                      double* S_bar, void* stream) {
+    SR_CHECK(h != nullptr, SR_EINVAL, "sr_gp_moment_match_vjp: NULL handle");
+    SR_CHECK(h->factorized, SR_ESTATE, "sr_gp_moment_match_vjp: model not factorized");
+    if (h->general) {
+        sr_set_error("sr_gp_moment_match_vjp: the closed form is for ARD-RBF models only (data set with sr_gp_set_data)");
+        return SR_EUNSUPPORTED;
+    }
+    SR_CHECK(T >= 0, SR_EINVAL, "sr_gp_moment_match_vjp: T=%ld", T);
+    if (T == 0) return SR_OK;
+    SR_CHECK(m && inv_k && (m_bar || S_bar), SR_EINVAL, "sr_gp_moment_match_vjp: NULL argument");
+    hipStream_t s = (hipStream_t)stream;
+    SR_DEVICE(h->device);
+    const long per = sr_mmg_ws_per_query(h->N, h->D, h->n_out);
+    const long chunk = std::max(1L, std::min({h->chunk, sr_mmg_max_queries(h->N, h->n_out), ((long)1 << 28) / per}));
+    const long Dl = h->D, DD = Dl * Dl, n = h->n_out;
+    SR_TRY(h->mm_ws.grow((size_t)(std::min(chunk, T) * per), wait::stream(s)));
+    for (long t0 = 0; t0 < T; t0 += chunk) {
+        const long Tc = std::min(chunk, T - t0);
+        SR_TRY(sr_launch_moment_match_vjp(h->Z, h->alpha, h->ls, h->sf2, h->N, h->Np, h->D, h->n_out, m + t0 * Dl,
+                                          S ? S + t0 * DD : nullptr, Tc, inv_k, mu_bar ? mu_bar + t0 * n : nullptr,
+                                          cov_bar ? cov_bar + t0 * n * n : nullptr, V_bar ? V_bar + t0 * n * Dl : nullptr,
+                                          m_bar ? m_bar + t0 * Dl : nullptr, S_bar ? S_bar + t0 * DD : nullptr,
+                                          h->mm_ws.get(), s));
+    }
+    return SR_OK;
+}
+
 extern "C" int sr_moment_step(int device, long T, int n_s, int n_u, int mode, const double* mu_x,
                               const double* sigma_x, const double* k_ff, const double* k_fb, const double* mu_g,
                               const double* var_g, const double* jac_g, const double* a, const double* b,

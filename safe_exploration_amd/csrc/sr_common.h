@@ -184,6 +184,14 @@ long sr_mm_max_queries(int N, int n_out);
 int sr_launch_moment_match(const double* Z, const double* alpha, const double* ls, const double* sf2, int N, int Np, int D,
                            int n_out, const double* m, const double* S, long T, const double* inv_k, double* mu,
                            double* cov, double* V, double* ws, hipStream_t s);
+// its reverse pass: m_bar (T x D) and S_bar (T x D x D, exactly symmetric; either may be NULL) from the seeds mu_bar, cov_bar,
+// V_bar (NULL = zero); one chunk of T <= sr_mmg_max_queries queries, ws: T x sr_mmg_ws_per_query doubles
+long sr_mmg_ws_per_query(int N, int D, int n_out);
+long sr_mmg_max_queries(int N, int n_out);
+int sr_launch_moment_match_vjp(const double* Z, const double* alpha, const double* ls, const double* sf2, int N, int Np,
+                               int D, int n_out, const double* m, const double* S, long T, const double* inv_k,
+                               const double* mu_bar, const double* cov_bar, const double* V_bar, double* m_bar,
+                               double* S_bar, double* ws, hipStream_t s);
 int sr_launch_fill(double* p, size_t n, double v, hipStream_t s);
 // Wt = J U^T J from the factor as the model update leaves it (diagonal 128-blocks in U, block rows in W; sr_sparse.hip);
 // nbatch members, U / W sS and Wt sD doubles apart

@@ -135,7 +135,8 @@ struct sr_gp {
     // partial rows | taken marks]
     srh::scratch<double> sel_L, sel_ws;
     // sr_gp_moment_match: per query of a chunk the D x D algebra of every output and pair of outputs, and the row tiles'
-    // partial sums of the double sum (sr_mm_ws_per_query doubles each)
+    // partial sums of the double sum (sr_mm_ws_per_query doubles each); sr_gp_moment_match_vjp: the same records, mu, V, the
+    // contribution records and the row tiles' sums (sr_mmg_ws_per_query doubles each)
     srh::scratch<double> mm_ws;
     // sr_gp_remove: per output the coefficient tables of the retired row (3 Np + 4), then the input rows behind it
     srh::scratch<double> rm_ws;

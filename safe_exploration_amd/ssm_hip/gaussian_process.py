@@ -158,6 +158,27 @@ class _Handle(object):
         return io["h_out_np"][:k].copy()
 
 
+class _MomentMatchFn(torch.autograd.Function):
+    """``SimpleGPModel.moment_match_device(m, S, differentiable=True)``: the forward is the plain call, the backward
+    ``moment_match_vjp_device`` at the saved inputs.  Seeds of outputs nobody used arrive as None (= zero, the same bits)."""
+
+    @staticmethod
+    def forward(ctx, model, m, S):
+        mu, cov, V = model.moment_match_device(m, S)
+        hd = model._handle
+        ctx.model = model
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(B.as_dev(m, hd.device), None if S is None else B.as_dev(S, hd.device))
+        return mu, cov, V
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, mu_bar, cov_bar, V_bar):
+        m, S = ctx.saved_tensors
+        m_bar, S_bar = ctx.model.moment_match_vjp_device(m, S, mu_bar, cov_bar, V_bar)
+        return None, m_bar, (None if S is None else S_bar)
+
+
 class SimpleGPModel(StateSpaceModel):
     """GP dynamics model x_{t+1} - prior(x_t,u_t) ~ GP, one output per state dimension.
 
@@ -891,11 +912,7 @@ class SimpleGPModel(StateSpaceModel):
             self._inv_K_dev = t
         return self._inv_K_dev
 
-    def moment_match_device(self, m, S=None):
-        """Exact moment matching on device tensors (``sr_gp_moment_match``): the GP at T Gaussian inputs z ~ N(m[t], S[t]).
-        m (T, D); S (T, D, D) symmetric PSD (may be singular) or None = point inputs.
-        Returns mu (T, n), cov (T, n, n) -- the full covariance across outputs -- and V (T, n, D) with cov(z, g_a) = S V_a
-        (V -> the mean Jacobian as S -> 0).  ARD-RBF models only (NotImplementedError otherwise).  Asynchronous."""
+    def _mm_inputs(self, m, S):
         self._need_trained()
         if any(kt != "rbf" for kt in self.kern_types):
             raise NotImplementedError("moment matching: the closed form is for ARD-RBF models only")
@@ -905,12 +922,47 @@ class SimpleGPModel(StateSpaceModel):
             raise ValueError("m must be (T, {})".format(hd.D))
         T = tm.shape[0]
         tS = B.as_dev(S, hd.device, (T, hd.D, hd.D)) if S is not None else None
+        return hd, tm, tS, T
+
+    def moment_match_device(self, m, S=None, differentiable=False):
+        """Exact moment matching on device tensors (``sr_gp_moment_match``): the GP at T Gaussian inputs z ~ N(m[t], S[t]).
+        m (T, D); S (T, D, D) symmetric PSD (may be singular) or None = point inputs.
+        Returns mu (T, n), cov (T, n, n) -- the full covariance across outputs -- and V (T, n, D) with cov(z, g_a) = S V_a
+        (V -> the mean Jacobian as S -> 0).  ARD-RBF models only (NotImplementedError otherwise).  Asynchronous.
+        ``differentiable=True``: the same three tensors (the same bits), hanging on a ``torch.autograd.Function`` whose
+        backward is ``moment_match_vjp_device`` (once differentiable; gradients in m and S, not in the model)."""
+        if differentiable:
+            return _MomentMatchFn.apply(self, m, S)
+        hd, tm, tS, T = self._mm_inputs(m, S)
         kinv = self.inv_K_device()
         mu, cov = B.empty((T, hd.n_out), hd.device), B.empty((T, hd.n_out, hd.n_out), hd.device)
         V = B.empty((T, hd.n_out, hd.D), hd.device)
         check(lib.sr_gp_moment_match(hd.h, B.ptr(tm), B.ptr(tS), T, B.ptr(kinv), B.ptr(mu), B.ptr(cov), B.ptr(V),
                                      B.stream_ptr(hd.device)))
         return mu, cov, V
+
+    def moment_match_vjp_device(self, m, S, mu_bar=None, cov_bar=None, V_bar=None):
+        """Reverse pass of ``moment_match_device`` (``sr_gp_moment_match_vjp``): for seeds mu_bar (T, n), cov_bar (T, n, n),
+        V_bar (T, n, D) (None = zero) the derivatives m_bar (T, D) and S_bar (T, D, D) of
+        sum(mu_bar * mu) + sum(cov_bar * cov) + sum(V_bar * V) in m and S (S None = zero; S_bar is returned all the same: it is
+        not zero there).  S_bar is exactly symmetric; the clip of the covariance diagonal is ignored.  Asynchronous."""
+        hd, tm, tS, T = self._mm_inputs(m, S)
+        n, D = hd.n_out, hd.D
+        seeds = [None if x is None else B.as_dev(x, hd.device, shp)
+                 for x, shp in ((mu_bar, (T, n)), (cov_bar, (T, n, n)), (V_bar, (T, n, D)))]
+        kinv = self.inv_K_device()
+        m_bar, S_bar = B.empty((T, D), hd.device), B.empty((T, D, D), hd.device)
+        check(lib.sr_gp_moment_match_vjp(hd.h, B.ptr(tm), B.ptr(tS), T, B.ptr(kinv), B.ptr(seeds[0]), B.ptr(seeds[1]),
+                                         B.ptr(seeds[2]), B.ptr(m_bar), B.ptr(S_bar), B.stream_ptr(hd.device)))
+        return m_bar, S_bar
+
+    def predict_uncertain_vjp(self, mean, cov=None, mu_bar=None, cov_bar=None, V_bar=None):
+        """NumPy form of ``moment_match_vjp_device``: mean (T, D) or (D,), cov (T, D, D) or (D, D) or None, seeds shaped
+        as the outputs of ``predict_uncertain`` -> m_bar (T, D), S_bar (T, D, D)."""
+        mean = np.atleast_2d(np.asarray(mean, dtype=np.float64))
+        if cov is not None:
+            cov = np.asarray(cov, dtype=np.float64).reshape(mean.shape[0], mean.shape[1], mean.shape[1])
+        return tuple(B.to_numpy(o) for o in self.moment_match_vjp_device(mean, cov, mu_bar, cov_bar, V_bar))
 
     def predict_uncertain(self, mean, cov=None):
         """NumPy form of ``moment_match_device``: mean (T, D) or (D,), cov (T, D, D) or (D, D) or None

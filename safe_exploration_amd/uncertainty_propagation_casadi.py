@@ -154,9 +154,10 @@ multi_step_taylor_symbolic = multi_step_taylor      # the reference's name (unce
 
 
 # ---------------------------------------------------------------------------------------------- exact moment matching
-def _mm_step(ssm, mu, sigma, kff, K, ta, tb, tz):
+def _mm_step(ssm, mu, sigma, kff, K, ta, tb, tz, differentiable=False):
     """One exact step on device tensors: mu (T,n_s), sigma (T,n_s,n_s) or None, kff (T,n_u), K (T,n_u,n_s) or None (= 0),
-    tz (n_x_in,n_s).  The control is u = K x + k_ff.  Returns mu_new, sigma_new, Cov of the GP outputs."""
+    tz (n_x_in,n_s).  The control is u = K x + k_ff.  Returns mu_new, sigma_new, Cov of the GP outputs.
+    differentiable: the GP call keeps the autograd graph (``moment_match_device(differentiable=True)``)."""
     T, n_s = mu.shape
     zx = mu.matmul(tz.t())
     if K is None:
@@ -168,7 +169,7 @@ def _mm_step(ssm, mu, sigma, kff, K, ta, tb, tz):
         zu = kff + K.matmul(mu.unsqueeze(2)).squeeze(2)
         G = torch.cat((tz.expand(T, -1, -1), K), dim=1)
     S = None if sigma is None else G.matmul(sigma).matmul(G.transpose(1, 2))
-    mu_g, cov, V = ssm.moment_match_device(torch.cat((zx, zu), dim=1), S)
+    mu_g, cov, V = ssm.moment_match_device(torch.cat((zx, zu), dim=1), S, differentiable=differentiable)
     mu_new = A.matmul(mu.unsqueeze(2)).squeeze(2) + kff.matmul(tb.t()) + mu_g
     if sigma is None:
         return mu_new, cov, cov
@@ -193,12 +194,15 @@ def _mm_setup(ssm, a, b, a_gp_inp_x):
     return dev, n_s, n_u, B.const_dev(a, dev, (n_s, n_s)), B.const_dev(b, dev, (n_s, n_u)), B.const_dev(tzn, dev, tzn.shape)
 
 
-def moment_matching_batch(mu_0, ssm, k_ff, k_fb, a=None, b=None, sigma_0=None, a_gp_inp_x=None):
+def moment_matching_batch(mu_0, ssm, k_ff, k_fb, a=None, b=None, sigma_0=None, a_gp_inp_x=None, differentiable=False):
     """Exact moment matching for T trajectories x H steps.  mu_0 (T,n_s); k_ff (T,H,n_u); k_fb (T,H-1,n_u,n_s) (step 0 has
     no feedback, step i >= 1 uses k_fb[:, i-1]); sigma_0 (T,n_s,n_s) or None (a point).
     Returns mu_all (T,H,n_s), sigma_all (T,H,n_s,n_s), gp_cov_all (T,H,n_s,n_s) (the GP's full output covariance).
     H calls of ``sr_gp_moment_match`` with the small algebra in batched torch ops; nothing synchronises between steps.
-    Device tensors in -> device tensors out."""
+    Device tensors in -> device tensors out.
+    differentiable=True: the autograd graph is kept from mu_0, sigma_0, k_ff and k_fb (device tensors that require grad) to the
+    three results: every GP call hangs on ``sr_gp_moment_match_vjp`` and the steps are stacked, not written into a buffer.
+    The values are those of the plain call."""
     dev, n_s, n_u, ta, tb, tz = _mm_setup(ssm, a, b, a_gp_inp_x)
     as_t = B.is_tensor(mu_0)
     mu = B.as_dev(mu_0, dev)
@@ -209,6 +213,13 @@ def moment_matching_batch(mu_0, ssm, k_ff, k_fb, a=None, b=None, sigma_0=None, a
     H = kff.shape[1]
     kfb = B.as_dev(k_fb, dev, (T, H - 1, n_u, n_s)) if H > 1 else None
     sigma = B.as_dev(sigma_0, dev, (T, n_s, n_s)) if sigma_0 is not None else None
+    if differentiable:
+        steps = []
+        for i in range(H):
+            mu, sigma, cov = _mm_step(ssm, mu, sigma, kff[:, i], None if i == 0 else kfb[:, i - 1], ta, tb, tz, True)
+            steps.append((mu, sigma, cov))
+        outs = tuple(torch.stack([st[k] for st in steps], dim=1) for k in range(3))
+        return outs if as_t else tuple(B.to_numpy(o.detach()) for o in outs)
     mu_all, sigma_all = B.empty((T, H, n_s), dev), B.empty((T, H, n_s, n_s), dev)
     cov_all = B.empty((T, H, n_s, n_s), dev)
     for i in range(H):
