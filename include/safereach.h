@@ -617,6 +617,18 @@ enum { SR_UPD_FIT = 1, SR_UPD_APPEND };
 enum { SR_UPD_PLAIN = 0, SR_UPD_PIPELINED, SR_UPD_FLOW };
 enum { SR_UPD_SMALL = 0, SR_UPD_ONE_WG, SR_UPD_GRID, SR_UPD_TILE };
 int sr_gp_last_update(sr_gp_t h, int* out, int cap);
+/* diagnostic: how sr_gp_remove retired its LAST point (host state only: no kernel or launch depends on it).  Fills
+ * out[0 .. min(cap, SR_REMOVE_WORDS)), returns the words written (SR_EINVAL: NULL argument, cap < 1):
+ *   [SR_RM_COUNT] points retired since the last fit (0: the other words are stale)   [SR_RM_NP0], [SR_RM_NP1] padded size before / after
+ *   [SR_RM_OFF0] front padding before   [SR_RM_Q] padded index retired   [SR_RM_SLIDE] slide of the source view (sr_gp_slide_steps)
+ *   [SR_RM_ALIGNED] rows kernel: 1 32-byte loads, 0 the 8-byte instance   [SR_RM_SPARE] the factor went into SR_RM_SPARE_NONE a fresh
+ *   allocation, _AS_IS the spare buffer as it lay, _CLEARED the spare buffer zeroed first   [SR_RM_VEC_SPARE] 1 = spare alpha / target vectors
+ *   reused   [SR_RM_CLEAN] 1 = sr_remove_clean_kernel ran on the slid source's allocation   [SR_RM_KEPT_OLD] 1 = the old buffers became the spares */
+#define SR_REMOVE_WORDS 11
+enum { SR_RM_COUNT = 0, SR_RM_NP0, SR_RM_NP1, SR_RM_OFF0, SR_RM_Q, SR_RM_SLIDE, SR_RM_ALIGNED, SR_RM_SPARE, SR_RM_VEC_SPARE, SR_RM_CLEAN,
+       SR_RM_KEPT_OLD };
+enum { SR_RM_SPARE_NONE = 0, SR_RM_SPARE_AS_IS, SR_RM_SPARE_CLEARED };
+int sr_gp_last_remove(sr_gp_t h, int* out, int cap);
 /* host only: the plan of the streamed MFMA route (csrc/sr_stream.hip) for a model of Np padded rows and n_out outputs, ncols
  * queries (5 .. 128, or 1 .. 4 widened to 16 as the 2 .. 4-query route does: pass 16) on a device of n_cu compute units;
  * can_fuse != 0: the kernel may evaluate its own K* rows (ARD-RBF, D <= 5).  out[0..5] = groups of 16 columns per workgroup,

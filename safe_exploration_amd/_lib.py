@@ -126,6 +126,7 @@ SIGNATURES = {
     "sr_gp_slide_steps": (_I, [_H, _PI]),
     "sr_gp_last_route": (_I, [_H, _PI, _I]),
     "sr_gp_last_update": (_I, [_H, _PI, _I]),
+    "sr_gp_last_remove": (_I, [_H, _PI, _I]),
     "sr_test_stream_plan": (_I, [_I, _I, _I, _I, _I, _PI]),
     "sr_prof_enable": (_I, [_H, _I]),
     "sr_prof_reset": (_I, [_H]),

@@ -58,12 +58,21 @@ static int remove_one(sr_gp* h, int j, hipStream_t s) {
     // (behind the launches that read the views; a failure here costs the spare buffers only: they are dropped below)
     const bool keep_old = same && (size_t)n_out * NN0 * sizeof(double) <= SR_FACT_PAR_BYTES * 2;
     bool cleaned = slide0 == 0;
-    if (slide0 > 0 && keep_old && h->slack_ok)
+    const bool clean_run = slide0 > 0 && keep_old && h->slack_ok;
+    if (clean_run)
         cleaned = sr_launch_remove_clean(old_wt, old_alpha, old_yT, Np0, n_out, slide0, (long)(wt_doubles(n_out, Np0) - (size_t)n_out * NN0),
                                          SR_SLIDE_STEPS, s) == SR_OK;
     SR_AH(hipStreamSynchronize(s));
 #undef SR_A
 #undef SR_AH
+    {   // sr_gp_last_remove: how this removal ran (host state only; the predicates above, and sr_launch_remove_rows' for the instance)
+        int* lr = h->last_remove;
+        lr[SR_RM_COUNT] = ++h->rm_count; lr[SR_RM_NP0] = Np0; lr[SR_RM_NP1] = Np1; lr[SR_RM_OFF0] = off0; lr[SR_RM_Q] = q;
+        lr[SR_RM_SLIDE] = slide0; lr[SR_RM_ALIGNED] = reinterpret_cast<uintptr_t>(h->Wt) % 32 == 0 ? 1 : 0;
+        lr[SR_RM_SPARE] = !reuse_alt ? SR_RM_SPARE_NONE : (h->wt_alt_off < off0 ? SR_RM_SPARE_CLEARED : SR_RM_SPARE_AS_IS);
+        lr[SR_RM_VEC_SPARE] = vec_alt ? 1 : 0; lr[SR_RM_CLEAN] = clean_run && cleaned ? 1 : 0;
+        lr[SR_RM_KEPT_OLD] = same && keep_old && cleaned ? 1 : 0;
+    }
     h->yT = yT1; h->alpha = alpha1; h->Wt = Wt1;
     h->slide = 0;                                 // (a plain model; its buffers carry the zeroed slack: slack_ok stays)
     h->N = N1;
@@ -117,6 +126,14 @@ extern "C" int sr_gp_remove(sr_gp_t h, const int* idx_host, int m, void* stream)
     SR_TRY(h->rm_ws.grow((size_t)h->n_out * sr_remove_coef_stride(h->Np) + (size_t)h->N * h->D, wait::device()));
     for (int k = 0; k < m; ++k) SR_TRY(remove_one(h, idx[k], s));
     return SR_OK;
+}
+
+extern "C" int sr_gp_last_remove(sr_gp_t h, int* out, int cap) {
+    SR_CHECK(h && out && cap >= 1, SR_EINVAL, "sr_gp_last_remove: bad argument");
+    const int n = std::min(cap, (int)SR_REMOVE_WORDS);
+    std::copy(h->last_remove, h->last_remove + n, out);
+    out[SR_RM_COUNT] = h->rm_count;               // (a fit in between has set it back; the other words stay those of the last removal)
+    return n;
 }
 
 extern "C" int sr_gp_loo(sr_gp_t h, double* mu_loo, double* var_loo, void* stream) {

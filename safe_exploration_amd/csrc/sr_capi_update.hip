@@ -298,6 +298,7 @@ static int factorize_impl(sr_gp* h, void* stream, int* info, const sr_fact_src* 
     SR_TRY(server_quiesce(h));
     SR_TRY(unslide(h));
     model_rewritten(h);                              // (the exact fit and the sparse one: both come through here)
+    h->rm_count = 0;                                 // (points retired since the last fit: sr_gp_last_remove)
     h->slide_hold = 0; h->slide_forced = 0;          // (a refit starts the in-place appends' hold-off afresh: sr_capi_posterior.hip)
     const auto t_begin = std::chrono::steady_clock::now();
     static const bool trace_laps = sr_lab_on("SR_FACT_TRACE");

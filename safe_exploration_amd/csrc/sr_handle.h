@@ -202,6 +202,7 @@ struct sr_gp {
                                                           // 3 = tile-flow Cholesky (one resident kernel), -1 = never the tile flow
     int last_fact_pipe = 0;                               // the last update ran pipelined (diagnostics / tests)
     int last_update[SR_UPDATE_WORDS] = {0};               // how the last fit / append ran (sr_gp_last_update; diagnostics / tests)
+    int last_remove[SR_REMOVE_WORDS] = {0}; int rm_count = 0;   // how the last point was retired, points retired since the last fit (sr_gp_last_remove)
     hipEvent_t fact_fork = nullptr, fact_join = nullptr;
     hipEvent_t ev_panel[2] = {nullptr, nullptr}, ev_bulk[2] = {nullptr, nullptr};
     hipEvent_t ev_inv[2] = {nullptr, nullptr};            // critical -> inversion stream, back

@@ -1661,6 +1661,21 @@ class SimpleGPModel(StateSpaceModel):
         d["kind"] = kind
         return d
 
+    REMOVE_WORDS = ("count", "Np0", "Np1", "off0", "q", "slide", "aligned", "spare", "vec_spare", "clean", "kept_old")
+    REMOVE_SPARES = ("none", "as_is", "cleared")
+
+    def last_remove(self):
+        """how sr_gp_remove retired its last point (sr_gp_last_remove): a dict of REMOVE_WORDS, "spare" by name (REMOVE_SPARES);
+        "count" is the number of points retired since the last fit.  Diagnostics."""
+        self._need_trained()
+        out = (ctypes.c_int * len(self.REMOVE_WORDS))()
+        n = lib.sr_gp_last_remove(self._handle.h, out, len(out))
+        if n != len(out):
+            check(n if n < 0 else -1)
+        d = dict(zip(self.REMOVE_WORDS, (int(v) for v in out)))
+        d["spare"] = self.REMOVE_SPARES[d["spare"]]
+        return d
+
     def get_forward_model_casadi(self, linearize_mu=True):
         """state_space_models.py:140-166.  The evaluator calls the model once per IPOPT callback and blocks: the resident
         single-query server is armed for it (``start_server``; SR_NO_SERVER=1 in the environment keeps the launched

@@ -22,7 +22,19 @@ The computed factor is the exact factor of K + dK with |dK| <= gamma_{3b+1} |U^T
 and to first order dW = -W up(W^T dK W) (up: the upper triangle, the diagonal halved), so |dW| <= |W| kappa |dK| / |K|.  The
 explicit inversion's own error and the five-ulp kernel entries sit under the + 40, as in _posterior_ref.  After `a` append calls
 since the last fit every bar is multiplied by 1 + a: each append is one more backward-stable step of the same kind on the
-factor it is handed.
+factor it is handed.  A REMOVED point counts like an append call (FactorRef(prob, appends=a): a = append calls + removed points
+since the last fit): sr_gp_remove applies the product of the Givens rotations of the column pairs (q, k) to the factor it is
+handed, written as x'_k = a_k x_k - b_k d_k with a_k = p_k / p_{k+1} <= 1 and |b_k d_k| = |w_k| |d_k| / (p_k p_{k+1}) <= |x|_2 (Cauchy-
+Schwarz on d_k = sum w_l x_l, |w_{q..k-1}|_2 = p_k) -- an orthogonal transformation of every row, backward stable like the
+rotations themselves (Higham, Th. 19.10: a perturbation of gamma_{c n} |x|_2 per row, below one Cholesky's c_b u kappa |W|_2).
+After removals the reference is FactorRef(prob.without(rows)): _posterior_ref.Problem.without says why it stays exact.
+LEAVE-ONE-OUT (sr_gp_loo; FactorRef.loo): var_j = 1 / k_jj with k = K_c^-1, mu_j = y_j - alpha_j var_j.  An error dk of k_jj moves
+var_j by -dk / k_jj^2 to first order, so |dvar_j| <= bar_kinv var_j^2; mu_j moves by -dalpha_j var_j - alpha_j dvar_j, so
+|dmu_j| <= bar_alpha var_j + |alpha_j| bar_kinv var_j^2.  (k_jj = |row j of W_c|^2 is summed from entries under bar_w: 2 |W_c|_2
+bar_w = bar_kinv, the K^-1 bar itself; y_j is data.)
+DENSE PROBLEM (dense_problem): the recipe of one cluster without the cap of 90 points -- all N points in one box of 3
+lengthscales, one block of size b = N, the same formulas.  Every row of U^-1 then depends on every other, so a removal transforms
+every row (on the clustered data only the ~90 rows of the retired point's cluster change; the others are shifted).
 EXACT VALUES (no bar): the strict lower triangle is 0.0, the front padding is the identity, the bands between padding and real
 rows are 0.0.  OFF-CLUSTER entries inside the real rows: |w| <= OFF_REL |W| with |W| the largest |W_c|_2 and OFF_REL = 1e-200
 (rbf) / 1e-24 (mat52): the cross-cluster kernel bounds of _posterior_ref's docstring (1e-278, 4e-32) times kappa^2 < 1e6 and the
@@ -43,6 +55,11 @@ OFF_REL = {"rbf": 1e-200, "mat52": 1e-24}
 
 def problem(seed, N, D, n_out, kern="rbf"):
     return R.Problem(seed, N, D, n_out, kern, max_clusters=MAX_CLUSTERS)
+
+
+def dense_problem(seed, N, D, n_out, kern="rbf"):
+    """all N points in ONE cluster (module docstring, DENSE PROBLEM); its FactorRef is a dense long-double Cholesky"""
+    return R.Problem(seed, N, D, n_out, kern, cap=N)
 
 
 def noise_per_output(prob, step=0.01):
@@ -125,6 +142,21 @@ class FactorRef(object):
         for q, i in enumerate(self.idx):
             out[i] = self.block(q, d)["alpha64"]
         return out
+
+    def loo(self, d):
+        """leave-one-out posterior of output d from the cluster blocks, float64: (mu, var, bar_mu, bar_var), each (N,) (module
+        docstring, LEAVE-ONE-OUT)"""
+        N = self.p.N
+        mu, var, bmu, bvar = np.empty(N), np.empty(N), np.empty(N), np.empty(N)
+        for q, i in enumerate(self.idx):
+            blk = self.block(q, d)
+            v = 1 / np.diag(blk["Kinv"])
+            mu[i] = np.asarray(self.p.Y[i, d], dtype=LD) - blk["alpha"] * v
+            var[i] = v
+            v64 = v.astype(np.float64)
+            bvar[i] = self.bar_kinv(q, d) * v64 ** 2
+            bmu[i] = self.bar_alpha(q, d) * v64 + np.abs(blk["alpha64"]) * self.bar_kinv(q, d) * v64 ** 2
+        return mu, var, bmu, bvar
 
     def alpha_ratio(self, alpha):
         """largest |alpha - reference| / bar over outputs and clusters; alpha (n_out, N)"""

@@ -74,10 +74,12 @@ class Problem(object):
     every point, centres (c, D), base (D,) base lengthscales, ls (n_out, D), sf2 (n_out,), kern, nugget (n_out,), hyp
     (the list SimpleGPModel takes)."""
 
-    def __init__(self, seed, N, D, n_out, kern="rbf", max_clusters=128):
+    def __init__(self, seed, N, D, n_out, kern="rbf", max_clusters=128, cap=CLUSTER):
+        """cap: points per cluster at most (CLUSTER); cap >= N is ONE cluster, the recipe without the cap: a dense problem in
+        which every row depends on every other (tests/_factor_ref.dense_problem)"""
         assert kern in ("rbf", "mat52")
         rng = np.random.default_rng(seed)
-        c = -(-N // CLUSTER)
+        c = -(-N // cap)
         assert 1 <= c <= max_clusters, "N = %d needs %d clusters (> %d)" % (N, c, max_clusters)
         self.seed, self.N, self.D, self.n_out, self.kern, self.c = seed, N, D, n_out, kern, c
         self.base = rng.uniform(0.6, 1.6, D)
@@ -125,6 +127,24 @@ class Problem(object):
         p = copy.copy(self)
         p.Z, p.Y, p.member = np.vstack((self.Z, x)), np.vstack((self.Y, y)), np.concatenate((self.member, q))
         p.N = p.Z.shape[0]
+        return p
+
+    def without(self, rows):
+        """a copy without the rows `rows` (indices into the current rows, any order, each once); the others keep their order.
+        Removal keeps the order inside every cluster, as appending behind the others does, so after any mixture of `grown` and
+        `without` the dense factor of the remaining rows restricted to a cluster's indices is still the factor of that
+        cluster's remaining rows in their order: the argument of tests/_factor_ref.py's docstring (a permutation that keeps
+        the order inside every block of a block-diagonal matrix) carries over unchanged, and Ref / FactorRef of the copy are
+        exact.  No cluster may lose its last point (the classes factor every cluster)."""
+        import copy
+        rows = np.atleast_1d(np.asarray(rows, dtype=np.int64))
+        assert rows.size == np.unique(rows).size and rows.min() >= 0 and rows.max() < self.N
+        keep = np.ones(self.N, dtype=bool)
+        keep[rows] = False
+        p = copy.copy(self)
+        p.Z, p.Y, p.member = self.Z[keep], self.Y[keep], self.member[keep]
+        p.N = p.Z.shape[0]
+        assert np.all(np.bincount(p.member, minlength=p.c) > 0), "a cluster lost its last point"
         return p
 
 
