@@ -52,7 +52,8 @@ typedef struct sr_gp* sr_gp_t;
 #define SR_K_PATHS_DRAW   11 /* sr_gp_paths_draw: feature slab, residual, the two triangular products              */
 #define SR_K_PATHS_EVAL   12 /* sr_gp_paths_eval[_grad]: feature (and derivative) slabs of the chunk + the two-range MFMA tile (K* pass: SR_K_KSTAR) */
 #define SR_K_PATHS_STEP   13 /* sr_gp_paths_step[_grad]: split pass + ordered sum                                  */
-#define SR_K_COUNT     14
+#define SR_K_REACH_VJP    14 /* sr_ellipsoid_step_vjp / sr_onestep_reach_vjp: the reverse of the ellipsoid algebra + the GP link (its linearisation: SR_K_KSTAR, SR_K_VAR, SR_K_FINAL) */
+#define SR_K_COUNT     15
 
 int         sr_version(void);
 const char* sr_last_error(void);
@@ -265,6 +266,54 @@ int sr_ellipsoid_step(int device, long T, int n_s, int n_u, const double* p, con
                       const double* jac, const double* a, const double* b, const double* l_mu,
                       const double* l_sigma, double c_safety, double* p_out, double* q_out,
                       int* n_bad, void* stream);
+
+/* ---- reverse pass of ONE reachability step (beyond the reference, whose MPC differentiates a CasADi graph of the same lines,
+ * one problem at a time) -------------------------------------------------------------------------------------------------
+ * sr_ellipsoid_step_vjp: the vector-Jacobian product of sr_ellipsoid_step, both branches.  Forward inputs as there (q NULL =
+ * point branch; k_fb and jac required iff q != NULL).  For seeds p1_bar T x n_s and q1_bar T x n_s x n_s (either NULL = zero,
+ * with the same bits as a zero array; not both) the derivatives of
+ *   L = sum_t p1_bar[t] . p_out[t] + sum_ij q1_bar[t]_ij q_out[t]_ij
+ * in the inputs:  p_bar T x n_s ; q_bar T x n_s x n_s ; kff_bar T x n_u ; kfb_bar T x n_u x n_s ; mu_bar, var_bar T x n_s ;
+ * jac_bar T x n_s x (n_s+n_u).  q_bar and kfb_bar are meaningless in the point branch and may be NULL there (zero-filled when
+ * given, and so is jac_bar, which may be NULL there too).  a, b, l_mu, l_sigma, c_safety get no derivative.
+ * Only the symmetric part of q1_bar counts.  q_bar is exactly symmetric: the gradient of the function extended to unsymmetric
+ * arguments by q -> (q + q^T) / 2.  Nothing is saved by the forward; H, Q0, r^2, c1, c2 are recomputed.
+ * r^2 = lambda_max(Q (I + K^T K)) is differentiated through its top eigenvector (accumulated Jacobi rotations):
+ *   d r^2 / dQ = w w^T,  d r^2 / dK = 2 r^2 (K v) v^T   (w, v the left / right eigenvector of Q (I + K^T K), w . v = 1).
+ * Where the top eigenvalue is repeated r^2 is not differentiable: the formulas are evaluated at the unit vector of the top
+ * eigenspace the iteration found -- an element of the generalised gradient, finite; near a tie the rounding error of what
+ * passes through r^2 grows as lambda_1 / (lambda_1 - lambda_2).
+ * A query whose box half-widths are not all > 0 (the queries sr_ellipsoid_step counts in n_bad) gets NaN in every output of
+ * that query; no other query is affected.  (var_i = 0 in the ellipsoid branch is no such query, but d sqrt(var)/d var is infinite
+ * there: var_bar_i is +-inf, or NaN under a zero seed, and the rest of the query is finite.)  n_s <= 8, n_u <= 4 (SR_EUNSUPPORTED beyond); SR_EINVAL: NULL where required, q
+ * without k_fb / jac, both seeds NULL, T < 0; T == 0 is a no-op.  Asynchronous on `stream`; one thread per query, no atomics. */
+int sr_ellipsoid_step_vjp(int device, long T, int n_s, int n_u, const double* p, const double* q, const double* k_ff,
+                          const double* k_fb, const double* mu, const double* var, const double* jac, const double* a,
+                          const double* b, const double* l_mu, const double* l_sigma, double c_safety,
+                          const double* p1_bar, const double* q1_bar, double* p_bar, double* q_bar, double* kff_bar,
+                          double* kfb_bar, double* mu_bar, double* var_bar, double* jac_bar, void* stream);
+/* sr_onestep_reach_vjp: the reverse pass of sr_onestep_reach, GP included: seeds on (p_out, q_out) as above -> p_bar, q_bar,
+ * kff_bar, kfb_bar (q_bar, kfb_bar may be NULL in the point branch).  Per chunk of sr_gp_set_chunk queries: z = [Tz p; k_ff]
+ * (Tz: sr_gp_set_input_transform, else the identity), sr_gp_linearize_batch at z into a grow-only scratch owned by the handle
+ * (freed by sr_gp_release_scratch), then ONE launch with the reverse of the ellipsoid algebra and the GP link
+ *   z_bar = sum_a jac_mu[a] mu_bar[a] + jac_var[a] var_bar[a] + sum_{a,d} jac_z_bar[a][d] hess_mu[a][d],
+ *   p_bar += Tz^T z_bar[:n_x_in],  kff_bar += z_bar[n_x_in:].
+ * The model rules are those of sr_gp_linearize_batch: every kernel identifier, exact and sparse handles, D <= 8
+ * (SR_EUNSUPPORTED beyond).  The GP outputs the step is differentiated at are those of the linearisation pass (equal to the
+ * forward's up to the rounding of another route).  The derivative ignores the clip of the predictive variance at 1e-15.
+ * The same inputs give the same bits for ANY chunk size.  The new kernels work one query per thread.  The linearisation pass splits
+ * its sums over the training rows by the width of the batch it is given (K* pass: min(Np / 16, ceil(768 / b)) splits, Hessian pass:
+ * min(ceil(N / 32), ceil(1024 / b)), b = n_out ceil(width / 256)) and its final stage sums in another order beyond 4096 queries, so
+ * this entry point gives it at most min(chunk, 256 k) queries at a time, k = clamp(min(768 / (Np / 16), 1024 / ceil(N / 32)) / n_out,
+ * 1, 16): up to there both split counts are the ones set by the model size alone (k = 1: a width of 256 is one block whatever
+ * the chunk).  Small models go through whole (N = 150, n_out = 4: 3072 queries per pass), big ones in passes of 256 (N = 5000).
+ * In the point branch the Hessian is not read and the pass is sr_gp_predict_grad's.
+ * SR_ESTATE not factorized; SR_EINVAL NULL where required, q != NULL without k_fb,
+ * both seeds NULL, T < 0; T == 0 is a no-op.  Asynchronous on `stream`. */
+int sr_onestep_reach_vjp(sr_gp_t h, long T, const double* p, const double* q, const double* k_ff, const double* k_fb,
+                         const double* a, const double* b, const double* l_mu, const double* l_sigma, double c_safety,
+                         const double* p1_bar, const double* q1_bar, double* p_bar, double* q_bar, double* kff_bar,
+                         double* kfb_bar, void* stream);
 
 /* ---- Gaussian moment propagation (the CautiousMPC baseline), batched -----------------------------
  * replaces: uncertainty_propagation_casadi.one_step_taylor / multi_step_taylor_symbolic (mode 1)

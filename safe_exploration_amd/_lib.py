@@ -76,6 +76,8 @@ SIGNATURES = {
     "sr_moment_step": (_I, [_I, _L, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "sr_ellipsoid_step": (_I, [_I, _L, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _D, _P, _P,
                                _P, _P]),
+    "sr_ellipsoid_step_vjp": (_I, [_I, _L, _I, _I] + [_P] * 11 + [_D] + [_P] * 10),
+    "sr_onestep_reach_vjp": (_I, [_H, _L] + [_P] * 8 + [_D] + [_P] * 7),
     "sr_remainder_overapprox": (_I, [_I, _L, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
     "sr_safety_distance": (_I, [_I, _L, _I, _I, _P, _P, _P, _P, _D, _P, _P]),
     "sr_distance_to_center": (_I, [_I, _L, _I, _I, _P, _I, _P, _P, _P, _P]),

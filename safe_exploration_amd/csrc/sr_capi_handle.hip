@@ -229,6 +229,7 @@ void srh::drop_np_sized(sr_gp* h) {
     // sel_L, sel_ws: sized by the candidate pool, checked against their capacity on every use
     // mm_ws: sized by the queries of a chunk and N, checked against its capacity on every use
     // rm_ws: sized by Np and N, checked against its capacity on every use
+    // reach_ws: sized by the queries of a chunk, checked against its capacity on every use
     // paths: valid for one model generation only (sr_gp::model_gen), sized again by the next draw; paths_ws: checked against
     // its capacity on every use
 }
@@ -237,7 +238,7 @@ void srh::drop_np_sized(sr_gp* h) {
 // and the selection, the workspace of the path calls (not the paths), and the spare model buffers of the appends
 static void release_big(sr_gp* h) {
     h->fact_ws.drop(); h->app_ws.drop(); h->paths_ws.drop();
-    h->grad_v.drop(); h->grad_part.drop(); h->hess_part.drop(); h->sel_L.drop(); h->sel_ws.drop(); h->mm_ws.drop(); h->rm_ws.drop();
+    h->grad_v.drop(); h->grad_part.drop(); h->hess_part.drop(); h->sel_L.drop(); h->sel_ws.drop(); h->mm_ws.drop(); h->rm_ws.drop(); h->reach_ws.drop();
     drop_wt_alt(h);
     dev_free(h->yT_alt); dev_free(h->alpha_alt); h->yT_alt = h->alpha_alt = nullptr; h->vec_alt_np = 0;
 }

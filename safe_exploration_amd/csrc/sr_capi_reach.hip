@@ -412,6 +412,100 @@ extern "C" int sr_ellipsoid_step(int device, long T, int n_s, int n_u, const dou
     return sr_launch_ellipsoid(ea, (hipStream_t)stream);
 }
 
+// ---- reverse pass of one step (sr_reach_vjp.hip) ---------------------------------------------------------------------------
+extern "C" int sr_ellipsoid_step_vjp(int device, long T, int n_s, int n_u, const double* p, const double* q,
+                                     const double* k_ff, const double* k_fb, const double* mu, const double* var,
+                                     const double* jac, const double* a, const double* b, const double* l_mu,
+                                     const double* l_sigma, double c_safety, const double* p1_bar, const double* q1_bar,
+                                     double* p_bar, double* q_bar, double* kff_bar, double* kfb_bar, double* mu_bar,
+                                     double* var_bar, double* jac_bar, void* stream) {
+    SR_CHECK(T >= 0, SR_EINVAL, "sr_ellipsoid_step_vjp: T=%ld", T);
+    if (T == 0) return SR_OK;
+    SR_CHECK(p && k_ff && mu && var && a && b && l_mu && l_sigma && p_bar && kff_bar && mu_bar && var_bar, SR_EINVAL,
+             "sr_ellipsoid_step_vjp: NULL argument");
+    SR_CHECK(q == nullptr || (k_fb && jac && q_bar && kfb_bar && jac_bar), SR_EINVAL,
+             "sr_ellipsoid_step_vjp: k_fb, jac, q_bar, kfb_bar and jac_bar required with q");
+    SR_CHECK(p1_bar || q1_bar, SR_EINVAL, "sr_ellipsoid_step_vjp: both seeds NULL");
+    SR_DEVICE(device);
+    sr_ellvjp_args ea{};
+    ea.T = T; ea.q = q; ea.k_fb = k_fb; ea.var = var; ea.jac = jac;
+    ea.a = a; ea.b = b; ea.l_mu = l_mu; ea.l_sigma = l_sigma; ea.c_safety = c_safety;
+    ea.p1_bar = p1_bar; ea.q1_bar = q1_bar;
+    ea.p_bar = p_bar; ea.q_bar = q_bar; ea.kff_bar = kff_bar; ea.kfb_bar = kfb_bar;
+    ea.mu_bar = mu_bar; ea.var_bar = var_bar; ea.jac_bar = jac_bar;
+    return sr_launch_reach_vjp(ea, n_s, n_u, (hipStream_t)stream);
+}
+
+// doubles of reach_ws per query: z | mu, var | jac_mu, jac_var | hess_mu | mu_bar, var_bar | jac_bar, jac_s | jz
+static long sr_reach_vjp_ws_per_query(int n_s, int n_u, int D) {
+    return D + 4L * n_s + 3L * n_s * D + (long)n_s * D * D + 2L * n_s * (n_s + n_u);
+}
+
+extern "C" int sr_onestep_reach_vjp(sr_gp_t h, long T, const double* p, const double* q, const double* k_ff,
+                                    const double* k_fb, const double* a, const double* b, const double* l_mu,
+                                    const double* l_sigma, double c_safety, const double* p1_bar, const double* q1_bar,
+                                    double* p_bar, double* q_bar, double* kff_bar, double* kfb_bar, void* stream) {
+    SR_CHECK(h != nullptr, SR_EINVAL, "sr_onestep_reach_vjp: NULL handle");
+    SR_CHECK(h->factorized, SR_ESTATE, "sr_onestep_reach_vjp: model not factorized");
+    SR_CHECK(T >= 0, SR_EINVAL, "sr_onestep_reach_vjp: T=%ld", T);
+    if (T == 0) return SR_OK;
+    SR_CHECK(p && k_ff && a && b && l_mu && l_sigma && p_bar && kff_bar, SR_EINVAL, "sr_onestep_reach_vjp: NULL argument");
+    SR_CHECK(q == nullptr || (k_fb && q_bar && kfb_bar), SR_EINVAL, "sr_onestep_reach_vjp: k_fb, q_bar and kfb_bar required with q");
+    SR_CHECK(p1_bar || q1_bar, SR_EINVAL, "sr_onestep_reach_vjp: both seeds NULL");
+    int n_s, n_u;
+    SR_TRY(check_reach_dims(h, &n_s, &n_u));
+    if (h->D > 8) {                                   // the widths sr_gp_linearize_batch is compiled for
+        sr_set_error("sr_onestep_reach_vjp: D=%d > 8 (the batched linearisation behind it)", h->D);
+        return SR_EUNSUPPORTED;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    SR_DEVICE(h->device);
+    const int D = h->D, n_xin = h->n_xin ? h->n_xin : n_s;
+    const long per = sr_reach_vjp_ws_per_query(n_s, n_u, D);
+    // The same bits for any chunk size: the linearisation splits its sums over the training rows by the width b = n_out
+    // ceil(Tp / 256) of the batch it is given -- pick_nsplit: min(Np / 16, ceil(768 / b)), sr_hess_nsplit: min(ceil(N / 32),
+    // ceil(1024 / b)) -- and sr_finalize sums in another order beyond SR_FINAL_WAVE_T queries.  Passes of at most 256 k queries,
+    // k the largest count of 256-query blocks at which both minima are still the first term (at least one block: b = n_out for
+    // every width up to 256), take the split counts the model size sets, whatever chunk the caller chose.
+    const long k_blocks = std::min(768L / std::max(1, h->Np / 16), 1024L / std::max(1, (h->N + 31) / 32)) / h->n_out;
+    const long pass_max = 256 * std::max(1L, std::min(k_blocks, (long)SR_FINAL_WAVE_T / 256));
+    const long chunk = std::max(1L, std::min({h->chunk, pass_max, ((long)1 << 28) / per}));
+    const long nss = (long)n_s * n_s, nus = (long)n_u * n_s, nd = (long)n_s * D, nds = (long)n_s * (n_s + n_u);
+    const long Tw = std::min(chunk, T);
+    SR_TRY(h->reach_ws.grow((size_t)(Tw * per), wait::stream(s)));
+    double* w = h->reach_ws.get();
+    double* z = w; w += Tw * D;
+    double* mu = w; w += Tw * n_s;
+    double* var = w; w += Tw * n_s;
+    double* jm = w; w += Tw * nd;
+    double* jv = w; w += Tw * nd;
+    double* hm = w; w += Tw * nd * D;
+    double* mu_bar = w; w += Tw * n_s;
+    double* var_bar = w; w += Tw * n_s;
+    double* jac_bar = w; w += Tw * nds;
+    double* jac_s = w; w += Tw * nds;
+    double* jz = w;
+    for (long t0 = 0; t0 < T; t0 += chunk) {
+        const long Tc = std::min(chunk, T - t0);
+        SR_TRY(sr_launch_reach_z(Tc, n_s, n_u, n_xin, p + t0 * n_s, k_ff + t0 * n_u, h->n_xin ? h->Tz : nullptr, z, s));
+        if (q) SR_TRY(sr_gp_linearize_batch(h, z, Tc, mu, var, jm, jv, hm, stream));
+        else SR_TRY(sr_gp_predict_grad(h, z, Tc, mu, var, jm, jv, stream));        // (the point branch reads no Hessian)
+        sr_ellvjp_args ea{};
+        ea.T = Tc; ea.q = q ? q + t0 * nss : nullptr; ea.k_fb = k_fb ? k_fb + t0 * nus : nullptr;
+        ea.var = var; ea.jac = jm;                    // (identity transform: the GP's Jacobian is the state-space one)
+        ea.a = a; ea.b = b; ea.l_mu = l_mu; ea.l_sigma = l_sigma; ea.c_safety = c_safety;
+        ea.p1_bar = p1_bar ? p1_bar + t0 * n_s : nullptr; ea.q1_bar = q1_bar ? q1_bar + t0 * nss : nullptr;
+        ea.p_bar = p_bar + t0 * n_s; ea.q_bar = q_bar ? q_bar + t0 * nss : nullptr;
+        ea.kff_bar = kff_bar + t0 * n_u; ea.kfb_bar = kfb_bar ? kfb_bar + t0 * nus : nullptr;
+        ea.mu_bar = mu_bar; ea.var_bar = var_bar; ea.jac_bar = jac_bar;
+        ea.jac_mu = jm; ea.jac_var = jv; ea.hess_mu = hm; ea.Tz = h->n_xin ? h->Tz : nullptr; ea.D = D; ea.n_xin = n_xin;
+        ea.jac_s = jac_s; ea.jz = jz;
+        sr_prof_scope ps(&h->prof, SR_K_REACH_VJP, s);
+        SR_TRY(sr_launch_reach_vjp(ea, n_s, n_u, s));
+    }
+    return SR_OK;
+}
+
 extern "C" int sr_remainder_overapprox(int device, long T, int n_s, int n_u, const double* q,
                                        const double* k_fb, const double* l_mu, const double* l_sigma,
                                        double* u_mu, double* u_sigma, void* stream) {

@@ -567,6 +567,23 @@ struct sr_ell_args {
                                       // Gaussian moment propagation (uncertainty_propagation_casadi.py)
 };
 int sr_launch_ellipsoid(const sr_ell_args& a, hipStream_t s);
+// reverse pass of one step in mode 0 (sr_ellipsoid_vjp_dev.h, sr_reach_vjp.hip); every array dense
+struct sr_ellvjp_args {
+    long T;
+    // forward inputs (dense): q T x n_s^2 or NULL (point branch), k_fb T x n_u n_s, jac T x n_s (n_s + n_u)
+    const double* q; const double* k_fb; const double* var; const double* jac;
+    const double* a; const double* b; const double* l_mu; const double* l_sigma; double c_safety;
+    const double* p1_bar; const double* q1_bar;            // seeds, either may be NULL
+    double* p_bar; double* q_bar; double* kff_bar; double* kfb_bar; double* mu_bar; double* var_bar; double* jac_bar;
+    // GP link (hess_mu == NULL: none).  jac_mu / jac_var T x n_s x D, hess_mu T x n_s x D x D at z = [Tz p; k_ff];
+    // Tz n_xin x n_s or NULL (identity, n_xin = n_s); jac_s T x n_s (n_s + n_u) and jz T x n_s x D: per-query scratch
+    const double* jac_mu; const double* jac_var; const double* hess_mu; const double* Tz; int D, n_xin;
+    double* jac_s; double* jz;
+};
+int sr_launch_reach_vjp(const sr_ellvjp_args& a, int n_s, int n_u, hipStream_t s);
+// z[t] = [Tz p[t]; k_ff[t]] (T x (n_xin + n_u); Tz NULL: the identity, n_xin = n_s)
+int sr_launch_reach_z(long T, int n_s, int n_u, int n_xin, const double* p, const double* k_ff, const double* Tz, double* z,
+                      hipStream_t s);
 int sr_launch_remainder(long T, int n_s, int n_u, const double* q, const double* k_fb,
                         const double* l_mu, const double* l_sigma, double* u_mu, double* u_sigma,
                         hipStream_t s);

@@ -9,6 +9,12 @@ All arithmetic happens in the HIP kernels behind include/safereach.h:
     on the device, nothing returns to the host between the kernels),
   * any other StateSpaceModel     -> its ``ssm(x, u)`` is called on the host exactly like the
     reference does (gp_reachability.py:74,101) and the ellipsoid algebra runs in sr_ellipsoid_step.
+
+Beyond the reference: the reverse pass of ONE step on the device (``ellipsoid_step_vjp_batch`` / ``sr_ellipsoid_step_vjp``,
+``onestep_reachability_vjp_batch`` / ``sr_onestep_reach_vjp``) and, on top of it, ``differentiable=True`` on the three batched
+entry points: the forward stays the plain call (the same bits), the backward is the device reverse pass, steps are chained by
+torch autograd.  Gradients reach the centres, shape matrices and controls (and mu, var, jac of ``ellipsoid_step_batch``), not
+the model.  Mode 0 only; D <= 8; no persistent reverse chain.
 """
 import ctypes
 
@@ -87,7 +93,8 @@ def _raise_if_chain_failed(hd, dev, synced):
 
 
 def onestep_reachability_batch(p_center, ssm, k_ff, l_mu, l_sigma, q_shape=None, k_fb=None,
-                               c_safety=1., a=None, b=None, check_bounds=False, return_var=False, t_z_gp=None):
+                               c_safety=1., a=None, b=None, check_bounds=False, return_var=False, t_z_gp=None,
+                               differentiable=False):
     """Batched ``onestep_reachability``.
 
     p_center (T,n_s); k_ff (T,n_u); q_shape (T,n_s,n_s) or None; k_fb (T,n_u,n_s) or None.
@@ -95,9 +102,17 @@ def onestep_reachability_batch(p_center, ssm, k_ff, l_mu, l_sigma, q_shape=None,
     t_z_gp (n_x_in, n_s): the GP's state inputs are t_z_gp @ state (the argument of the same name of
     gp_reachability_casadi.onestep_reachability, :17-19,60-61); the model then has D = n_x_in + n_u inputs.
     Returns p_new (T,n_s), q_new (T,n_s,n_s) [, var (T,n_s)].
+    differentiable (tensors only): p_new and q_new, the same bits, carry an autograd graph to p_center, q_shape, k_ff and k_fb
+    whose backward is ``onestep_reachability_vjp_batch`` (once differentiable; no gradient to the model or to var).
     """
     if not isinstance(ssm, SimpleGPModel):
         raise TypeError("onestep_reachability_batch needs the HIP SimpleGPModel")
+    if differentiable:
+        if not B.is_tensor(p_center):
+            raise TypeError("differentiable=True needs tensors")
+        p1, q1, var = _OnestepReachFn.apply(ssm, (l_mu, l_sigma, c_safety, a, b, check_bounds, t_z_gp), p_center, q_shape,
+                                            k_ff, k_fb if q_shape is not None else None)
+        return (p1, q1, var) if return_var else (p1, q1)
     as_t = B.is_tensor(p_center)
     hd = ssm._handle
     ssm._need_trained()
@@ -165,9 +180,16 @@ def onestep_reachability_batch(p_center, ssm, k_ff, l_mu, l_sigma, q_shape=None,
 
 
 def ellipsoid_step_batch(p_center, k_ff, mu, var, jac, l_mu, l_sigma, q_shape=None, k_fb=None,
-                         c_safety=1., a=None, b=None, check_bounds=False, device=None):
+                         c_safety=1., a=None, b=None, check_bounds=False, device=None, differentiable=False):
     """The ellipsoid algebra of gp_reachability.py:65-156 for T queries whose GP outputs
-    (mu (T,n_s), var (T,n_s), jac (T,n_s,n_s+n_u)) are supplied by the caller."""
+    (mu (T,n_s), var (T,n_s), jac (T,n_s,n_s+n_u)) are supplied by the caller.
+    differentiable (tensors only): the outputs, the same bits, carry an autograd graph to p_center, q_shape, k_ff, k_fb, mu, var
+    and jac whose backward is ``ellipsoid_step_vjp_batch`` (once differentiable)."""
+    if differentiable:
+        if not B.is_tensor(p_center):
+            raise TypeError("differentiable=True needs tensors")
+        return _EllipsoidStepFn.apply((l_mu, l_sigma, c_safety, a, b, check_bounds), p_center, q_shape, k_ff,
+                                      k_fb if q_shape is not None else None, mu, var, jac if q_shape is not None else None)
     as_t = B.is_tensor(p_center)
     dev = B.resolve_device(p_center.device if as_t else device)
     p = B.as_dev(p_center, dev)
@@ -192,6 +214,132 @@ def ellipsoid_step_batch(p_center, k_ff, mu, var, jac, l_mu, l_sigma, q_shape=No
                                 B.ptr(n_bad), B.stream_ptr(dev)))
     _raise_if_bad(n_bad)
     return (p_out, q_out) if as_t else (B.to_numpy(p_out), B.to_numpy(q_out))
+
+
+def _seed_pair(p1_bar, q1_bar, dev, T, n_s):
+    if p1_bar is None and q1_bar is None:
+        raise ValueError("at least one of p1_bar, q1_bar is needed")
+    return B.as_dev(p1_bar, dev, (T, n_s)), B.as_dev(q1_bar, dev, (T, n_s, n_s))
+
+
+def ellipsoid_step_vjp_batch(p_center, k_ff, mu, var, jac, l_mu, l_sigma, p1_bar=None, q1_bar=None, q_shape=None, k_fb=None,
+                             c_safety=1., a=None, b=None, device=None):
+    """Reverse pass of ``ellipsoid_step_batch`` (``sr_ellipsoid_step_vjp``): for seeds p1_bar (T,n_s), q1_bar (T,n_s,n_s) on its two
+    outputs (None = zero) the gradients (p_bar, q_bar, kff_bar, kfb_bar, mu_bar, var_bar, jac_bar), shaped like the inputs;
+    q_bar, kfb_bar and jac_bar are None in the point branch (q_shape None).  Only the symmetric part of q1_bar counts, q_bar is
+    exactly symmetric, a query the forward would count as a bound violation is NaN.  numpy in -> numpy out, tensors in ->
+    tensors out."""
+    as_t = B.is_tensor(p_center)
+    dev = B.resolve_device(p_center.device if as_t else device)
+    p = B.as_dev(p_center, dev)
+    T, n_s = p.shape
+    kff = B.as_dev(k_ff, dev).reshape(T, -1)
+    n_u = kff.shape[1]
+    tmu, tvar = B.as_dev(mu, dev, (T, n_s)), B.as_dev(var, dev, (T, n_s))
+    q = B.as_dev(q_shape, dev, (T, n_s, n_s)) if q_shape is not None else None
+    if q is not None and (k_fb is None or jac is None):
+        raise ValueError("k_fb and jac are required when q_shape is given")
+    kfb = B.as_dev(k_fb, dev, (T, n_u, n_s)) if q is not None else None
+    tjac = B.as_dev(jac, dev, (T, n_s, n_s + n_u)) if q is not None else None
+    pb, qb = _seed_pair(p1_bar, q1_bar, dev, T, n_s)
+    a, b = _lin_model(a, b, n_s, n_u)
+    ta, tb = B.const_dev(a, dev, (n_s, n_s)), B.const_dev(b, dev, (n_s, n_u))
+    tlm, tls = B.const_dev(l_mu, dev, (n_s,)), B.const_dev(l_sigma, dev, (n_s,))
+    ell = q is not None
+    outs = [B.empty((T, n_s), dev), B.empty((T, n_s, n_s), dev) if ell else None, B.empty((T, n_u), dev),
+            B.empty((T, n_u, n_s), dev) if ell else None, B.empty((T, n_s), dev), B.empty((T, n_s), dev),
+            B.empty((T, n_s, n_s + n_u), dev) if ell else None]
+    check(lib.sr_ellipsoid_step_vjp(dev.index, T, n_s, n_u, B.ptr(p), B.ptr(q), B.ptr(kff), B.ptr(kfb), B.ptr(tmu), B.ptr(tvar),
+                                    B.ptr(tjac), B.ptr(ta), B.ptr(tb), B.ptr(tlm), B.ptr(tls), float(c_safety), B.ptr(pb),
+                                    B.ptr(qb), *[B.ptr(o) for o in outs], B.stream_ptr(dev)))
+    return tuple(outs) if as_t else tuple(None if o is None else B.to_numpy(o) for o in outs)
+
+
+def onestep_reachability_vjp_batch(p_center, ssm, k_ff, l_mu, l_sigma, p1_bar=None, q1_bar=None, q_shape=None, k_fb=None,
+                                   c_safety=1., a=None, b=None, t_z_gp=None):
+    """Reverse pass of ``onestep_reachability_batch``, GP included (``sr_onestep_reach_vjp``: a batched linearisation at
+    z = [t_z_gp p; k_ff], then one launch with the reverse of the ellipsoid algebra and the GP link): for seeds p1_bar (T,n_s),
+    q1_bar (T,n_s,n_s) (None = zero) the gradients (p_bar, q_bar, kff_bar, kfb_bar); q_bar and kfb_bar are None in the point
+    branch.  Models as ``linearize_device_batch`` takes them (every kernel, exact and sparse, D <= 8: NotImplementedError
+    beyond).  numpy in -> numpy out, tensors in -> tensors out."""
+    if not isinstance(ssm, SimpleGPModel):
+        raise TypeError("onestep_reachability_vjp_batch needs the HIP SimpleGPModel")
+    as_t = B.is_tensor(p_center)
+    hd = ssm._handle
+    ssm._need_trained()
+    dev = hd.device
+    n_s, n_u = _reach_dims(hd, t_z_gp)
+    if q_shape is not None and k_fb is None:
+        raise ValueError("k_fb is required when q_shape is given")
+    p = B.as_dev(p_center, dev)
+    T = p.shape[0]
+    if p.dim() != 2 or p.shape[1] != n_s:
+        raise ValueError("p_center must be (T, {})".format(n_s))
+    kff = B.as_dev(k_ff, dev, (T, n_u))
+    q = B.as_dev(q_shape, dev, (T, n_s, n_s)) if q_shape is not None else None
+    kfb = B.as_dev(k_fb, dev, (T, n_u, n_s)) if q is not None else None
+    pb, qb = _seed_pair(p1_bar, q1_bar, dev, T, n_s)
+    a, b = _lin_model(a, b, n_s, n_u)
+    ta, tb = B.const_dev(a, dev, (n_s, n_s)), B.const_dev(b, dev, (n_s, n_u))
+    tlm, tls = B.const_dev(l_mu, dev, (n_s,)), B.const_dev(l_sigma, dev, (n_s,))
+    ell = q is not None
+    outs = [B.empty((T, n_s), dev), B.empty((T, n_s, n_s), dev) if ell else None, B.empty((T, n_u), dev),
+            B.empty((T, n_u, n_s), dev) if ell else None]
+    with _input_transform(ssm, t_z_gp):
+        check(lib.sr_onestep_reach_vjp(hd.h, T, B.ptr(p), B.ptr(q), B.ptr(kff), B.ptr(kfb), B.ptr(ta), B.ptr(tb), B.ptr(tlm),
+                                       B.ptr(tls), float(c_safety), B.ptr(pb), B.ptr(qb), *[B.ptr(o) for o in outs],
+                                       B.stream_ptr(dev)))
+    return tuple(outs) if as_t else tuple(None if o is None else B.to_numpy(o) for o in outs)
+
+
+class _OnestepReachFn(torch.autograd.Function):
+    """``onestep_reachability_batch(..., differentiable=True)``: the forward is the plain call, the backward
+    ``onestep_reachability_vjp_batch`` at the saved inputs.  Seeds of outputs nobody used arrive as None (= zero, the same
+    bits); the variance output carries no gradient."""
+
+    @staticmethod
+    def forward(ctx, ssm, cfg, p, q, k_ff, k_fb):
+        l_mu, l_sigma, c_safety, a, b, check_bounds, t_z_gp = cfg
+        p1, q1, var = onestep_reachability_batch(p, ssm, k_ff, l_mu, l_sigma, q, k_fb, c_safety, a, b, check_bounds, True, t_z_gp)
+        ctx.ssm, ctx.cfg = ssm, cfg
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(p, q, k_ff, k_fb)
+        ctx.mark_non_differentiable(var)
+        return p1, q1, var
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, p1_bar, q1_bar, _var_bar):
+        p, q, k_ff, k_fb = ctx.saved_tensors
+        l_mu, l_sigma, c_safety, a, b, _, t_z_gp = ctx.cfg
+        if p1_bar is None and q1_bar is None:
+            return (None,) * 6
+        p_bar, q_bar, kff_bar, kfb_bar = onestep_reachability_vjp_batch(p, ctx.ssm, k_ff, l_mu, l_sigma, p1_bar, q1_bar, q, k_fb,
+                                                                        c_safety, a, b, t_z_gp)
+        return None, None, p_bar, q_bar, kff_bar.reshape(k_ff.shape), kfb_bar
+
+
+class _EllipsoidStepFn(torch.autograd.Function):
+    """``ellipsoid_step_batch(..., differentiable=True)``, likewise over ``ellipsoid_step_vjp_batch``."""
+
+    @staticmethod
+    def forward(ctx, cfg, p, q, k_ff, k_fb, mu, var, jac):
+        l_mu, l_sigma, c_safety, a, b, check_bounds = cfg
+        p1, q1 = ellipsoid_step_batch(p, k_ff, mu, var, jac, l_mu, l_sigma, q, k_fb, c_safety, a, b, check_bounds)
+        ctx.cfg = cfg
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(p, q, k_ff, k_fb, mu, var, jac)
+        return p1, q1
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, p1_bar, q1_bar):
+        p, q, k_ff, k_fb, mu, var, jac = ctx.saved_tensors
+        l_mu, l_sigma, c_safety, a, b, _ = ctx.cfg
+        if p1_bar is None and q1_bar is None:
+            return (None,) * 8
+        g = ellipsoid_step_vjp_batch(p, k_ff, mu, var, jac, l_mu, l_sigma, p1_bar, q1_bar, q, k_fb, c_safety, a, b)
+        return (None, g[0], g[1], g[2].reshape(k_ff.shape), g[3], g[4].reshape(mu.shape), g[5].reshape(var.shape), g[6])
 
 
 def onestep_reachability(p_center, ssm, k_ff, l_mu, l_sigma, q_shape=None, k_fb=None,
@@ -235,15 +383,36 @@ def onestep_reachability(p_center, ssm, k_ff, l_mu, l_sigma, q_shape=None, k_fb=
 
 
 def multistep_reachability_batch(p_0, gp, k_fb, k_ff, L_mu, L_sigm, q_0=None, c_safety=1., a=None,
-                                 b=None, k_fb_init=None, check_bounds=False, t_z_gp=None):
+                                 b=None, k_fb_init=None, check_bounds=False, t_z_gp=None, differentiable=False):
     """Batched ``multistep_reachability``: T independent trajectories, H sequential steps each.
 
     p_0 (T,n_s); k_fb (T,H-1,n_u,n_s); k_ff (T,H,n_u); q_0 (T,n_s,n_s) or None;
     k_fb_init (T,n_u,n_s) (needed iff q_0 is given).  Returns p_all (T,H,n_s), q_all (T,H,n_s,n_s).
+    differentiable (tensors only): H differentiable one-step calls chained in torch (step 0 from the point, or from
+    (q_0, k_fb_init), exactly as the forward), stacked into p_all, q_all with an autograd graph to p_0, q_0, k_fb_init, k_ff and
+    k_fb.  Every step is one ``sr_onestep_reach`` call, so the values are those of the forward's per-step-launch route
+    (``gp.set_chain(False)``: a K* pass, the variance contraction and the ellipsoid kernel per step), to the bit, wherever one
+    step takes that route itself: for n_s >= 3 always, for n_s <= 2 with ``gp.set_chain(False)`` around this call as well (a
+    one-step call of a small model with n_s <= 2 otherwise runs posterior and step in one launch of its own and agrees with the
+    per-step route to rounding).  There is no persistent reverse chain.
     """
     if not isinstance(gp, SimpleGPModel):
         raise TypeError("multistep_reachability_batch needs the HIP SimpleGPModel")
     gp._need_trained()
+    if differentiable:
+        if not B.is_tensor(p_0):
+            raise TypeError("differentiable=True needs tensors")
+        if q_0 is not None and k_fb_init is None:
+            raise ValueError("k_fb_init is required when q_0 is given")
+        H = k_ff.shape[1]
+        p, q, ps, qs = p_0, q_0, [], []
+        for i in range(H):
+            kfb_i = (k_fb_init if q_0 is not None else None) if i == 0 else k_fb[:, i - 1]
+            p, q = onestep_reachability_batch(p, gp, k_ff[:, i], L_mu, L_sigm, q, kfb_i, c_safety, a, b,
+                                              check_bounds=check_bounds, t_z_gp=t_z_gp, differentiable=True)
+            ps.append(p)
+            qs.append(q)
+        return torch.stack(ps, dim=1), torch.stack(qs, dim=1)
     as_t = B.is_tensor(p_0)
     hd = gp._handle
     dev = hd.device
