@@ -52,7 +52,7 @@ typedef struct sr_gp* sr_gp_t;
 #define SR_K_PATHS_DRAW   11 /* sr_gp_paths_draw: feature slab, residual, the two triangular products              */
 #define SR_K_PATHS_EVAL   12 /* sr_gp_paths_eval[_grad]: feature (and derivative) slabs of the chunk + the two-range MFMA tile (K* pass: SR_K_KSTAR) */
 #define SR_K_PATHS_STEP   13 /* sr_gp_paths_step[_grad]: split pass + ordered sum                                  */
-#define SR_K_REACH_VJP    14 /* sr_ellipsoid_step_vjp / sr_onestep_reach_vjp: the reverse of the ellipsoid algebra + the GP link (its linearisation: SR_K_KSTAR, SR_K_VAR, SR_K_FINAL) */
+#define SR_K_REACH_VJP    14 /* sr_ellipsoid_step_vjp / sr_onestep_reach_vjp, sr_onestep_moments_vjp: the reverse of the step's algebra + the GP link (its linearisation: SR_K_KSTAR, SR_K_VAR, SR_K_FINAL) */
 #define SR_K_COUNT     15
 
 int         sr_version(void);
@@ -330,6 +330,58 @@ int sr_moment_step(int device, long T, int n_s, int n_u, int mode, const double*
                    const double* sigma_x, const double* k_ff, const double* k_fb, const double* mu_g,
                    const double* var_g, const double* jac_g, const double* a, const double* b,
                    double* mu_out, double* sigma_out, void* stream);
+/* sr_onestep_moments: one step with the GP inside, from a point (sigma_x NULL) or from N(mu_x, sigma_x) -- what
+ * sr_multistep_moments cannot start from.  mu_x T x n_s ; sigma_x T x n_s x n_s ; k_ff T x n_u ; k_fb T x n_u x n_s (required iff
+ * sigma_x != NULL) -> mu_out T x n_s ; sigma_out T x n_s x n_s ; var_out T x n_s (GP variances, or NULL).  u = k_ff, the GP is
+ * evaluated at z = [Tz mu_x; k_ff] (Tz: sr_gp_set_input_transform, else the identity).  No new kernel: per chunk of
+ * sr_gp_set_chunk the launches of one step of sr_multistep_moments on its per-step route (the posterior with its Jacobian into
+ * the handle's workspace, then the moment step), so H calls in a row give the bits of that route.
+ * SR_ESTATE not factorized; SR_EINVAL NULL where required, sigma_x without k_fb, T < 0, mode outside {1, 2}; T == 0 is a no-op;
+ * n_s <= 8, n_u <= 4 (SR_EUNSUPPORTED beyond).  Asynchronous on `stream`. */
+int sr_onestep_moments(sr_gp_t h, long T, int mode, const double* mu_x, const double* sigma_x, const double* k_ff,
+                       const double* k_fb, const double* a, const double* b, double* mu_out, double* sigma_out,
+                       double* var_out, void* stream);
+
+/* ---- reverse pass of ONE moment step, modes 1 and 2 (beyond the reference, whose CautiousMPC differentiates a CasADi graph of the
+ * same lines, one problem at a time) ---------------------------------------------------------------------------------------
+ * sr_moment_step_vjp: the vector-Jacobian product of sr_moment_step, both starts.  Forward inputs as there (sigma_x NULL = point
+ * start; k_fb required iff sigma_x != NULL, jac_g iff sigma_x != NULL in mode 1 -- it is never read in mode 2).  With
+ *   mu1 = a mu_x + b k_ff + mu_g ,  Sigma1 = H Sigma H^T + diag(var_g) ,  H = a + J_x + (b + J_u) K (mode 1) or a + b K (mode 2)
+ * and seeds mu1_bar T x n_s, sigma1_bar T x n_s x n_s (either NULL = zero, with the same bits as a zero array; not both), S its
+ * symmetric part, the derivatives of  L = sum_t mu1_bar[t] . mu_out[t] + sum_ij sigma1_bar[t]_ij sigma_out[t]_ij  in the inputs:
+ *   mux_bar = a^T mu1_bar ; kff_bar = b^T mu1_bar ; mug_bar = mu1_bar ; var_bar_i = S_ii ;
+ *   sigma_bar = H^T S H ; with H_bar = 2 S H sym(Sigma):  jac_bar = [H_bar, H_bar K^T], kfb_bar = (J_u + b)^T H_bar (mode 1),
+ *   jac_bar = 0, kfb_bar = b^T H_bar (mode 2).
+ * At a point start jac_bar, sigma_bar and kfb_bar are zero: they may be NULL there and are zero-filled where given.  sigma_x is
+ * read as (Sigma + Sigma^T) / 2 and sigma_bar is exactly symmetric: the gradient of the function extended to unsymmetric
+ * arguments that way.  Only the symmetric part of sigma1_bar counts.  a and b get no derivative.  Nothing is saved by the
+ * forward; H is recomputed.  There is no square root in these modes: no query is refused and nothing is NaN that was not.
+ * n_s <= 8, n_u <= 4 (SR_EUNSUPPORTED beyond); SR_EINVAL: NULL where required, sigma_x without k_fb / jac_g (mode 1) / sigma_bar /
+ * kfb_bar / jac_bar, both seeds NULL, T < 0, mode outside {1, 2}; T == 0 is a no-op.  Asynchronous on `stream`; one thread per
+ * query, no atomics, sums in a fixed order. */
+int sr_moment_step_vjp(int device, long T, int n_s, int n_u, int mode, const double* mu_x, const double* sigma_x,
+                       const double* k_ff, const double* k_fb, const double* mu_g, const double* var_g, const double* jac_g,
+                       const double* a, const double* b, const double* mu1_bar, const double* sigma1_bar, double* mux_bar,
+                       double* sigma_bar, double* kff_bar, double* kfb_bar, double* mug_bar, double* var_bar, double* jac_bar,
+                       void* stream);
+/* sr_onestep_moments_vjp: the reverse pass of sr_onestep_moments, GP included: seeds on (mu_out, sigma_out) as above and
+ * gpvar_bar T x n_s on var_out (var_bar_i = S_ii + gpvar_bar_i; any seed NULL = zero, not all three) -> mux_bar, sigma_bar,
+ * kff_bar, kfb_bar (sigma_bar, kfb_bar may be NULL at a point start).  Per pass: z = [Tz mu_x; k_ff], the GP derivatives at z
+ * into the grow-only scratch of sr_onestep_reach_vjp (freed by sr_gp_release_scratch), then ONE launch with the reverse of the
+ * moment algebra and the GP link of sr_onestep_reach_vjp
+ *   z_bar = sum_a jac_mu[a] mug_bar[a] + jac_var[a] var_bar[a] + sum_{a,d} jac_z_bar[a][d] hess_mu[a][d],
+ *   mux_bar += Tz^T z_bar[:n_x_in],  kff_bar += z_bar[n_x_in:].
+ * The Hessian term is there only where jac_bar is not zero, mode 1 from a Gaussian start: that case runs sr_gp_linearize_batch,
+ * every other one (mode 2, point starts) sr_gp_predict_grad.  The width of a pass is bounded exactly as in sr_onestep_reach_vjp
+ * (see there), so the same inputs give the same bits for ANY chunk size.  Model rules of sr_gp_linearize_batch in every case:
+ * every kernel identifier, exact and sparse handles, D <= 8 (SR_EUNSUPPORTED beyond).  The GP outputs the step is differentiated
+ * at are those of this pass (equal to the forward's up to the rounding of another route); the clip of the predictive variance
+ * at 1e-15 is ignored.  SR_ESTATE not factorized; SR_EINVAL NULL where required, sigma_x without k_fb / sigma_bar / kfb_bar,
+ * every seed NULL, T < 0, mode outside {1, 2}; T == 0 is a no-op.  Asynchronous on `stream`. */
+int sr_onestep_moments_vjp(sr_gp_t h, long T, int mode, const double* mu_x, const double* sigma_x, const double* k_ff,
+                           const double* k_fb, const double* a, const double* b, const double* mu1_bar,
+                           const double* sigma1_bar, const double* gpvar_bar, double* mux_bar, double* sigma_bar,
+                           double* kff_bar, double* kfb_bar, void* stream);
 
 /* ---- exact moment matching: the GP at Gaussian inputs (beyond the reference, which has the two approximations above) ----
  * For T inputs z ~ N(m[t], S[t]) (m T x D; S T x D x D symmetric PSD, may be singular; NULL = all zero) the exact mean,

@@ -78,6 +78,9 @@ SIGNATURES = {
                                _P, _P]),
     "sr_ellipsoid_step_vjp": (_I, [_I, _L, _I, _I] + [_P] * 11 + [_D] + [_P] * 10),
     "sr_onestep_reach_vjp": (_I, [_H, _L] + [_P] * 8 + [_D] + [_P] * 7),
+    "sr_moment_step_vjp": (_I, [_I, _L, _I, _I, _I] + [_P] * 19),
+    "sr_onestep_moments": (_I, [_H, _L, _I] + [_P] * 10),
+    "sr_onestep_moments_vjp": (_I, [_H, _L, _I] + [_P] * 14),
     "sr_remainder_overapprox": (_I, [_I, _L, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
     "sr_safety_distance": (_I, [_I, _L, _I, _I, _P, _P, _P, _P, _D, _P, _P]),
     "sr_distance_to_center": (_I, [_I, _L, _I, _I, _P, _I, _P, _P, _P, _P]),

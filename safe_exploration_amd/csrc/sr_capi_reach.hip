@@ -1,5 +1,6 @@
 // sr_capi_reach.hip -- reachability entry points: one-step and multi-step ellipsoid propagation, Gaussian moment
-// propagation, the stateless per-query steps (ellipsoid, remainder, safety distance, distance to centre, sampling)
+// propagation, the reverse pass of one step of either, the stateless per-query steps (ellipsoid, remainder, safety distance,
+// distance to centre, sampling)
 // and the dispatch of the persistent chain kernel (sr_chain.hip K0c) with its process-wide launch gate.
 #include "sr_handle.h"
 using namespace srh;
@@ -502,6 +503,140 @@ extern "C" int sr_onestep_reach_vjp(sr_gp_t h, long T, const double* p, const do
         ea.jac_s = jac_s; ea.jz = jz;
         sr_prof_scope ps(&h->prof, SR_K_REACH_VJP, s);
         SR_TRY(sr_launch_reach_vjp(ea, n_s, n_u, s));
+    }
+    return SR_OK;
+}
+
+// ---- moment propagation from a Gaussian state with the GP inside, and the reverse pass of one moment step (sr_moments_vjp.hip) ----
+// The launches of one step of sr_multistep_moments on its per-step route (transformed states, posterior with the Jacobian, the
+// moment step of sr_ellipsoid.hip), from a point or from N(mu_x, sigma_x).
+extern "C" int sr_onestep_moments(sr_gp_t h, long T, int mode, const double* mu_x, const double* sigma_x, const double* k_ff,
+                                  const double* k_fb, const double* a, const double* b, double* mu_out, double* sigma_out,
+                                  double* var_out, void* stream) {
+    SR_CHECK(h != nullptr, SR_EINVAL, "sr_onestep_moments: NULL handle");
+    SR_CHECK(h->factorized, SR_ESTATE, "sr_onestep_moments: model not factorized");
+    SR_CHECK(T >= 0 && (mode == 1 || mode == 2), SR_EINVAL, "sr_onestep_moments: T=%ld mode=%d", T, mode);
+    if (T == 0) return SR_OK;
+    SR_CHECK(mu_x && k_ff && a && b && mu_out && sigma_out, SR_EINVAL, "sr_onestep_moments: NULL argument");
+    SR_CHECK(sigma_x == nullptr || k_fb != nullptr, SR_EINVAL, "sr_onestep_moments: k_fb required with sigma_x");
+    int n_s, n_u;
+    SR_TRY(check_reach_dims(h, &n_s, &n_u));
+    hipStream_t s = (hipStream_t)stream;
+    SR_DEVICE(h->device);
+    h->last_chain = 0;
+    const long nss = (long)n_s * n_s, nus = (long)n_u * n_s;
+    for (long t0 = 0; t0 < T; t0 += h->chunk) {
+        const long Tc = std::min(h->chunk, T - t0);
+        double* var_dst = var_out ? var_out + t0 * n_s : nullptr;
+        SR_TRY(prepare_ws(h, Tc));
+        sr_ws_lock lock(h);
+        if (!var_dst) var_dst = h->var;
+        const double* jac_su = nullptr;
+        SR_TRY(gp_pass_states(h, Tc, mu_x + t0 * n_s, n_s, n_s, k_ff + t0 * n_u, n_u, n_u, h->mu, var_dst, &jac_su, s));
+        sr_ell_args ea;
+        ea.T = Tc; ea.n_s = n_s; ea.n_u = n_u;
+        ea.p = mu_x + t0 * n_s; ea.ldp = n_s;
+        ea.q = sigma_x ? sigma_x + t0 * nss : nullptr; ea.ldq = nss;
+        ea.k_ff = k_ff + t0 * n_u; ea.ldkff = n_u;
+        ea.k_fb = k_fb ? k_fb + t0 * nus : nullptr; ea.ldkfb = nus;
+        ea.mu = h->mu; ea.var = var_dst; ea.jac = jac_su;
+        ea.a = a; ea.b = b; ea.l_mu = a; ea.l_sigma = a; ea.c_safety = 1.0;        // (unused by the moment modes)
+        ea.p_out = mu_out + t0 * n_s; ea.ldpo = n_s;
+        ea.q_out = sigma_out + t0 * nss; ea.ldqo = nss;
+        ea.n_bad = nullptr; ea.mode = mode;
+        sr_prof_scope ps(&h->prof, SR_K_ELL, s);
+        SR_TRY(sr_launch_ellipsoid(ea, s));
+    }
+    return SR_OK;
+}
+
+extern "C" int sr_moment_step_vjp(int device, long T, int n_s, int n_u, int mode, const double* mu_x, const double* sigma_x,
+                                  const double* k_ff, const double* k_fb, const double* mu_g, const double* var_g,
+                                  const double* jac_g, const double* a, const double* b, const double* mu1_bar,
+                                  const double* sigma1_bar, double* mux_bar, double* sigma_bar, double* kff_bar, double* kfb_bar,
+                                  double* mug_bar, double* var_bar, double* jac_bar, void* stream) {
+    SR_CHECK(T >= 0 && (mode == 1 || mode == 2), SR_EINVAL, "sr_moment_step_vjp: T=%ld mode=%d", T, mode);
+    if (T == 0) return SR_OK;
+    SR_CHECK(mu_x && k_ff && mu_g && var_g && a && b && mux_bar && kff_bar && mug_bar && var_bar, SR_EINVAL,
+             "sr_moment_step_vjp: NULL argument");
+    SR_CHECK(sigma_x == nullptr || (k_fb && (mode == 2 || jac_g) && sigma_bar && kfb_bar && jac_bar), SR_EINVAL,
+             "sr_moment_step_vjp: k_fb (and jac_g for the Taylor mode), sigma_bar, kfb_bar and jac_bar required with sigma_x");
+    SR_CHECK(mu1_bar || sigma1_bar, SR_EINVAL, "sr_moment_step_vjp: both seeds NULL");
+    SR_DEVICE(device);
+    sr_momvjp_args ma{};
+    ma.e.T = T; ma.e.q = sigma_x; ma.e.k_fb = k_fb; ma.e.var = var_g; ma.e.jac = jac_g;
+    ma.e.a = a; ma.e.b = b; ma.e.c_safety = 1.0;
+    ma.e.p1_bar = mu1_bar; ma.e.q1_bar = sigma1_bar;
+    ma.e.p_bar = mux_bar; ma.e.q_bar = sigma_bar; ma.e.kff_bar = kff_bar; ma.e.kfb_bar = kfb_bar;
+    ma.e.mu_bar = mug_bar; ma.e.var_bar = var_bar; ma.e.jac_bar = jac_bar;
+    ma.gpvar_bar = nullptr; ma.mode = mode;
+    return sr_launch_moments_vjp(ma, n_s, n_u, (hipStream_t)stream);
+}
+
+// scratch (reach_ws) and passes as sr_onestep_reach_vjp; the Hessian, and with it sr_gp_linearize_batch, only where jac_bar is not
+// zero (mode 1 from a Gaussian start)
+extern "C" int sr_onestep_moments_vjp(sr_gp_t h, long T, int mode, const double* mu_x, const double* sigma_x, const double* k_ff,
+                                      const double* k_fb, const double* a, const double* b, const double* mu1_bar,
+                                      const double* sigma1_bar, const double* gpvar_bar, double* mux_bar, double* sigma_bar,
+                                      double* kff_bar, double* kfb_bar, void* stream) {
+    SR_CHECK(h != nullptr, SR_EINVAL, "sr_onestep_moments_vjp: NULL handle");
+    SR_CHECK(h->factorized, SR_ESTATE, "sr_onestep_moments_vjp: model not factorized");
+    SR_CHECK(T >= 0 && (mode == 1 || mode == 2), SR_EINVAL, "sr_onestep_moments_vjp: T=%ld mode=%d", T, mode);
+    if (T == 0) return SR_OK;
+    SR_CHECK(mu_x && k_ff && a && b && mux_bar && kff_bar, SR_EINVAL, "sr_onestep_moments_vjp: NULL argument");
+    SR_CHECK(sigma_x == nullptr || (k_fb && sigma_bar && kfb_bar), SR_EINVAL,
+             "sr_onestep_moments_vjp: k_fb, sigma_bar and kfb_bar required with sigma_x");
+    SR_CHECK(mu1_bar || sigma1_bar || gpvar_bar, SR_EINVAL, "sr_onestep_moments_vjp: every seed NULL");
+    int n_s, n_u;
+    SR_TRY(check_reach_dims(h, &n_s, &n_u));
+    if (h->D > 8) {                                   // the widths sr_gp_linearize_batch is compiled for
+        sr_set_error("sr_onestep_moments_vjp: D=%d > 8 (the batched linearisation behind it)", h->D);
+        return SR_EUNSUPPORTED;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    SR_DEVICE(h->device);
+    const int D = h->D, n_xin = h->n_xin ? h->n_xin : n_s;
+    const bool second = mode == 1 && sigma_x != nullptr;
+    const long per = sr_reach_vjp_ws_per_query(n_s, n_u, D);
+    // the bound on the width of a pass of sr_onestep_reach_vjp (its comment has the rule and the reason), whichever of the two GP
+    // calls runs: both split their sums by the width of the batch
+    const long k_blocks = std::min(768L / std::max(1, h->Np / 16), 1024L / std::max(1, (h->N + 31) / 32)) / h->n_out;
+    const long pass_max = 256 * std::max(1L, std::min(k_blocks, (long)SR_FINAL_WAVE_T / 256));
+    const long chunk = std::max(1L, std::min({h->chunk, pass_max, ((long)1 << 28) / per}));
+    const long nss = (long)n_s * n_s, nus = (long)n_u * n_s, nd = (long)n_s * D, nds = (long)n_s * (n_s + n_u);
+    const long Tw = std::min(chunk, T);
+    SR_TRY(h->reach_ws.grow((size_t)(Tw * per), wait::stream(s)));
+    double* w = h->reach_ws.get();
+    double* z = w; w += Tw * D;
+    double* mu = w; w += Tw * n_s;
+    double* var = w; w += Tw * n_s;
+    double* jm = w; w += Tw * nd;
+    double* jv = w; w += Tw * nd;
+    double* hm = w; w += Tw * nd * D;
+    double* mug_bar = w; w += Tw * n_s;
+    double* var_bar = w; w += Tw * n_s;
+    double* jac_bar = w; w += Tw * nds;
+    double* jac_s = w; w += Tw * nds;
+    double* jz = w;
+    for (long t0 = 0; t0 < T; t0 += chunk) {
+        const long Tc = std::min(chunk, T - t0);
+        SR_TRY(sr_launch_reach_z(Tc, n_s, n_u, n_xin, mu_x + t0 * n_s, k_ff + t0 * n_u, h->n_xin ? h->Tz : nullptr, z, s));
+        if (second) SR_TRY(sr_gp_linearize_batch(h, z, Tc, mu, var, jm, jv, hm, stream));
+        else SR_TRY(sr_gp_predict_grad(h, z, Tc, mu, var, jm, jv, stream));
+        sr_momvjp_args ma{};
+        ma.e.T = Tc; ma.e.q = sigma_x ? sigma_x + t0 * nss : nullptr; ma.e.k_fb = k_fb ? k_fb + t0 * nus : nullptr;
+        ma.e.var = var; ma.e.jac = jm;                // (identity transform: the GP's Jacobian is the state-space one)
+        ma.e.a = a; ma.e.b = b; ma.e.c_safety = 1.0;
+        ma.e.p1_bar = mu1_bar ? mu1_bar + t0 * n_s : nullptr; ma.e.q1_bar = sigma1_bar ? sigma1_bar + t0 * nss : nullptr;
+        ma.e.p_bar = mux_bar + t0 * n_s; ma.e.q_bar = sigma_bar ? sigma_bar + t0 * nss : nullptr;
+        ma.e.kff_bar = kff_bar + t0 * n_u; ma.e.kfb_bar = kfb_bar ? kfb_bar + t0 * nus : nullptr;
+        ma.e.mu_bar = mug_bar; ma.e.var_bar = var_bar; ma.e.jac_bar = second ? jac_bar : nullptr;
+        ma.e.jac_mu = jm; ma.e.jac_var = jv; ma.e.hess_mu = second ? hm : nullptr;
+        ma.e.Tz = h->n_xin ? h->Tz : nullptr; ma.e.D = D; ma.e.n_xin = n_xin;
+        ma.e.jac_s = jac_s; ma.e.jz = jz;
+        ma.gpvar_bar = gpvar_bar ? gpvar_bar + t0 * n_s : nullptr; ma.mode = mode;
+        sr_prof_scope ps(&h->prof, SR_K_REACH_VJP, s);
+        SR_TRY(sr_launch_moments_vjp(ma, n_s, n_u, s));
     }
     return SR_OK;
 }

@@ -584,6 +584,16 @@ int sr_launch_reach_vjp(const sr_ellvjp_args& a, int n_s, int n_u, hipStream_t s
 // z[t] = [Tz p[t]; k_ff[t]] (T x (n_xin + n_u); Tz NULL: the identity, n_xin = n_s)
 int sr_launch_reach_z(long T, int n_s, int n_u, int n_xin, const double* p, const double* k_ff, const double* Tz, double* z,
                       hipStream_t s);
+// reverse pass of one step in mode 1 / 2 (sr_moments_vjp_dev.h, sr_moments_vjp.hip): the fields of sr_ellvjp_args under the names of
+// the moment step -- q = sigma_x (NULL: point start), var / l_mu / l_sigma / c_safety unread, jac unread in mode 2, p1_bar = mu1_bar,
+// q1_bar = sigma1_bar, p_bar = mux_bar, q_bar = sigma_bar, mu_bar = mug_bar; jac_bar may be NULL where it is zero (point start,
+// mode 2); GP link: jac_mu == NULL: none, hess_mu read in mode 1 with sigma_x only
+struct sr_momvjp_args {
+    sr_ellvjp_args e;
+    const double* gpvar_bar;          // seed on the GP variances (T x n_s) or NULL
+    int mode;                         // 1 Taylor, 2 mean-equivalent
+};
+int sr_launch_moments_vjp(const sr_momvjp_args& m, int n_s, int n_u, hipStream_t s);
 int sr_launch_remainder(long T, int n_s, int n_u, const double* q, const double* k_fb,
                         const double* l_mu, const double* l_sigma, double* u_mu, double* u_sigma,
                         hipStream_t s);

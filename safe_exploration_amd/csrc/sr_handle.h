@@ -138,7 +138,7 @@ struct sr_gp {
     // partial sums of the double sum (sr_mm_ws_per_query doubles each); sr_gp_moment_match_vjp: the same records, mu, V, the
     // contribution records and the row tiles' sums (sr_mmg_ws_per_query doubles each)
     srh::scratch<double> mm_ws;
-    // sr_onestep_reach_vjp: per query of a chunk z, the outputs of sr_gp_linearize_batch at z, the seeds on (mu, var, jac) and the
+    // sr_onestep_reach_vjp, sr_onestep_moments_vjp: per query of a chunk z, the outputs of sr_gp_linearize_batch at z, the seeds on (mu, var, jac) and the
     // two transformed Jacobians (sr_reach_vjp_ws_per_query doubles each)
     srh::scratch<double> reach_ws;
     // sr_gp_remove: per output the coefficient tables of the retired row (3 Np + 4), then the input rows behind it

@@ -14,7 +14,7 @@ Beyond the reference: the reverse pass of ONE step on the device (``ellipsoid_st
 ``onestep_reachability_vjp_batch`` / ``sr_onestep_reach_vjp``) and, on top of it, ``differentiable=True`` on the three batched
 entry points: the forward stays the plain call (the same bits), the backward is the device reverse pass, steps are chained by
 torch autograd.  Gradients reach the centres, shape matrices and controls (and mu, var, jac of ``ellipsoid_step_batch``), not
-the model.  Mode 0 only; D <= 8; no persistent reverse chain.
+the model.  Mode 0 here (the moment modes: uncertainty_propagation_casadi); D <= 8; no persistent reverse chain.
 """
 import ctypes
 

@@ -15,6 +15,13 @@ the Gaussian input z = G x + g0, G = [a_gp_inp_x; K], g0 = [0; k_ff] (``SimpleGP
 covariance across outputs and expected Jacobian V in closed form), and with A = a + b K
 ``mu_new = A mu + b k_ff + mu_g``, ``Sigma_new = (A + V G) Sigma (A + V G)^T + Cov - (V G) Sigma (V G)^T``.
 An initial covariance ``sigma_0`` is supported there.
+
+Beyond the reference as well: the reverse pass of ONE Taylor / mean-equivalent step on the device (``moment_step_vjp_batch`` /
+``sr_moment_step_vjp``, ``onestep_moments_vjp_batch`` / ``sr_onestep_moments_vjp``), the one-step call from a Gaussian state with
+the GP inside (``onestep_moments_batch`` / ``sr_onestep_moments``) and, on top of them, ``differentiable=True`` on
+``moment_step_batch``, ``onestep_moments_batch`` and ``multistep_moments_batch``: the forward stays the plain call (the same
+bits), the backward is the device reverse pass, steps are chained by torch autograd.  Gradients reach the means, covariances and
+controls (and mu_g, var_g, jac_g of ``moment_step_batch``), not the model.  D <= 8; no persistent reverse chain.
 """
 import numpy as np
 import torch
@@ -32,13 +39,36 @@ def _lin(a, b, n_s, n_u):
     return np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
 
 
-def multistep_moments_batch(mu_0, ssm, k_ff, k_fb, a=None, b=None, mode=TAYLOR, a_gp_inp_x=None):
+def multistep_moments_batch(mu_0, ssm, k_ff, k_fb, a=None, b=None, mode=TAYLOR, a_gp_inp_x=None, differentiable=False,
+                            sigma_0=None):
     """T trajectories x H steps.  mu_0 (T,n_s); k_ff (T,H,n_u); k_fb (T,H-1,n_u,n_s); a_gp_inp_x (n_x_in,n_s) or None.
-    Returns mu_all (T,H,n_s), sigma_all (T,H,n_s,n_s), gp_var_all (T,H,n_s)."""
+    Returns mu_all (T,H,n_s), sigma_all (T,H,n_s,n_s), gp_var_all (T,H,n_s).
+    differentiable (tensors only): H differentiable ``onestep_moments_batch`` calls chained in torch and stacked, with an autograd
+    graph from mu_0, sigma_0, k_ff and k_fb to the three results.  Every step is one ``sr_onestep_moments`` call: the
+    launches of the plain call's per-step route (``ssm.set_chain(False)``), so the values are that route's to the bit.
+    sigma_0 (T,n_s,n_s), with differentiable=True only: the roll-out starts from N(mu_0, sigma_0); step 0 has no feedback (a zero
+    gain), as in ``moment_matching_batch``."""
     from .gp_reachability import _input_transform, _reach_dims
     if not isinstance(ssm, SimpleGPModel):
         raise TypeError("multistep_moments_batch needs the HIP SimpleGPModel")
     ssm._need_trained()
+    if differentiable:
+        if not B.is_tensor(mu_0):
+            raise TypeError("differentiable=True needs tensors")
+        if k_ff.dim() != 3:
+            raise ValueError("k_ff must be (T, H, n_u)")
+        H = k_ff.shape[1]
+        mu, sigma, steps = mu_0, sigma_0, []
+        for i in range(H):
+            if i == 0:
+                kfb_i = None if sigma_0 is None else sigma_0.new_zeros((mu_0.shape[0], k_ff.shape[2], mu_0.shape[1]))
+            else:
+                kfb_i = k_fb[:, i - 1]
+            mu, sigma, var = onestep_moments_batch(mu, ssm, k_ff[:, i], sigma, kfb_i, a, b, mode, a_gp_inp_x, differentiable=True)
+            steps.append((mu, sigma, var))
+        return tuple(torch.stack([st[k] for st in steps], dim=1) for k in range(3))
+    if sigma_0 is not None:
+        raise NotImplementedError("sigma_0 needs differentiable=True (the per-step route; sr_multistep_moments starts from a point)")
     as_t = B.is_tensor(mu_0)
     hd = ssm._handle
     dev = hd.device
@@ -66,8 +96,18 @@ def multistep_moments_batch(mu_0, ssm, k_ff, k_fb, a=None, b=None, mode=TAYLOR, 
 
 
 def moment_step_batch(mu_x, k_ff, mu_g, var_g, jac_g, sigma_x=None, k_fb=None, a=None, b=None, mode=TAYLOR,
-                      device=None):
-    """One propagation step for T inputs with caller-supplied GP outputs (any StateSpaceModel)."""
+                      device=None, differentiable=False):
+    """One propagation step for T inputs with caller-supplied GP outputs (any StateSpaceModel).
+    differentiable (tensors only): the outputs, the same bits, carry an autograd graph to mu_x, sigma_x, k_ff, k_fb, mu_g, var_g
+    and jac_g whose backward is ``moment_step_vjp_batch`` (once differentiable)."""
+    if differentiable:
+        if not B.is_tensor(mu_x):
+            raise TypeError("differentiable=True needs tensors")
+        if sigma_x is not None and k_fb is None:
+            raise ValueError("k_fb is required when sigma_x is given")
+        gauss = sigma_x is not None
+        return _MomentStepFn.apply((a, b, mode), mu_x, sigma_x, k_ff, k_fb if gauss else None, mu_g, var_g,
+                                   jac_g if gauss else None)
     as_t = B.is_tensor(mu_x)
     dev = B.resolve_device(mu_x.device if as_t else device)
     mx = B.as_dev(mu_x, dev)
@@ -87,6 +127,181 @@ def moment_step_batch(mu_x, k_ff, mu_g, var_g, jac_g, sigma_x=None, k_fb=None, a
                              B.ptr(tmu), B.ptr(tvar), B.ptr(tjac), B.ptr(ta), B.ptr(tb), B.ptr(mo), B.ptr(so),
                              B.stream_ptr(dev)))
     return (mo, so) if as_t else (B.to_numpy(mo), B.to_numpy(so))
+
+
+def _check_step(mu_x, k_ff, sigma_x, k_fb, mode, n_u=None):
+    """argument checks of the one-step calls, before any device is touched: (T, n_s, n_u)"""
+    if int(mode) not in (TAYLOR, MEAN_EQUIVALENT):
+        raise ValueError("mode must be TAYLOR (1) or MEAN_EQUIVALENT (2), got {}".format(mode))
+    shp = tuple(np.shape(mu_x))
+    if len(shp) != 2:
+        raise ValueError("mu_x must be (T, n_s)")
+    T, n_s = shp
+    kshp = tuple(np.shape(k_ff))
+    if len(kshp) not in (1, 2) or kshp[0] != T or (n_u is not None and int(np.prod(kshp[1:])) != n_u):
+        raise ValueError("k_ff must be (T, {})".format("n_u" if n_u is None else n_u))
+    n_u = int(np.prod(kshp[1:]))
+    if sigma_x is not None:
+        if k_fb is None:
+            raise ValueError("k_fb is required when sigma_x is given")
+        if tuple(np.shape(sigma_x)) != (T, n_s, n_s) or tuple(np.shape(k_fb)) != (T, n_u, n_s):
+            raise ValueError("sigma_x must be (T, {0}, {0}) and k_fb (T, {1}, {0})".format(n_s, n_u))
+    return T, n_s, n_u
+
+
+def _check_seeds(seeds, shapes):
+    if all(s is None for s in seeds):
+        raise ValueError("at least one seed is needed")
+    for s, shape in zip(seeds, shapes):
+        if s is not None and tuple(np.shape(s)) != shape:
+            raise ValueError("a seed must be shaped like its output, {}".format(shape))
+
+
+def moment_step_vjp_batch(mu_x, k_ff, mu_g, var_g, jac_g, mu1_bar=None, sigma1_bar=None, sigma_x=None, k_fb=None, a=None,
+                          b=None, mode=TAYLOR, device=None):
+    """Reverse pass of ``moment_step_batch`` (``sr_moment_step_vjp``): for seeds mu1_bar (T,n_s), sigma1_bar (T,n_s,n_s) on its two
+    outputs (None = zero) the gradients (mux_bar, sigma_bar, kff_bar, kfb_bar, mug_bar, var_bar, jac_bar), shaped like the inputs;
+    sigma_bar, kfb_bar and jac_bar are None at a point start (sigma_x None); jac_bar is zero in the mean-equivalent mode.  Only
+    the symmetric part of sigma1_bar counts, sigma_bar is exactly symmetric.  numpy in -> numpy out, tensors in -> tensors out."""
+    T, n_s, n_u = _check_step(mu_x, k_ff, sigma_x, k_fb, mode)
+    gauss = sigma_x is not None
+    if gauss and int(mode) == TAYLOR and jac_g is None:
+        raise ValueError("jac_g is required when sigma_x is given (Taylor mode)")
+    if tuple(np.shape(mu_g)) != (T, n_s) or tuple(np.shape(var_g)) != (T, n_s):
+        raise ValueError("mu_g and var_g must be (T, {})".format(n_s))
+    if gauss and jac_g is not None and tuple(np.shape(jac_g)) != (T, n_s, n_s + n_u):
+        raise ValueError("jac_g must be (T, {}, {})".format(n_s, n_s + n_u))
+    _check_seeds((mu1_bar, sigma1_bar), ((T, n_s), (T, n_s, n_s)))
+    as_t = B.is_tensor(mu_x)
+    dev = B.resolve_device(mu_x.device if as_t else device)
+    mx, kff = B.as_dev(mu_x, dev), B.as_dev(k_ff, dev, (T, n_u))
+    sx = B.as_dev(sigma_x, dev) if gauss else None
+    kfb = B.as_dev(k_fb, dev) if gauss else None
+    tmu, tvar = B.as_dev(mu_g, dev), B.as_dev(var_g, dev)
+    tjac = B.as_dev(jac_g, dev) if (gauss and jac_g is not None) else None
+    mb, sb = B.as_dev(mu1_bar, dev), B.as_dev(sigma1_bar, dev)
+    a, b = _lin(a, b, n_s, n_u)
+    ta, tb = B.const_dev(a, dev, (n_s, n_s)), B.const_dev(b, dev, (n_s, n_u))
+    outs = [B.empty((T, n_s), dev), B.empty((T, n_s, n_s), dev) if gauss else None, B.empty((T, n_u), dev),
+            B.empty((T, n_u, n_s), dev) if gauss else None, B.empty((T, n_s), dev), B.empty((T, n_s), dev),
+            B.empty((T, n_s, n_s + n_u), dev) if gauss else None]
+    check(lib.sr_moment_step_vjp(dev.index, T, n_s, n_u, int(mode), B.ptr(mx), B.ptr(sx), B.ptr(kff), B.ptr(kfb), B.ptr(tmu),
+                                 B.ptr(tvar), B.ptr(tjac), B.ptr(ta), B.ptr(tb), B.ptr(mb), B.ptr(sb), *[B.ptr(o) for o in outs],
+                                 B.stream_ptr(dev)))
+    return tuple(outs) if as_t else tuple(None if o is None else B.to_numpy(o) for o in outs)
+
+
+def _onestep_setup(name, mu_x, ssm, k_ff, sigma_x, k_fb, a, b, mode, a_gp_inp_x):
+    from .gp_reachability import _reach_dims
+    if not isinstance(ssm, SimpleGPModel):
+        raise TypeError(name + " needs the HIP SimpleGPModel")
+    ssm._need_trained()
+    hd = ssm._handle
+    n_s, n_u = _reach_dims(hd, a_gp_inp_x)
+    T, ns_in, _ = _check_step(mu_x, k_ff, sigma_x, k_fb, mode, n_u)
+    if ns_in != n_s:
+        raise ValueError("mu_x must be (T, {})".format(n_s))
+    dev = hd.device
+    gauss = sigma_x is not None
+    a, b = _lin(a, b, n_s, n_u)
+    return (hd, dev, T, n_s, n_u, B.as_dev(mu_x, dev), B.as_dev(sigma_x, dev) if gauss else None, B.as_dev(k_ff, dev, (T, n_u)),
+            B.as_dev(k_fb, dev) if gauss else None, B.const_dev(a, dev, (n_s, n_s)), B.const_dev(b, dev, (n_s, n_u)))
+
+
+def onestep_moments_batch(mu_x, ssm, k_ff, sigma_x=None, k_fb=None, a=None, b=None, mode=TAYLOR, a_gp_inp_x=None,
+                          differentiable=False):
+    """One Taylor / mean-equivalent step for T states with the GP inside (``sr_onestep_moments``), from points (sigma_x None) or
+    from N(mu_x, sigma_x).  mu_x (T,n_s); k_ff (T,n_u); sigma_x (T,n_s,n_s); k_fb (T,n_u,n_s), required with sigma_x.
+    Returns mu_new (T,n_s), sigma_new (T,n_s,n_s), gp variances (T,n_s).  numpy in -> numpy out, tensors in -> tensors out.
+    differentiable (tensors only): the three outputs, the same bits, carry an autograd graph to mu_x, sigma_x, k_ff and k_fb whose
+    backward is ``onestep_moments_vjp_batch`` (once differentiable; no gradient to the model)."""
+    from .gp_reachability import _input_transform
+    if differentiable:
+        if not isinstance(ssm, SimpleGPModel):
+            raise TypeError("onestep_moments_batch needs the HIP SimpleGPModel")
+        if not B.is_tensor(mu_x):
+            raise TypeError("differentiable=True needs tensors")
+        if sigma_x is not None and k_fb is None:
+            raise ValueError("k_fb is required when sigma_x is given")
+        return _OnestepMomentsFn.apply(ssm, (a, b, mode, a_gp_inp_x), mu_x, sigma_x, k_ff, k_fb if sigma_x is not None else None)
+    as_t = B.is_tensor(mu_x)
+    hd, dev, T, n_s, n_u, mx, sx, kff, kfb, ta, tb = _onestep_setup("onestep_moments_batch", mu_x, ssm, k_ff, sigma_x, k_fb, a, b,
+                                                                    mode, a_gp_inp_x)
+    outs = (B.empty((T, n_s), dev), B.empty((T, n_s, n_s), dev), B.empty((T, n_s), dev))
+    with _input_transform(ssm, a_gp_inp_x):
+        check(lib.sr_onestep_moments(hd.h, T, int(mode), B.ptr(mx), B.ptr(sx), B.ptr(kff), B.ptr(kfb), B.ptr(ta), B.ptr(tb),
+                                     *[B.ptr(o) for o in outs], B.stream_ptr(dev)))
+    return outs if as_t else tuple(B.to_numpy(o) for o in outs)
+
+
+def onestep_moments_vjp_batch(mu_x, ssm, k_ff, mu1_bar=None, sigma1_bar=None, gpvar_bar=None, sigma_x=None, k_fb=None, a=None,
+                              b=None, mode=TAYLOR, a_gp_inp_x=None):
+    """Reverse pass of ``onestep_moments_batch``, GP included (``sr_onestep_moments_vjp``: the GP derivatives at
+    z = [a_gp_inp_x mu_x; k_ff], then one launch with the reverse of the moment algebra and the GP link): for seeds mu1_bar (T,n_s),
+    sigma1_bar (T,n_s,n_s), gpvar_bar (T,n_s) on the three outputs (None = zero) the gradients (mux_bar, sigma_bar, kff_bar,
+    kfb_bar); sigma_bar and kfb_bar are None at a point start.  Models as ``linearize_device_batch`` takes them (every kernel, exact
+    and sparse, D <= 8: NotImplementedError beyond).  numpy in -> numpy out, tensors in -> tensors out."""
+    from .gp_reachability import _input_transform
+    as_t = B.is_tensor(mu_x)
+    hd, dev, T, n_s, n_u, mx, sx, kff, kfb, ta, tb = _onestep_setup("onestep_moments_vjp_batch", mu_x, ssm, k_ff, sigma_x, k_fb, a,
+                                                                    b, mode, a_gp_inp_x)
+    _check_seeds((mu1_bar, sigma1_bar, gpvar_bar), ((T, n_s), (T, n_s, n_s), (T, n_s)))
+    seeds = [B.as_dev(x, dev) for x in (mu1_bar, sigma1_bar, gpvar_bar)]
+    gauss = sx is not None
+    outs = [B.empty((T, n_s), dev), B.empty((T, n_s, n_s), dev) if gauss else None, B.empty((T, n_u), dev),
+            B.empty((T, n_u, n_s), dev) if gauss else None]
+    with _input_transform(ssm, a_gp_inp_x):
+        check(lib.sr_onestep_moments_vjp(hd.h, T, int(mode), B.ptr(mx), B.ptr(sx), B.ptr(kff), B.ptr(kfb), B.ptr(ta), B.ptr(tb),
+                                         *[B.ptr(x) for x in seeds], *[B.ptr(o) for o in outs], B.stream_ptr(dev)))
+    return tuple(outs) if as_t else tuple(None if o is None else B.to_numpy(o) for o in outs)
+
+
+class _MomentStepFn(torch.autograd.Function):
+    """``moment_step_batch(..., differentiable=True)``: the forward is the plain call, the backward ``moment_step_vjp_batch`` at
+    the saved inputs.  Seeds of outputs nobody used arrive as None (= zero, the same bits)."""
+
+    @staticmethod
+    def forward(ctx, cfg, mu_x, sigma_x, k_ff, k_fb, mu_g, var_g, jac_g):
+        a, b, mode = cfg
+        mu1, sigma1 = moment_step_batch(mu_x, k_ff, mu_g, var_g, jac_g, sigma_x, k_fb, a, b, mode)
+        ctx.cfg = cfg
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(mu_x, sigma_x, k_ff, k_fb, mu_g, var_g, jac_g)
+        return mu1, sigma1
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, mu1_bar, sigma1_bar):
+        mu_x, sigma_x, k_ff, k_fb, mu_g, var_g, jac_g = ctx.saved_tensors
+        a, b, mode = ctx.cfg
+        if mu1_bar is None and sigma1_bar is None:
+            return (None,) * 8
+        g = moment_step_vjp_batch(mu_x, k_ff, mu_g, var_g, jac_g, mu1_bar, sigma1_bar, sigma_x, k_fb, a, b, mode)
+        return (None, g[0], g[1], g[2].reshape(k_ff.shape), g[3], g[4], g[5], g[6] if jac_g is not None else None)
+
+
+class _OnestepMomentsFn(torch.autograd.Function):
+    """``onestep_moments_batch(..., differentiable=True)``, likewise over ``onestep_moments_vjp_batch``; the GP variances carry a
+    gradient too (the seed gpvar_bar)."""
+
+    @staticmethod
+    def forward(ctx, ssm, cfg, mu_x, sigma_x, k_ff, k_fb):
+        a, b, mode, a_gp_inp_x = cfg
+        outs = onestep_moments_batch(mu_x, ssm, k_ff, sigma_x, k_fb, a, b, mode, a_gp_inp_x)
+        ctx.ssm, ctx.cfg = ssm, cfg
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(mu_x, sigma_x, k_ff, k_fb)
+        return outs
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, mu1_bar, sigma1_bar, gpvar_bar):
+        mu_x, sigma_x, k_ff, k_fb = ctx.saved_tensors
+        a, b, mode, a_gp_inp_x = ctx.cfg
+        if mu1_bar is None and sigma1_bar is None and gpvar_bar is None:
+            return (None,) * 6
+        g = onestep_moments_vjp_batch(mu_x, ctx.ssm, k_ff, mu1_bar, sigma1_bar, gpvar_bar, sigma_x, k_fb, a, b, mode, a_gp_inp_x)
+        return None, None, g[0], g[1], g[2].reshape(k_ff.shape), g[3]
 
 
 def _one_step(mu_x, ssm, k_ff, sigma_x, k_fb, a, b, a_gp_inp_x, mode):
