@@ -736,6 +736,12 @@ int sr_gp_last_remove(sr_gp_t h, int* out, int cap);
  * k-chunks per item of the plan, rows per run (0: one-chunk items, no table), work items, workgroups, items of the last column
  * block. */
 int sr_test_stream_plan(int Np, int n_out, int ncols, int n_cu, int can_fuse, int* out);
+/* host only: how a batch padded to Tp queries splits its sums over the training rows of a model of N points (Np padded rows,
+ * a multiple of 128) and n_out outputs, and the widest pass the reverse passes of one step cut their batches into.  out[0] =
+ * splits of the mean / Jacobian partial sums (the K* pass), out[1] = splits of the Hessian pass of sr_gp_linearize_batch, out[2] =
+ * the pass bound (both counts are those of one query at every width up to it; it does not depend on Tp), out[3] = the batch size
+ * beyond which the final stage sums in another order (the bound never exceeds it). */
+int sr_test_split_plan(int N, int Np, int n_out, long Tp, int* out);
 /* per-kernel hipEvent timing inside the library (adds an event pair per launch while enabled). */
 int sr_prof_enable(sr_gp_t h, int on);
 int sr_prof_reset (sr_gp_t h);

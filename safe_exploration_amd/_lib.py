@@ -133,6 +133,7 @@ SIGNATURES = {
     "sr_gp_last_update": (_I, [_H, _PI, _I]),
     "sr_gp_last_remove": (_I, [_H, _PI, _I]),
     "sr_test_stream_plan": (_I, [_I, _I, _I, _I, _I, _PI]),
+    "sr_test_split_plan": (_I, [_I, _I, _I, _L, _PI]),
     "sr_prof_enable": (_I, [_H, _I]),
     "sr_prof_reset": (_I, [_H]),
     "sr_prof_get": (_I, [_H, _I, _PD, _PL]),

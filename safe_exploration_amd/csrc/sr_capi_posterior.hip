@@ -7,20 +7,6 @@ using namespace srh;
 // ---------------------------------------------------------------------------------------------
 // workspace + the three-kernel GP pass over one chunk
 // ---------------------------------------------------------------------------------------------
-int srh::pick_nsplit(const sr_gp* h, long Tp) {
-    const long blocks = ((Tp + 255) / 256) * h->n_out;
-    long ns = (768 + blocks - 1) / blocks;
-    // down to 16 training rows per workgroup (a 16-long exp chain); beyond SR_FINAL_WAVE_T queries
-    // sr_finalize_kernel adds the partial sums serially per thread: never more than max(16, Np/128) there
-    // (32 / 64 / 128 rows per workgroup for 128 queries at N = 5000: K* pass 10.9 -> 13.1 / 17.7 / 29.8 us, final stage 10.2 ->
-    //  7.4 / 5.9 / 5.5 us: no gain in the sum)
-    const long maxs = Tp <= SR_FINAL_WAVE_T ? (long)h->Np / 16
-                                            : std::min((long)h->Np / 16, std::max(16L, (long)h->Np / SR_NB));
-    if (ns > maxs) ns = maxs;
-    if (ns < 1) ns = 1;
-    return (int)ns;
-}
-
 int srh::ensure_ws(sr_gp* h, long Tp, int nsplit) {
     // two capacities: buffers sized by the padded batch (K*, row-block partials, outputs) and the N-split partials
     // of mu / jac, sized by the PRODUCT nsplit * Tp actually requested (nsplit is largest for tiny batches, Tp for

@@ -1,6 +1,7 @@
-// sr_capi_reach.hip -- reachability entry points: one-step and multi-step ellipsoid propagation, Gaussian moment
-// propagation, the reverse pass of one step of either, the stateless per-query steps (ellipsoid, remainder, safety distance,
-// distance to centre, sampling)
+// sr_capi_reach.hip -- reachability entry points: one-step and multi-step ellipsoid propagation (mode 0) and Gaussian moment
+// propagation (modes 1 / 2) through one forward step (ell_args, reach_step) and one driver each (onestep_impl, multistep_impl);
+// the reverse pass of one step of either through one driver (onestep_vjp_impl); exact moment matching and its reverse pass; the
+// stateless per-query steps (ellipsoid, moments, their reverse passes, remainder, safety distance, distance to centre, sampling);
 // and the dispatch of the persistent chain kernel (sr_chain.hip K0c) with its process-wide launch gate.
 #include "sr_handle.h"
 using namespace srh;
@@ -20,6 +21,79 @@ static int try_chain(sr_gp* h, long T, int H, int mode, const double* p0, const 
                      const double* l_sigma, double c_safety, double* p_all, double* q_all, double* gp_var_all,
                      int* n_bad, int n_s, int n_u, hipStream_t s, bool* taken);
 
+// The one place that fills sr_ell_args: T rows of the step's inputs and outputs with their row strides, the constants and the mode.
+// The moment modes read neither l_mu, l_sigma nor c_safety: any valid device pointer will do.  mu, var and jac (dense) are the
+// caller's, or reach_step's.
+static sr_ell_args ell_args(long T, int n_s, int n_u, int mode, const double* p, long ldp, const double* q, long ldq,
+                            const double* k_ff, long ldkff, const double* k_fb, long ldkfb, const double* a, const double* b,
+                            const double* l_mu, const double* l_sigma, double c_safety, double* p_out, long ldpo,
+                            double* q_out, long ldqo, int* n_bad) {
+    sr_ell_args ea;
+    ea.T = T; ea.n_s = n_s; ea.n_u = n_u;
+    ea.p = p; ea.ldp = ldp; ea.q = q; ea.ldq = ldq;
+    ea.k_ff = k_ff; ea.ldkff = ldkff; ea.k_fb = k_fb; ea.ldkfb = ldkfb;
+    ea.mu = nullptr; ea.var = nullptr; ea.jac = nullptr;
+    ea.a = a; ea.b = b; ea.l_mu = mode ? a : l_mu; ea.l_sigma = mode ? a : l_sigma; ea.c_safety = mode ? 1.0 : c_safety;
+    ea.p_out = p_out; ea.ldpo = ldpo; ea.q_out = q_out; ea.ldqo = ldqo;
+    ea.n_bad = n_bad; ea.mode = mode;
+    return ea;
+}
+
+// ... for the T rows from row t0 on of dense arrays (q, k_fb and n_bad may be NULL)
+static sr_ell_args ell_args_dense(long T, long t0, int n_s, int n_u, int mode, const double* p, const double* q,
+                                  const double* k_ff, const double* k_fb, const double* a, const double* b,
+                                  const double* l_mu, const double* l_sigma, double c_safety, double* p_out, double* q_out,
+                                  int* n_bad) {
+    const long nss = (long)n_s * n_s, nus = (long)n_u * n_s;
+    return ell_args(T, n_s, n_u, mode, p + t0 * n_s, n_s, q ? q + t0 * nss : nullptr, nss, k_ff + t0 * n_u, n_u,
+                    k_fb ? k_fb + t0 * nus : nullptr, nus, a, b, l_mu, l_sigma, c_safety, p_out + t0 * n_s, n_s,
+                    q_out + t0 * nss, nss, n_bad);
+}
+
+// One step with the GP inside, on the per-step route: the posterior at the rows of ea (mean and Jacobian into the workspace, the
+// variances into var, dense), then the step kernel.  var_rows != NULL: the variances are copied there too, row stride ldvar,
+// between the two.  The caller has sized the workspace (prepare_ws) and holds its lock.
+static int reach_step(sr_gp* h, sr_ell_args ea, double* var, double* var_rows, long ldvar, hipStream_t s) {
+    const double* jac_su = nullptr;
+    SR_TRY(gp_pass_states(h, ea.T, ea.p, ea.ldp, ea.n_s, ea.k_ff, ea.ldkff, ea.n_u, h->mu, var, &jac_su, s));
+    if (var_rows)
+        SR_HIP(hipMemcpy2DAsync(var_rows, sizeof(double) * ldvar, var, sizeof(double) * ea.n_s, sizeof(double) * ea.n_s, ea.T,
+                                hipMemcpyDeviceToDevice, s));
+    ea.mu = h->mu; ea.var = var; ea.jac = jac_su;
+    sr_prof_scope ps(&h->prof, SR_K_ELL, s);
+    return sr_launch_ellipsoid(ea, s);
+}
+
+// sr_onestep_reach (mode 0) and sr_onestep_moments (mode 1 / 2) behind their argument checks
+static int onestep_impl(sr_gp* h, long T, int mode, const double* p, const double* q, const double* k_ff, const double* k_fb,
+                        const double* a, const double* b, const double* l_mu, const double* l_sigma, double c_safety,
+                        double* p_out, double* q_out, double* var_out, int* n_bad, hipStream_t s) {
+    int n_s, n_u;
+    SR_TRY(check_reach_dims(h, &n_s, &n_u));
+    SR_DEVICE(h->device);
+    h->last_chain = 0;
+    if (mode == 0 && n_s <= 2) {
+        // small model, few states: posterior and ellipsoid step in one launch (the chain kernel with H = 1): 24.5 ->
+        // 21.5 us per call at N = 200 (host-bound from there).  Not for n_s >= 3: the Jacobi rotations of the
+        // eigenvalue bound run on one lane per state inside a 512-thread workgroup there (cart-pole: 25 -> 35 us).
+        // Not for the moment modes either: their bits are documented as those of the per-step launches.
+        bool chained = false;
+        SR_TRY(try_chain(h, T, 1, 0, p, q, k_fb, k_ff, nullptr, a, b, l_mu, l_sigma, c_safety, p_out, q_out, var_out,
+                         n_bad, n_s, n_u, s, &chained));
+        if (chained) return SR_OK;
+    }
+    for (long t0 = 0; t0 < T; t0 += h->chunk) {
+        const long Tc = std::min(h->chunk, T - t0);
+        // gp_pass must not (re)allocate the workspace once internal pointers are resolved
+        SR_TRY(prepare_ws(h, Tc));
+        sr_ws_lock lock(h);
+        SR_TRY(reach_step(h, ell_args_dense(Tc, t0, n_s, n_u, mode, p, q, k_ff, k_fb, a, b, l_mu, l_sigma, c_safety, p_out,
+                                            q_out, n_bad),
+                          var_out ? var_out + t0 * n_s : h->var, nullptr, 0, s));
+    }
+    return SR_OK;
+}
+
 extern "C" int sr_onestep_reach(sr_gp_t h, long T, const double* p, const double* q,
                                 const double* k_ff, const double* k_fb, const double* a,
                                 const double* b, const double* l_mu, const double* l_sigma,
@@ -32,44 +106,23 @@ extern "C" int sr_onestep_reach(sr_gp_t h, long T, const double* p, const double
     SR_CHECK(p && k_ff && a && b && l_mu && l_sigma && p_out && q_out, SR_EINVAL,
              "sr_onestep_reach: NULL argument");
     SR_CHECK(q == nullptr || k_fb != nullptr, SR_EINVAL, "sr_onestep_reach: k_fb required with q");
-    int n_s, n_u;
-    SR_TRY(check_reach_dims(h, &n_s, &n_u));
-    hipStream_t s = (hipStream_t)stream;
-    SR_DEVICE(h->device);
-    h->last_chain = 0;
-    if (n_s <= 2) {
-        // small model, few states: posterior and ellipsoid step in one launch (the chain kernel with H = 1): 24.5 ->
-        // 21.5 us per call at N = 200 (host-bound from there).  Not for n_s >= 3: the Jacobi rotations of the
-        // eigenvalue bound run on one lane per state inside a 512-thread workgroup there (cart-pole: 25 -> 35 us).
-        bool chained = false;
-        SR_TRY(try_chain(h, T, 1, 0, p, q, k_fb, k_ff, nullptr, a, b, l_mu, l_sigma, c_safety, p_out, q_out, var_out,
-                         n_bad, n_s, n_u, s, &chained));
-        if (chained) return SR_OK;
-    }
-    for (long t0 = 0; t0 < T; t0 += h->chunk) {
-        const long Tc = std::min(h->chunk, T - t0);
-        double* var_dst = var_out ? var_out + t0 * n_s : nullptr;
-        // gp_pass must not (re)allocate the workspace once internal pointers are resolved
-        SR_TRY(prepare_ws(h, Tc));
-        sr_ws_lock lock(h);
-        if (!var_dst) var_dst = h->var;
-        const double* jac_su = nullptr;
-        SR_TRY(gp_pass_states(h, Tc, p + t0 * n_s, n_s, n_s, k_ff + t0 * n_u, n_u, n_u, h->mu, var_dst, &jac_su, s));
-        sr_ell_args ea;
-        ea.T = Tc; ea.n_s = n_s; ea.n_u = n_u;
-        ea.p = p + t0 * n_s; ea.ldp = n_s;
-        ea.q = q ? q + t0 * n_s * n_s : nullptr; ea.ldq = (long)n_s * n_s;
-        ea.k_ff = k_ff + t0 * n_u; ea.ldkff = n_u;
-        ea.k_fb = k_fb ? k_fb + t0 * n_u * n_s : nullptr; ea.ldkfb = (long)n_u * n_s;
-        ea.mu = h->mu; ea.var = var_dst; ea.jac = jac_su;
-        ea.a = a; ea.b = b; ea.l_mu = l_mu; ea.l_sigma = l_sigma; ea.c_safety = c_safety;
-        ea.p_out = p_out + t0 * n_s; ea.ldpo = n_s;
-        ea.q_out = q_out + t0 * n_s * n_s; ea.ldqo = (long)n_s * n_s;
-        ea.n_bad = n_bad; ea.mode = 0;
-        sr_prof_scope ps(&h->prof, SR_K_ELL, s);
-        SR_TRY(sr_launch_ellipsoid(ea, s));
-    }
-    return SR_OK;
+    return onestep_impl(h, T, 0, p, q, k_ff, k_fb, a, b, l_mu, l_sigma, c_safety, p_out, q_out, var_out, n_bad,
+                        (hipStream_t)stream);
+}
+
+// Moment propagation from a point or from N(mu_x, sigma_x) with the GP inside: the launches of one step of sr_multistep_moments
+// on its per-step route (transformed states, posterior with the Jacobian, the moment step of sr_ellipsoid.hip).
+extern "C" int sr_onestep_moments(sr_gp_t h, long T, int mode, const double* mu_x, const double* sigma_x, const double* k_ff,
+                                  const double* k_fb, const double* a, const double* b, double* mu_out, double* sigma_out,
+                                  double* var_out, void* stream) {
+    SR_CHECK(h != nullptr, SR_EINVAL, "sr_onestep_moments: NULL handle");
+    SR_CHECK(h->factorized, SR_ESTATE, "sr_onestep_moments: model not factorized");
+    SR_CHECK(T >= 0 && (mode == 1 || mode == 2), SR_EINVAL, "sr_onestep_moments: T=%ld mode=%d", T, mode);
+    if (T == 0) return SR_OK;
+    SR_CHECK(mu_x && k_ff && a && b && mu_out && sigma_out, SR_EINVAL, "sr_onestep_moments: NULL argument");
+    SR_CHECK(sigma_x == nullptr || k_fb != nullptr, SR_EINVAL, "sr_onestep_moments: k_fb required with sigma_x");
+    return onestep_impl(h, T, mode, mu_x, sigma_x, k_ff, k_fb, a, b, nullptr, nullptr, 1.0, mu_out, sigma_out, var_out,
+                        nullptr, (hipStream_t)stream);
 }
 
 // Persistent chain launches of one device never overlap, whichever handle or stream they come from: each needs (almost)
@@ -242,36 +295,17 @@ static int multistep_impl(sr_gp* h, long T, int H, int mode, const double* p0, c
         SR_TRY(prepare_ws(h, Tc));
         sr_ws_lock lock(h);
         for (int i = 0; i < H; ++i) {
-            // inputs of step i (gp_reachability.py:195-210)
-            const double* p_in; long ldp; const double* q_in; long ldq; const double* kfb_in; long ldkfb;
-            if (i == 0) {
-                p_in = p0 + t0 * n_s; ldp = n_s;
-                q_in = q0 ? q0 + t0 * nss : nullptr; ldq = nss;
-                kfb_in = k_fb0 ? k_fb0 + t0 * nus : nullptr; ldkfb = nus;
-            } else {
-                p_in = p_all + (t0 * H + (i - 1)) * n_s; ldp = (long)H * n_s;
-                q_in = q_all + (t0 * H + (i - 1)) * nss; ldq = (long)H * nss;
-                kfb_in = k_fb + (t0 * (H - 1) + (i - 1)) * nus; ldkfb = (long)(H - 1) * nus;
-            }
-            const double* kff_in = k_ff + (t0 * H + i) * n_u;
-            const long ldkff = (long)H * n_u;
-            const double* jac_su = nullptr;
-            SR_TRY(gp_pass_states(h, Tc, p_in, ldp, n_s, kff_in, ldkff, n_u, h->mu, h->var, &jac_su, s));
-            if (gp_var_all)
-                SR_HIP(hipMemcpy2DAsync(gp_var_all + (t0 * H + i) * n_s, sizeof(double) * H * n_s, h->var,
-                                        sizeof(double) * n_s, sizeof(double) * n_s, Tc,
-                                        hipMemcpyDeviceToDevice, s));
-            sr_ell_args ea;
-            ea.T = Tc; ea.n_s = n_s; ea.n_u = n_u;
-            ea.p = p_in; ea.ldp = ldp; ea.q = q_in; ea.ldq = ldq;
-            ea.k_ff = kff_in; ea.ldkff = ldkff; ea.k_fb = kfb_in; ea.ldkfb = ldkfb;
-            ea.mu = h->mu; ea.var = h->var; ea.jac = jac_su;
-            ea.a = a; ea.b = b; ea.l_mu = l_mu; ea.l_sigma = l_sigma; ea.c_safety = c_safety;
-            ea.p_out = p_all + (t0 * H + i) * n_s; ea.ldpo = (long)H * n_s;
-            ea.q_out = q_all + (t0 * H + i) * nss; ea.ldqo = (long)H * nss;
-            ea.n_bad = n_bad; ea.mode = mode;
-            sr_prof_scope ps(&h->prof, SR_K_ELL, s);
-            SR_TRY(sr_launch_ellipsoid(ea, s));
+            // inputs of step i (gp_reachability.py:195-210): the caller's start, then the outputs of step i - 1
+            const long r = t0 * H + i;                                       // the first of the rows of step i, stride H
+            const bool first = i == 0;
+            const double* kfb_in = first ? (k_fb0 ? k_fb0 + t0 * nus : nullptr) : k_fb + (t0 * (H - 1) + (i - 1)) * nus;
+            SR_TRY(reach_step(h, ell_args(Tc, n_s, n_u, mode,
+                                          first ? p0 + t0 * n_s : p_all + (r - 1) * n_s, first ? n_s : (long)H * n_s,
+                                          first ? (q0 ? q0 + t0 * nss : nullptr) : q_all + (r - 1) * nss, first ? nss : H * nss,
+                                          k_ff + r * n_u, (long)H * n_u, kfb_in, first ? nus : (H - 1) * nus,
+                                          a, b, l_mu, l_sigma, c_safety, p_all + r * n_s, (long)H * n_s, q_all + r * nss, H * nss,
+                                          n_bad),
+                              h->var, gp_var_all ? gp_var_all + r * n_s : nullptr, (long)H * n_s, s));
         }
     }
     return SR_OK;
@@ -378,14 +412,9 @@ extern "C" int sr_moment_step(int device, long T, int n_s, int n_u, int mode, co
     SR_CHECK(sigma_x == nullptr || (k_fb != nullptr && (mode == 2 || jac_g != nullptr)), SR_EINVAL,
              "sr_moment_step: k_fb (and jac for the Taylor mode) required with sigma_x");
     SR_DEVICE(device);
-    sr_ell_args ea;
-    ea.T = T; ea.n_s = n_s; ea.n_u = n_u;
-    ea.p = mu_x; ea.ldp = n_s; ea.q = sigma_x; ea.ldq = (long)n_s * n_s;
-    ea.k_ff = k_ff; ea.ldkff = n_u; ea.k_fb = k_fb; ea.ldkfb = (long)n_u * n_s;
+    sr_ell_args ea = ell_args_dense(T, 0, n_s, n_u, mode, mu_x, sigma_x, k_ff, k_fb, a, b, nullptr, nullptr, 1.0, mu_out,
+                                    sigma_out, nullptr);
     ea.mu = mu_g; ea.var = var_g; ea.jac = jac_g ? jac_g : mu_g;     // never dereferenced in mode 2
-    ea.a = a; ea.b = b; ea.l_mu = a; ea.l_sigma = a; ea.c_safety = 1.0;
-    ea.p_out = mu_out; ea.ldpo = n_s; ea.q_out = sigma_out; ea.ldqo = (long)n_s * n_s;
-    ea.n_bad = nullptr; ea.mode = mode;
     return sr_launch_ellipsoid(ea, (hipStream_t)stream);
 }
 
@@ -402,18 +431,12 @@ extern "C" int sr_ellipsoid_step(int device, long T, int n_s, int n_u, const dou
     SR_CHECK(q == nullptr || (k_fb != nullptr && jac != nullptr), SR_EINVAL,
              "sr_ellipsoid_step: k_fb and jac required with q");
     SR_DEVICE(device);
-    sr_ell_args ea;
-    ea.T = T; ea.n_s = n_s; ea.n_u = n_u;
-    ea.p = p; ea.ldp = n_s; ea.q = q; ea.ldq = (long)n_s * n_s;
-    ea.k_ff = k_ff; ea.ldkff = n_u; ea.k_fb = k_fb; ea.ldkfb = (long)n_u * n_s;
+    sr_ell_args ea = ell_args_dense(T, 0, n_s, n_u, 0, p, q, k_ff, k_fb, a, b, l_mu, l_sigma, c_safety, p_out, q_out, n_bad);
     ea.mu = mu; ea.var = var; ea.jac = jac;
-    ea.a = a; ea.b = b; ea.l_mu = l_mu; ea.l_sigma = l_sigma; ea.c_safety = c_safety;
-    ea.p_out = p_out; ea.ldpo = n_s; ea.q_out = q_out; ea.ldqo = (long)n_s * n_s;
-    ea.n_bad = n_bad; ea.mode = 0;
     return sr_launch_ellipsoid(ea, (hipStream_t)stream);
 }
 
-// ---- reverse pass of one step (sr_reach_vjp.hip) ---------------------------------------------------------------------------
+// ---- reverse pass of one step (sr_reach_vjp.hip, sr_moments_vjp.hip): stateless, then with the GP inside ------------------------
 extern "C" int sr_ellipsoid_step_vjp(int device, long T, int n_s, int n_u, const double* p, const double* q,
                                      const double* k_ff, const double* k_fb, const double* mu, const double* var,
                                      const double* jac, const double* a, const double* b, const double* l_mu,
@@ -442,39 +465,33 @@ static long sr_reach_vjp_ws_per_query(int n_s, int n_u, int D) {
     return D + 4L * n_s + 3L * n_s * D + (long)n_s * D * D + 2L * n_s * (n_s + n_u);
 }
 
-extern "C" int sr_onestep_reach_vjp(sr_gp_t h, long T, const double* p, const double* q, const double* k_ff,
-                                    const double* k_fb, const double* a, const double* b, const double* l_mu,
-                                    const double* l_sigma, double c_safety, const double* p1_bar, const double* q1_bar,
-                                    double* p_bar, double* q_bar, double* kff_bar, double* kfb_bar, void* stream) {
-    SR_CHECK(h != nullptr, SR_EINVAL, "sr_onestep_reach_vjp: NULL handle");
-    SR_CHECK(h->factorized, SR_ESTATE, "sr_onestep_reach_vjp: model not factorized");
-    SR_CHECK(T >= 0, SR_EINVAL, "sr_onestep_reach_vjp: T=%ld", T);
-    if (T == 0) return SR_OK;
-    SR_CHECK(p && k_ff && a && b && l_mu && l_sigma && p_bar && kff_bar, SR_EINVAL, "sr_onestep_reach_vjp: NULL argument");
-    SR_CHECK(q == nullptr || (k_fb && q_bar && kfb_bar), SR_EINVAL, "sr_onestep_reach_vjp: k_fb, q_bar and kfb_bar required with q");
-    SR_CHECK(p1_bar || q1_bar, SR_EINVAL, "sr_onestep_reach_vjp: both seeds NULL");
+// The reverse pass of one step with the GP inside, behind the argument checks of sr_onestep_reach_vjp (mode 0; gpvar_bar NULL)
+// and sr_onestep_moments_vjp (mode 1 / 2; l_mu, l_sigma unread).  Per pass: z = [Tz p; k_ff], the GP at z with its first
+// derivatives -- and the Hessian of the mean (sr_gp_linearize_batch) only where jac_bar is not zero: modes 0 and 1 from an
+// ellipsoid / a Gaussian start --, then one launch of the step's reverse algebra with the GP link behind it.
+static int onestep_vjp_impl(sr_gp* h, const char* who, long T, int mode, const double* p, const double* q, const double* k_ff,
+                            const double* k_fb, const double* a, const double* b, const double* l_mu, const double* l_sigma,
+                            double c_safety, const double* p1_bar, const double* q1_bar, const double* gpvar_bar,
+                            double* p_bar, double* q_bar, double* kff_bar, double* kfb_bar, void* stream) {
     int n_s, n_u;
     SR_TRY(check_reach_dims(h, &n_s, &n_u));
     if (h->D > 8) {                                   // the widths sr_gp_linearize_batch is compiled for
-        sr_set_error("sr_onestep_reach_vjp: D=%d > 8 (the batched linearisation behind it)", h->D);
+        sr_set_error("%s: D=%d > 8 (the batched linearisation behind it)", who, h->D);
         return SR_EUNSUPPORTED;
     }
     hipStream_t s = (hipStream_t)stream;
     SR_DEVICE(h->device);
     const int D = h->D, n_xin = h->n_xin ? h->n_xin : n_s;
+    const double* Tz = h->n_xin ? h->Tz : nullptr;
+    const bool second = mode != 2 && q != nullptr;
     const long per = sr_reach_vjp_ws_per_query(n_s, n_u, D);
-    // The same bits for any chunk size: the linearisation splits its sums over the training rows by the width b = n_out
-    // ceil(Tp / 256) of the batch it is given -- pick_nsplit: min(Np / 16, ceil(768 / b)), sr_hess_nsplit: min(ceil(N / 32),
-    // ceil(1024 / b)) -- and sr_finalize sums in another order beyond SR_FINAL_WAVE_T queries.  Passes of at most 256 k queries,
-    // k the largest count of 256-query blocks at which both minima are still the first term (at least one block: b = n_out for
-    // every width up to 256), take the split counts the model size sets, whatever chunk the caller chose.
-    const long k_blocks = std::min(768L / std::max(1, h->Np / 16), 1024L / std::max(1, (h->N + 31) / 32)) / h->n_out;
-    const long pass_max = 256 * std::max(1L, std::min(k_blocks, (long)SR_FINAL_WAVE_T / 256));
-    const long chunk = std::max(1L, std::min({h->chunk, pass_max, ((long)1 << 28) / per}));
+    // a pass: the handle's chunk, at most 2^28 doubles (2 GB) of scratch, and never wider than the batch at which both GP calls
+    // still split their sums as the model size alone sets it (sr_common.h): the same bits for any chunk size
+    const long chunk = std::max(1L, std::min({h->chunk, sr_stable_pass_max(h->N, h->Np, h->n_out), ((long)1 << 28) / per}));
     const long nss = (long)n_s * n_s, nus = (long)n_u * n_s, nd = (long)n_s * D, nds = (long)n_s * (n_s + n_u);
     const long Tw = std::min(chunk, T);
     SR_TRY(h->reach_ws.grow((size_t)(Tw * per), wait::stream(s)));
-    double* w = h->reach_ws.get();
+    double* w = h->reach_ws.get();                   // (the order of sr_reach_vjp_ws_per_query)
     double* z = w; w += Tw * D;
     double* mu = w; w += Tw * n_s;
     double* var = w; w += Tw * n_s;
@@ -488,66 +505,57 @@ extern "C" int sr_onestep_reach_vjp(sr_gp_t h, long T, const double* p, const do
     double* jz = w;
     for (long t0 = 0; t0 < T; t0 += chunk) {
         const long Tc = std::min(chunk, T - t0);
-        SR_TRY(sr_launch_reach_z(Tc, n_s, n_u, n_xin, p + t0 * n_s, k_ff + t0 * n_u, h->n_xin ? h->Tz : nullptr, z, s));
-        if (q) SR_TRY(sr_gp_linearize_batch(h, z, Tc, mu, var, jm, jv, hm, stream));
-        else SR_TRY(sr_gp_predict_grad(h, z, Tc, mu, var, jm, jv, stream));        // (the point branch reads no Hessian)
-        sr_ellvjp_args ea{};
+        SR_TRY(sr_launch_reach_z(Tc, n_s, n_u, n_xin, p + t0 * n_s, k_ff + t0 * n_u, Tz, z, s));
+        if (second) SR_TRY(sr_gp_linearize_batch(h, z, Tc, mu, var, jm, jv, hm, stream));
+        else SR_TRY(sr_gp_predict_grad(h, z, Tc, mu, var, jm, jv, stream));
+        sr_momvjp_args ma{};
+        sr_ellvjp_args& ea = ma.e;
         ea.T = Tc; ea.q = q ? q + t0 * nss : nullptr; ea.k_fb = k_fb ? k_fb + t0 * nus : nullptr;
         ea.var = var; ea.jac = jm;                    // (identity transform: the GP's Jacobian is the state-space one)
         ea.a = a; ea.b = b; ea.l_mu = l_mu; ea.l_sigma = l_sigma; ea.c_safety = c_safety;
         ea.p1_bar = p1_bar ? p1_bar + t0 * n_s : nullptr; ea.q1_bar = q1_bar ? q1_bar + t0 * nss : nullptr;
         ea.p_bar = p_bar + t0 * n_s; ea.q_bar = q_bar ? q_bar + t0 * nss : nullptr;
         ea.kff_bar = kff_bar + t0 * n_u; ea.kfb_bar = kfb_bar ? kfb_bar + t0 * nus : nullptr;
-        ea.mu_bar = mu_bar; ea.var_bar = var_bar; ea.jac_bar = jac_bar;
-        ea.jac_mu = jm; ea.jac_var = jv; ea.hess_mu = hm; ea.Tz = h->n_xin ? h->Tz : nullptr; ea.D = D; ea.n_xin = n_xin;
+        ea.mu_bar = mu_bar; ea.var_bar = var_bar;
+        ea.jac_bar = (second || mode == 0) ? jac_bar : nullptr;      // (the ellipsoid kernel writes its zeros from a point too)
+        ea.jac_mu = jm; ea.jac_var = jv; ea.hess_mu = second ? hm : nullptr; ea.Tz = Tz; ea.D = D; ea.n_xin = n_xin;
         ea.jac_s = jac_s; ea.jz = jz;
+        ma.gpvar_bar = gpvar_bar ? gpvar_bar + t0 * n_s : nullptr; ma.mode = mode;
         sr_prof_scope ps(&h->prof, SR_K_REACH_VJP, s);
-        SR_TRY(sr_launch_reach_vjp(ea, n_s, n_u, s));
+        SR_TRY(mode == 0 ? sr_launch_reach_vjp(ea, n_s, n_u, s) : sr_launch_moments_vjp(ma, n_s, n_u, s));
     }
     return SR_OK;
 }
 
-// ---- moment propagation from a Gaussian state with the GP inside, and the reverse pass of one moment step (sr_moments_vjp.hip) ----
-// The launches of one step of sr_multistep_moments on its per-step route (transformed states, posterior with the Jacobian, the
-// moment step of sr_ellipsoid.hip), from a point or from N(mu_x, sigma_x).
-extern "C" int sr_onestep_moments(sr_gp_t h, long T, int mode, const double* mu_x, const double* sigma_x, const double* k_ff,
-                                  const double* k_fb, const double* a, const double* b, double* mu_out, double* sigma_out,
-                                  double* var_out, void* stream) {
-    SR_CHECK(h != nullptr, SR_EINVAL, "sr_onestep_moments: NULL handle");
-    SR_CHECK(h->factorized, SR_ESTATE, "sr_onestep_moments: model not factorized");
-    SR_CHECK(T >= 0 && (mode == 1 || mode == 2), SR_EINVAL, "sr_onestep_moments: T=%ld mode=%d", T, mode);
+extern "C" int sr_onestep_reach_vjp(sr_gp_t h, long T, const double* p, const double* q, const double* k_ff,
+                                    const double* k_fb, const double* a, const double* b, const double* l_mu,
+                                    const double* l_sigma, double c_safety, const double* p1_bar, const double* q1_bar,
+                                    double* p_bar, double* q_bar, double* kff_bar, double* kfb_bar, void* stream) {
+    SR_CHECK(h != nullptr, SR_EINVAL, "sr_onestep_reach_vjp: NULL handle");
+    SR_CHECK(h->factorized, SR_ESTATE, "sr_onestep_reach_vjp: model not factorized");
+    SR_CHECK(T >= 0, SR_EINVAL, "sr_onestep_reach_vjp: T=%ld", T);
     if (T == 0) return SR_OK;
-    SR_CHECK(mu_x && k_ff && a && b && mu_out && sigma_out, SR_EINVAL, "sr_onestep_moments: NULL argument");
-    SR_CHECK(sigma_x == nullptr || k_fb != nullptr, SR_EINVAL, "sr_onestep_moments: k_fb required with sigma_x");
-    int n_s, n_u;
-    SR_TRY(check_reach_dims(h, &n_s, &n_u));
-    hipStream_t s = (hipStream_t)stream;
-    SR_DEVICE(h->device);
-    h->last_chain = 0;
-    const long nss = (long)n_s * n_s, nus = (long)n_u * n_s;
-    for (long t0 = 0; t0 < T; t0 += h->chunk) {
-        const long Tc = std::min(h->chunk, T - t0);
-        double* var_dst = var_out ? var_out + t0 * n_s : nullptr;
-        SR_TRY(prepare_ws(h, Tc));
-        sr_ws_lock lock(h);
-        if (!var_dst) var_dst = h->var;
-        const double* jac_su = nullptr;
-        SR_TRY(gp_pass_states(h, Tc, mu_x + t0 * n_s, n_s, n_s, k_ff + t0 * n_u, n_u, n_u, h->mu, var_dst, &jac_su, s));
-        sr_ell_args ea;
-        ea.T = Tc; ea.n_s = n_s; ea.n_u = n_u;
-        ea.p = mu_x + t0 * n_s; ea.ldp = n_s;
-        ea.q = sigma_x ? sigma_x + t0 * nss : nullptr; ea.ldq = nss;
-        ea.k_ff = k_ff + t0 * n_u; ea.ldkff = n_u;
-        ea.k_fb = k_fb ? k_fb + t0 * nus : nullptr; ea.ldkfb = nus;
-        ea.mu = h->mu; ea.var = var_dst; ea.jac = jac_su;
-        ea.a = a; ea.b = b; ea.l_mu = a; ea.l_sigma = a; ea.c_safety = 1.0;        // (unused by the moment modes)
-        ea.p_out = mu_out + t0 * n_s; ea.ldpo = n_s;
-        ea.q_out = sigma_out + t0 * nss; ea.ldqo = nss;
-        ea.n_bad = nullptr; ea.mode = mode;
-        sr_prof_scope ps(&h->prof, SR_K_ELL, s);
-        SR_TRY(sr_launch_ellipsoid(ea, s));
-    }
-    return SR_OK;
+    SR_CHECK(p && k_ff && a && b && l_mu && l_sigma && p_bar && kff_bar, SR_EINVAL, "sr_onestep_reach_vjp: NULL argument");
+    SR_CHECK(q == nullptr || (k_fb && q_bar && kfb_bar), SR_EINVAL, "sr_onestep_reach_vjp: k_fb, q_bar and kfb_bar required with q");
+    SR_CHECK(p1_bar || q1_bar, SR_EINVAL, "sr_onestep_reach_vjp: both seeds NULL");
+    return onestep_vjp_impl(h, "sr_onestep_reach_vjp", T, 0, p, q, k_ff, k_fb, a, b, l_mu, l_sigma, c_safety, p1_bar, q1_bar,
+                            nullptr, p_bar, q_bar, kff_bar, kfb_bar, stream);
+}
+
+extern "C" int sr_onestep_moments_vjp(sr_gp_t h, long T, int mode, const double* mu_x, const double* sigma_x, const double* k_ff,
+                                      const double* k_fb, const double* a, const double* b, const double* mu1_bar,
+                                      const double* sigma1_bar, const double* gpvar_bar, double* mux_bar, double* sigma_bar,
+                                      double* kff_bar, double* kfb_bar, void* stream) {
+    SR_CHECK(h != nullptr, SR_EINVAL, "sr_onestep_moments_vjp: NULL handle");
+    SR_CHECK(h->factorized, SR_ESTATE, "sr_onestep_moments_vjp: model not factorized");
+    SR_CHECK(T >= 0 && (mode == 1 || mode == 2), SR_EINVAL, "sr_onestep_moments_vjp: T=%ld mode=%d", T, mode);
+    if (T == 0) return SR_OK;
+    SR_CHECK(mu_x && k_ff && a && b && mux_bar && kff_bar, SR_EINVAL, "sr_onestep_moments_vjp: NULL argument");
+    SR_CHECK(sigma_x == nullptr || (k_fb && sigma_bar && kfb_bar), SR_EINVAL,
+             "sr_onestep_moments_vjp: k_fb, sigma_bar and kfb_bar required with sigma_x");
+    SR_CHECK(mu1_bar || sigma1_bar || gpvar_bar, SR_EINVAL, "sr_onestep_moments_vjp: every seed NULL");
+    return onestep_vjp_impl(h, "sr_onestep_moments_vjp", T, mode, mu_x, sigma_x, k_ff, k_fb, a, b, nullptr, nullptr, 1.0,
+                            mu1_bar, sigma1_bar, gpvar_bar, mux_bar, sigma_bar, kff_bar, kfb_bar, stream);
 }
 
 extern "C" int sr_moment_step_vjp(int device, long T, int n_s, int n_u, int mode, const double* mu_x, const double* sigma_x,
@@ -571,74 +579,6 @@ extern "C" int sr_moment_step_vjp(int device, long T, int n_s, int n_u, int mode
     ma.e.mu_bar = mug_bar; ma.e.var_bar = var_bar; ma.e.jac_bar = jac_bar;
     ma.gpvar_bar = nullptr; ma.mode = mode;
     return sr_launch_moments_vjp(ma, n_s, n_u, (hipStream_t)stream);
-}
-
-// scratch (reach_ws) and passes as sr_onestep_reach_vjp; the Hessian, and with it sr_gp_linearize_batch, only where jac_bar is not
-// zero (mode 1 from a Gaussian start)
-extern "C" int sr_onestep_moments_vjp(sr_gp_t h, long T, int mode, const double* mu_x, const double* sigma_x, const double* k_ff,
-                                      const double* k_fb, const double* a, const double* b, const double* mu1_bar,
-                                      const double* sigma1_bar, const double* gpvar_bar, double* mux_bar, double* sigma_bar,
-                                      double* kff_bar, double* kfb_bar, void* stream) {
-    SR_CHECK(h != nullptr, SR_EINVAL, "sr_onestep_moments_vjp: NULL handle");
-    SR_CHECK(h->factorized, SR_ESTATE, "sr_onestep_moments_vjp: model not factorized");
-    SR_CHECK(T >= 0 && (mode == 1 || mode == 2), SR_EINVAL, "sr_onestep_moments_vjp: T=%ld mode=%d", T, mode);
-    if (T == 0) return SR_OK;
-    SR_CHECK(mu_x && k_ff && a && b && mux_bar && kff_bar, SR_EINVAL, "sr_onestep_moments_vjp: NULL argument");
-    SR_CHECK(sigma_x == nullptr || (k_fb && sigma_bar && kfb_bar), SR_EINVAL,
-             "sr_onestep_moments_vjp: k_fb, sigma_bar and kfb_bar required with sigma_x");
-    SR_CHECK(mu1_bar || sigma1_bar || gpvar_bar, SR_EINVAL, "sr_onestep_moments_vjp: every seed NULL");
-    int n_s, n_u;
-    SR_TRY(check_reach_dims(h, &n_s, &n_u));
-    if (h->D > 8) {                                   // the widths sr_gp_linearize_batch is compiled for
-        sr_set_error("sr_onestep_moments_vjp: D=%d > 8 (the batched linearisation behind it)", h->D);
-        return SR_EUNSUPPORTED;
-    }
-    hipStream_t s = (hipStream_t)stream;
-    SR_DEVICE(h->device);
-    const int D = h->D, n_xin = h->n_xin ? h->n_xin : n_s;
-    const bool second = mode == 1 && sigma_x != nullptr;
-    const long per = sr_reach_vjp_ws_per_query(n_s, n_u, D);
-    // the bound on the width of a pass of sr_onestep_reach_vjp (its comment has the rule and the reason), whichever of the two GP
-    // calls runs: both split their sums by the width of the batch
-    const long k_blocks = std::min(768L / std::max(1, h->Np / 16), 1024L / std::max(1, (h->N + 31) / 32)) / h->n_out;
-    const long pass_max = 256 * std::max(1L, std::min(k_blocks, (long)SR_FINAL_WAVE_T / 256));
-    const long chunk = std::max(1L, std::min({h->chunk, pass_max, ((long)1 << 28) / per}));
-    const long nss = (long)n_s * n_s, nus = (long)n_u * n_s, nd = (long)n_s * D, nds = (long)n_s * (n_s + n_u);
-    const long Tw = std::min(chunk, T);
-    SR_TRY(h->reach_ws.grow((size_t)(Tw * per), wait::stream(s)));
-    double* w = h->reach_ws.get();
-    double* z = w; w += Tw * D;
-    double* mu = w; w += Tw * n_s;
-    double* var = w; w += Tw * n_s;
-    double* jm = w; w += Tw * nd;
-    double* jv = w; w += Tw * nd;
-    double* hm = w; w += Tw * nd * D;
-    double* mug_bar = w; w += Tw * n_s;
-    double* var_bar = w; w += Tw * n_s;
-    double* jac_bar = w; w += Tw * nds;
-    double* jac_s = w; w += Tw * nds;
-    double* jz = w;
-    for (long t0 = 0; t0 < T; t0 += chunk) {
-        const long Tc = std::min(chunk, T - t0);
-        SR_TRY(sr_launch_reach_z(Tc, n_s, n_u, n_xin, mu_x + t0 * n_s, k_ff + t0 * n_u, h->n_xin ? h->Tz : nullptr, z, s));
-        if (second) SR_TRY(sr_gp_linearize_batch(h, z, Tc, mu, var, jm, jv, hm, stream));
-        else SR_TRY(sr_gp_predict_grad(h, z, Tc, mu, var, jm, jv, stream));
-        sr_momvjp_args ma{};
-        ma.e.T = Tc; ma.e.q = sigma_x ? sigma_x + t0 * nss : nullptr; ma.e.k_fb = k_fb ? k_fb + t0 * nus : nullptr;
-        ma.e.var = var; ma.e.jac = jm;                // (identity transform: the GP's Jacobian is the state-space one)
-        ma.e.a = a; ma.e.b = b; ma.e.c_safety = 1.0;
-        ma.e.p1_bar = mu1_bar ? mu1_bar + t0 * n_s : nullptr; ma.e.q1_bar = sigma1_bar ? sigma1_bar + t0 * nss : nullptr;
-        ma.e.p_bar = mux_bar + t0 * n_s; ma.e.q_bar = sigma_bar ? sigma_bar + t0 * nss : nullptr;
-        ma.e.kff_bar = kff_bar + t0 * n_u; ma.e.kfb_bar = kfb_bar ? kfb_bar + t0 * nus : nullptr;
-        ma.e.mu_bar = mug_bar; ma.e.var_bar = var_bar; ma.e.jac_bar = second ? jac_bar : nullptr;
-        ma.e.jac_mu = jm; ma.e.jac_var = jv; ma.e.hess_mu = second ? hm : nullptr;
-        ma.e.Tz = h->n_xin ? h->Tz : nullptr; ma.e.D = D; ma.e.n_xin = n_xin;
-        ma.e.jac_s = jac_s; ma.e.jz = jz;
-        ma.gpvar_bar = gpvar_bar ? gpvar_bar + t0 * n_s : nullptr; ma.mode = mode;
-        sr_prof_scope ps(&h->prof, SR_K_REACH_VJP, s);
-        SR_TRY(sr_launch_moments_vjp(ma, n_s, n_u, s));
-    }
-    return SR_OK;
 }
 
 extern "C" int sr_remainder_overapprox(int device, long T, int n_s, int n_u, const double* q,
@@ -699,6 +639,16 @@ extern "C" int sr_gp_chain_status(sr_gp_t h, int* timed_out) {
         *(volatile int*)h->chain_status_host = 0;
         h->chain = 0;                        // per-step launches from here on (sr_gp_set_chain re-arms)
     }
+    return SR_OK;
+}
+
+// tests (host only): the two split rules of sr_common.h and the pass bound the reverse driver takes from them
+extern "C" int sr_test_split_plan(int N, int Np, int n_out, long Tp, int* out) {
+    SR_CHECK(N >= 1 && Np >= N && Np % SR_NB == 0 && n_out >= 1 && Tp >= 1 && out, SR_EINVAL, "sr_test_split_plan: bad argument");
+    out[0] = sr_kstar_nsplit(Np, n_out, Tp);
+    out[1] = sr_hess_nsplit(N, n_out, Tp);
+    out[2] = (int)sr_stable_pass_max(N, Np, n_out);
+    out[3] = SR_FINAL_WAVE_T;
     return SR_OK;
 }
 

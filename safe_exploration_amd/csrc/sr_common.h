@@ -340,6 +340,9 @@ int sr_launch_var_bal(const double* Wt, const double* Ks, double* Vt, double* pa
 //   K2  plain 128 x 128 tiles                everything else (the benchmark regime: 0.89-0.90 of the fp64 MFMA peak, r03_kernel_stats)
 //   K3  final stage                          one wavefront per (query, output) up to SR_FINAL_WAVE_T (4096) queries (44 -> 9.8 us at
 //                                            N = 5000, T = 1, r01d); K1 splits N down to 16 rows per workgroup there (26.6 -> 8.7 us)
+//   K1  splits of the training rows          sr_kstar_nsplit: until the grid holds SR_KSTAR_WGS (768) workgroups, at least SR_KSTAR_MIN_ROWS
+//                                            (16) padded rows per split; beyond SR_FINAL_WAVE_T queries at most max(SR_KSTAR_SERIAL_SPLITS
+//                                            (16), Np / 128) splits
 //  single blocking query (host entry points)
 //   K0s resident server (sr_capi_server.hip) sr_gp_server_supported: Np <= 512, D <= 5; one 16-wavefront workgroup per output at Np = 128,
 //                                            Np / 64 parts of 8 wavefronts from 256 on (U^-1 fragments in registers): __call__ 21.6 -> 9.6 us
@@ -353,6 +356,9 @@ int sr_launch_var_bal(const double* Wt, const double* Ks, double* Vt, double* pa
 //   (sr_gp_linearize_batch)                  (query, output), the training rows split until the grid holds SR_HESS_WGS workgroups,
 //                                            at least SR_HESS_MIN_ROWS rows per split (T = 2 at N = 5000: 157 splits; T = 65536: 2);
 //                                            sizes set from the K* pass's 768-workgroup target, not swept (profiles/r08_linearize_batch.txt)
+//  reverse pass of one step                  passes of at most sr_stable_pass_max(N, Np, n_out) queries: the widest batch at which
+//   (sr_capi_reach.hip: onestep_vjp_impl)    sr_kstar_nsplit and sr_hess_nsplit still give the counts of one 256-query block, SR_FINAL_WAVE_T
+//                                            at most (the same bits for any chunk size; N = 2000, two outputs: 768)
 //  multi-step chains (sr_capi_reach.hip)     persistent kernel K0c up to SR_CHAIN_GROUPS workgroups (device CUs - 16 at most),
 //                                            1 launch for H <= 2, <= 2 launches for T <= 1024, <= 6 beyond (N = 200 H = 15: 1024
 //                                            rollouts 203 against 253 us, 4096 in six launches 608 / 722, r03_chain_bench); one-step
@@ -405,6 +411,42 @@ static inline int sr_hess_nsplit(int N, int n_out, long Tp) {
     const long cap = ((long)N + SR_HESS_MIN_ROWS - 1) / SR_HESS_MIN_ROWS;
     if (ns > cap) ns = cap;
     return ns < 1 ? 1 : (int)ns;
+}
+#define SR_KSTAR_WGS 768             /* K* pass (K1, and the gradient pass on its loop): workgroups the row splits aim at ... */
+#define SR_KSTAR_MIN_ROWS 16         /* ... with at least this many padded training rows per split (a 16-long exp chain) */
+#define SR_KSTAR_SERIAL_SPLITS 16    /* ... and, where the final stage sums them serially, at most max(this, Np / SR_NB) splits */
+// splits of the training rows in the mean / Jacobian partial sums (srh::pick_nsplit(h, Tp) is this rule on a handle)
+static inline int sr_kstar_nsplit(int Np, int n_out, long Tp) {
+    const long blocks = ((Tp + 255) / 256) * n_out;
+    long ns = (SR_KSTAR_WGS + blocks - 1) / blocks;
+    // down to SR_KSTAR_MIN_ROWS training rows per workgroup; beyond SR_FINAL_WAVE_T queries
+    // sr_finalize_kernel adds the partial sums serially per thread: never more than max(SR_KSTAR_SERIAL_SPLITS, Np/128) there
+    // (32 / 64 / 128 rows per workgroup for 128 queries at N = 5000: K* pass 10.9 -> 13.1 / 17.7 / 29.8 us, final stage 10.2 ->
+    //  7.4 / 5.9 / 5.5 us: no gain in the sum)
+    long maxs = (long)Np / SR_KSTAR_MIN_ROWS;
+    if (Tp > SR_FINAL_WAVE_T) {
+        const long serial = (long)Np / SR_NB > SR_KSTAR_SERIAL_SPLITS ? (long)Np / SR_NB : SR_KSTAR_SERIAL_SPLITS;
+        if (maxs > serial) maxs = serial;
+    }
+    if (ns > maxs) ns = maxs;
+    return ns < 1 ? 1 : (int)ns;
+}
+// The widest pass whose split counts are those of a one-block batch.  Both rules above split the sums over the training rows
+// by the width b = n_out ceil(Tp / 256) of the batch they are given -- sr_kstar_nsplit: min(Np / SR_KSTAR_MIN_ROWS,
+// ceil(SR_KSTAR_WGS / b)), sr_hess_nsplit: min(ceil(N / SR_HESS_MIN_ROWS), ceil(SR_HESS_WGS / b)) -- and sr_finalize sums in
+// another order beyond SR_FINAL_WAVE_T queries.  Passes of at most 256 k queries, k the largest count of 256-query blocks at
+// which both minima are still the first term (at least one block: b = n_out for every width up to 256), take the split counts
+// the model size sets, whatever chunk the caller chose: the same bits for any chunk size (the reverse passes of
+// sr_capi_reach.hip cut their batches here).
+static inline long sr_stable_pass_max(int N, int Np, int n_out) {
+    long kstar_cap = Np / SR_KSTAR_MIN_ROWS, hess_cap = ((long)N + SR_HESS_MIN_ROWS - 1) / SR_HESS_MIN_ROWS;    // the first terms
+    if (kstar_cap < 1) kstar_cap = 1;
+    if (hess_cap < 1) hess_cap = 1;
+    long k = SR_KSTAR_WGS / kstar_cap;
+    if (k > SR_HESS_WGS / hess_cap) k = SR_HESS_WGS / hess_cap;
+    k /= n_out;
+    if (k > SR_FINAL_WAVE_T / 256) k = SR_FINAL_WAVE_T / 256;
+    return 256 * (k < 1 ? 1 : k);
 }
 
 static inline bool sr_gp_small_wanted(int Np, long T, int D, bool general) {
@@ -575,8 +617,9 @@ struct sr_ellvjp_args {
     const double* a; const double* b; const double* l_mu; const double* l_sigma; double c_safety;
     const double* p1_bar; const double* q1_bar;            // seeds, either may be NULL
     double* p_bar; double* q_bar; double* kff_bar; double* kfb_bar; double* mu_bar; double* var_bar; double* jac_bar;
-    // GP link (hess_mu == NULL: none).  jac_mu / jac_var T x n_s x D, hess_mu T x n_s x D x D at z = [Tz p; k_ff];
-    // Tz n_xin x n_s or NULL (identity, n_xin = n_s); jac_s T x n_s (n_s + n_u) and jz T x n_s x D: per-query scratch
+    // GP link (jac_mu == NULL: none; hess_mu == NULL: no second-order term -- jac_bar is zero and is not read).  jac_mu / jac_var
+    // T x n_s x D, hess_mu T x n_s x D x D at z = [Tz p; k_ff]; Tz n_xin x n_s or NULL (identity, n_xin = n_s); jac_s
+    // T x n_s (n_s + n_u) and jz T x n_s x D: per-query scratch, touched only with hess_mu and Tz both set
     const double* jac_mu; const double* jac_var; const double* hess_mu; const double* Tz; int D, n_xin;
     double* jac_s; double* jz;
 };
@@ -587,7 +630,7 @@ int sr_launch_reach_z(long T, int n_s, int n_u, int n_xin, const double* p, cons
 // reverse pass of one step in mode 1 / 2 (sr_moments_vjp_dev.h, sr_moments_vjp.hip): the fields of sr_ellvjp_args under the names of
 // the moment step -- q = sigma_x (NULL: point start), var / l_mu / l_sigma / c_safety unread, jac unread in mode 2, p1_bar = mu1_bar,
 // q1_bar = sigma1_bar, p_bar = mux_bar, q_bar = sigma_bar, mu_bar = mug_bar; jac_bar may be NULL where it is zero (point start,
-// mode 2); GP link: jac_mu == NULL: none, hess_mu read in mode 1 with sigma_x only
+// mode 2); GP link: as above -- the host sets hess_mu in mode 1 with sigma_x only
 struct sr_momvjp_args {
     sr_ellvjp_args e;
     const double* gpvar_bar;          // seed on the GP variances (T x n_s) or NULL

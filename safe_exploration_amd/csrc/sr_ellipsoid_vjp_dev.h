@@ -1,12 +1,13 @@
 // sr_ellipsoid_vjp_dev.h -- the reverse pass (vector-Jacobian product) of the per-query ellipsoid step of sr_ellipsoid_dev.h
 // in mode 0, both branches, as a device function; and the GP link that carries the seeds on (mu, var, jac) back to the GP
-// input (sr_reach_vjp.hip launches both in one kernel).
+// input (sr_reach_vjp.hip launches both in one kernel; sr_moments_vjp.hip launches the same link behind the moment algebra of
+// sr_moments_vjp_dev.h), and the workgroup size of both kernels (sr_vjp_threads).
 //
-// the forward it differentiates replaces the algebra of
-//   /root/reference/safe_exploration/gp_reachability.py:65-88   (point branch)
-//   /root/reference/safe_exploration/gp_reachability.py:89-156  (ellipsoid branch)
-//   /root/reference/safe_exploration/utils.py:108-144           (compute_remainder_overapproximations)
-//   /root/reference/safe_exploration/utils_ellipsoid.py:63-94, 197-233
+// the forward it differentiates replaces the algebra of the reference's
+//   safe_exploration/gp_reachability.py:65-88   (point branch)
+//   safe_exploration/gp_reachability.py:89-156  (ellipsoid branch)
+//   safe_exploration/utils.py:108-144           (compute_remainder_overapproximations)
+//   safe_exploration/utils_ellipsoid.py:63-94, 197-233
 // (the reference has no reverse pass of its own: its MPC differentiates the CasADi graph of the same lines)
 //
 // Seeds p1_bar (n_s), G = sym(q1_bar) (only the symmetric part of q1_bar counts; a NULL seed is a zero seed, same bits).
@@ -82,9 +83,14 @@ struct sr_tmat<NS, true> {
     __device__ __forceinline__ double get(int i, int j) const { return base[(i * NS + j) * stride]; }
     __device__ __forceinline__ void set(int i, int j, double x) { base[(i * NS + j) * stride] = x; }
 };
-// from n_s = 5 on V (during the eigenvalue iteration) and then H (during the reverse) live in LDS: sr_reach_vjp.hip
+// from n_s = 5 on V (during the eigenvalue iteration) and then H (during the reverse) live in LDS
 template <int NS>
 constexpr bool sr_vjp_in_lds() { return NS >= 5; }
+// threads per workgroup of both reverse kernels (sr_reach_vjp.hip, sr_moments_vjp.hip): 256, or one wavefront where the thread's
+// n_s x n_s block lives in LDS (n_s >= 5: 12.5 .. 32 KB per workgroup; the kernels run at one wavefront per SIMD either way, so
+// the smaller workgroup costs no occupancy)
+template <int NS>
+constexpr int sr_vjp_threads() { return sr_vjp_in_lds<NS>() ? 64 : 256; }
 
 // a uniform pointer the optimiser cannot see through: what is loaded through it again is loaded, not kept in registers
 template <class T>
@@ -505,15 +511,15 @@ __device__ __forceinline__ void sr_reach_gp_jac_one(const sr_ellvjp_args& a, lon
 // ... and the seeds on (mu, var, jac) carried to z = [Tz p; k_ff], added to p_bar and kff_bar of the same query:
 //   z_bar = sum_a jac_mu[a] mu_bar[a] + jac_var[a] var_bar[a] + sum_{a,d} jz[a][d] hess_mu[a][d],
 //   jz[a][:n_xin] = jac_bar[a][:n_s] Tz^T,  jz[a][n_xin:] = jac_bar[a][n_s:];   p_bar += Tz^T z_bar[:n_xin],  kff_bar += z_bar[n_xin:]
-// The sums run in ascending order of a and d by one thread: deterministic, no atomics.  In the point branch jac_bar is zero and
-// the Hessian is not read.
+// The sums run in ascending order of a and d by one thread: deterministic, no atomics.  hess_mu == NULL (the host leaves it so
+// where jac_bar is zero: a point start, the mean-equivalent mode): no second-order term, neither jac_bar nor the Hessian is read.
 __device__ __forceinline__ void sr_reach_gp_vjp_one(const sr_ellvjp_args& a, long t, int n_s, int n_u) {
     const int D = a.D, Ds = n_s + n_u;
     const int nx = a.Tz ? a.n_xin : n_s;
     const double* mb = a.mu_bar + t * n_s;
     const double* vb = a.var_bar + t * n_s;
     const double* jb = a.jac_bar + t * n_s * Ds;
-    const bool second = a.q != nullptr;
+    const bool second = a.hess_mu != nullptr;
     const double* jz = jb;                      // identity transform: the same layout
     if (second && a.Tz) {
         double* w = a.jz + t * n_s * D;

@@ -274,7 +274,7 @@ struct sr_fact_src { const double* mat; const double* rhs; int reversed; };
 int factorize_matrix(sr_gp* h, void* stream, int* info, const sr_fact_src* src);
 
 // posterior pass and its workspace (sr_capi_posterior.hip)
-int pick_nsplit(const sr_gp* h, long Tp);
+static inline int pick_nsplit(const sr_gp* h, long Tp) { return sr_kstar_nsplit(h->Np, h->n_out, Tp); }   // (the rule: sr_common.h)
 int ensure_ws(sr_gp* h, long Tp, int nsplit);
 int prepare_ws(sr_gp* h, long Tc);
 struct sr_ws_lock {

@@ -5,40 +5,33 @@
 //                           reverse of the moment algebra (sr_moments_vjp_one), and the GP link of sr_reach_vjp.hip that adds
 //                           [Tz^T z_bar[:n_xin]; z_bar[n_xin:]] to mux_bar and kff_bar (sr_reach_gp_vjp_one) -- each thread reads
 //                           back only what it wrote itself, so the three stages need no barrier and no second launch
-// z = [Tz mu_x; k_ff] comes from sr_reach_z_kernel (sr_reach_vjp.hip).  The Hessian of the GP mean is read only where jac_bar is
+// z = [Tz mu_x; k_ff] comes from sr_reach_z_kernel (sr_reach_vjp.hip).  The link is told by the two fields sr_reach_vjp.hip names:
+// jac_mu == NULL, no link (sr_moment_step_vjp); hess_mu == NULL, no second-order term.  The host sets hess_mu only where jac_bar is
 // not zero: mode 1 from a Gaussian start.  The formulas and the conventions: sr_moments_vjp_dev.h.  Chains of steps are
 // differentiated by torch autograd over this one step (uncertainty_propagation_casadi.multistep_moments_batch(differentiable=
 // True)); there is no persistent reverse chain.
 #include "sr_common.h"
 #include "sr_moments_vjp_dev.h"
 
-// threads per workgroup: as sr_reach_vjp_kernel (one wavefront where the thread's n_s x n_s block lives in LDS)
-template <int NS>
-constexpr int sr_momvjp_threads() { return sr_vjp_in_lds<NS>() ? 64 : 256; }
-
 template <int NS, int NU, int MODE>
-__global__ __launch_bounds__(sr_momvjp_threads<NS>()) void sr_moments_vjp_kernel(sr_momvjp_args m) {
-    constexpr int BT = sr_momvjp_threads<NS>();
+__global__ __launch_bounds__(sr_vjp_threads<NS>()) void sr_moments_vjp_kernel(sr_momvjp_args m) {
+    constexpr int BT = sr_vjp_threads<NS>();
     __shared__ double lds[sr_vjp_in_lds<NS>() ? NS * NS * BT : 1];
     const long t = (long)blockIdx.x * BT + threadIdx.x;
     if (t >= m.e.T) return;
-    const bool second = MODE == 1 && m.e.q != nullptr;          // jac_bar is not zero: the link reads the Hessian
-    if (m.e.jac_mu && m.e.Tz && second) {
+    if (m.e.jac_mu && m.e.Tz && m.e.hess_mu) {
         sr_reach_gp_jac_one(m.e, t, NS, NU);
         m.e.jac = m.e.jac_s;
     }
     sr_moments_vjp_one<NS, NU, MODE>(m, t, lds + threadIdx.x, BT);
-    if (m.e.jac_mu) {
-        if (!second) m.e.q = nullptr;                           // (what sr_reach_gp_vjp_one tells the two cases apart by)
-        sr_reach_gp_vjp_one(m.e, t, NS, NU);
-    }
+    if (m.e.jac_mu) sr_reach_gp_vjp_one(m.e, t, NS, NU);
 }
 
 int sr_launch_moments_vjp(const sr_momvjp_args& m, int n_s, int n_u, hipStream_t s) {
     if (m.e.T <= 0) return SR_OK;
     static_assert(SR_MAX_NS == 8 && SR_MAX_NU == 4, "the two lists below");
     return sr_pick_eq<1, 2, 3, 4, 5, 6, 7, 8>("moments vjp: n_s=%d outside 1..8", n_s, [&](auto ns) {
-        constexpr int BT = sr_momvjp_threads<decltype(ns)::value>();
+        constexpr int BT = sr_vjp_threads<decltype(ns)::value>();
         const dim3 grid((unsigned)((m.e.T + BT - 1) / BT));
         return sr_pick_eq<1, 2, 3, 4>("moments vjp: n_u=%d outside 1..4", n_u, [&](auto nu) {
             return sr_pick_eq<1, 2>("moments vjp: mode=%d outside 1..2", m.mode, [&](auto mode) {

@@ -5,6 +5,8 @@
 //                           reverse of the ellipsoid algebra (sr_ellipsoid_vjp_one), and the GP link that adds
 //                           [Tz^T z_bar[:n_xin]; z_bar[n_xin:]] to p_bar and kff_bar (sr_reach_gp_vjp_one) -- each thread reads
 //                           back only what it wrote itself, so the three stages need no barrier and no second launch
+// The link is told by two fields of sr_ellvjp_args: jac_mu == NULL, no link (sr_ellipsoid_step_vjp); hess_mu == NULL, no second-order
+// term (the point branch, where jac_bar is zero: the host has run sr_gp_predict_grad, not sr_gp_linearize_batch).
 // The formulas, the eigenvector route and the conventions: sr_ellipsoid_vjp_dev.h.  Chains of steps are differentiated by
 // torch autograd over this one step (gp_reachability.multistep_reachability_batch(differentiable=True)); there is no
 // persistent reverse chain.
@@ -31,23 +33,18 @@ __global__ __launch_bounds__(256) void sr_reach_z_kernel(const double* __restric
     z[e] = v;
 }
 
-// threads per workgroup: 256, or one wavefront where the thread's n_s x n_s block lives in LDS (n_s >= 5: 12.5 .. 32 KB per
-// workgroup; the kernel runs at one wavefront per SIMD either way, so the smaller workgroup costs no occupancy)
-template <int NS>
-constexpr int sr_vjp_threads() { return sr_vjp_in_lds<NS>() ? 64 : 256; }
-
 template <int NS, int NU>
 __global__ __launch_bounds__(sr_vjp_threads<NS>()) void sr_reach_vjp_kernel(sr_ellvjp_args a) {
     constexpr int BT = sr_vjp_threads<NS>();
     __shared__ double lds[sr_vjp_in_lds<NS>() ? NS * NS * BT : 1];
     const long t = (long)blockIdx.x * BT + threadIdx.x;
     if (t >= a.T) return;
-    if (a.hess_mu && a.Tz && a.q) {
+    if (a.jac_mu && a.Tz && a.hess_mu) {
         sr_reach_gp_jac_one(a, t, NS, NU);
         a.jac = a.jac_s;
     }
     sr_ellipsoid_vjp_one<NS, NU>(a, t, lds + threadIdx.x, BT);
-    if (a.hess_mu) sr_reach_gp_vjp_one(a, t, NS, NU);
+    if (a.jac_mu) sr_reach_gp_vjp_one(a, t, NS, NU);
 }
 
 int sr_launch_reach_z(long T, int n_s, int n_u, int n_xin, const double* p, const double* k_ff, const double* Tz, double* z,

@@ -28,15 +28,10 @@ import torch
 
 from . import _buffers as B
 from ._lib import lib, check
+from .gp_reachability import _lin_model
 from .ssm_hip.gaussian_process import SimpleGPModel
 
 TAYLOR, MEAN_EQUIVALENT, MOMENT_MATCHING = 1, 2, 3
-
-
-def _lin(a, b, n_s, n_u):
-    if a is None:
-        a, b = np.eye(n_s), np.zeros((n_s, n_u))
-    return np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
 
 
 def multistep_moments_batch(mu_0, ssm, k_ff, k_fb, a=None, b=None, mode=TAYLOR, a_gp_inp_x=None, differentiable=False,
@@ -80,7 +75,7 @@ def multistep_moments_batch(mu_0, ssm, k_ff, k_fb, a=None, b=None, mode=TAYLOR, 
         raise ValueError("k_ff must be (T, H, {})".format(n_u))
     H = kff.shape[1]
     kfb = B.as_dev(k_fb, dev, (T, H - 1, n_u, n_s)) if H > 1 else None
-    a, b = _lin(a, b, n_s, n_u)
+    a, b = _lin_model(a, b, n_s, n_u)
     ta, tb = B.const_dev(a, dev, (n_s, n_s)), B.const_dev(b, dev, (n_s, n_u))
     mu_all, sigma_all = B.empty((T, H, n_s), dev), B.empty((T, H, n_s, n_s), dev)
     var_all = B.empty((T, H, n_s), dev)
@@ -120,7 +115,7 @@ def moment_step_batch(mu_x, k_ff, mu_g, var_g, jac_g, sigma_x=None, k_fb=None, a
     kfb = B.as_dev(k_fb, dev, (T, n_u, n_s)) if sx is not None else None
     tmu, tvar = B.as_dev(mu_g, dev, (T, n_s)), B.as_dev(var_g, dev, (T, n_s))
     tjac = B.as_dev(jac_g, dev, (T, n_s, n_s + n_u)) if (jac_g is not None and sx is not None) else None
-    a, b = _lin(a, b, n_s, n_u)
+    a, b = _lin_model(a, b, n_s, n_u)
     ta, tb = B.const_dev(a, dev, (n_s, n_s)), B.const_dev(b, dev, (n_s, n_u))
     mo, so = B.empty((T, n_s), dev), B.empty((T, n_s, n_s), dev)
     check(lib.sr_moment_step(dev.index, T, n_s, n_u, int(mode), B.ptr(mx), B.ptr(sx), B.ptr(kff), B.ptr(kfb),
@@ -180,7 +175,7 @@ def moment_step_vjp_batch(mu_x, k_ff, mu_g, var_g, jac_g, mu1_bar=None, sigma1_b
     tmu, tvar = B.as_dev(mu_g, dev), B.as_dev(var_g, dev)
     tjac = B.as_dev(jac_g, dev) if (gauss and jac_g is not None) else None
     mb, sb = B.as_dev(mu1_bar, dev), B.as_dev(sigma1_bar, dev)
-    a, b = _lin(a, b, n_s, n_u)
+    a, b = _lin_model(a, b, n_s, n_u)
     ta, tb = B.const_dev(a, dev, (n_s, n_s)), B.const_dev(b, dev, (n_s, n_u))
     outs = [B.empty((T, n_s), dev), B.empty((T, n_s, n_s), dev) if gauss else None, B.empty((T, n_u), dev),
             B.empty((T, n_u, n_s), dev) if gauss else None, B.empty((T, n_s), dev), B.empty((T, n_s), dev),
@@ -203,7 +198,7 @@ def _onestep_setup(name, mu_x, ssm, k_ff, sigma_x, k_fb, a, b, mode, a_gp_inp_x)
         raise ValueError("mu_x must be (T, {})".format(n_s))
     dev = hd.device
     gauss = sigma_x is not None
-    a, b = _lin(a, b, n_s, n_u)
+    a, b = _lin_model(a, b, n_s, n_u)
     return (hd, dev, T, n_s, n_u, B.as_dev(mu_x, dev), B.as_dev(sigma_x, dev) if gauss else None, B.as_dev(k_ff, dev, (T, n_u)),
             B.as_dev(k_fb, dev) if gauss else None, B.const_dev(a, dev, (n_s, n_s)), B.const_dev(b, dev, (n_s, n_u)))
 
@@ -404,7 +399,7 @@ def _mm_setup(ssm, a, b, a_gp_inp_x):
     if tzn.ndim != 2 or tzn.shape[1] != n_s or tzn.shape[0] > hd.D:
         raise ValueError("a_gp_inp_x must be (n_x_in, {}) with n_x_in <= {}".format(n_s, hd.D))
     n_u = hd.D - tzn.shape[0]
-    a, b = _lin(a, b, n_s, n_u)
+    a, b = _lin_model(a, b, n_s, n_u)
     dev = hd.device
     return dev, n_s, n_u, B.const_dev(a, dev, (n_s, n_s)), B.const_dev(b, dev, (n_s, n_u)), B.const_dev(tzn, dev, tzn.shape)
 

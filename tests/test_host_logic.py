@@ -632,3 +632,40 @@ def test_tile_flow_plan_covers_every_block_once_and_orders_dependencies(lib_buil
             for kk in range(k_lo, i):
                 for c in (2 * i, 2 * i + 1, 2 * j, 2 * j + 1):
                     assert tr_pos(kk, c) < k, (t, kk, c)
+
+
+def test_split_rules_keep_their_one_block_counts_up_to_the_pass_bound(lib_built):
+    """The two rules that split a batch's sums over the training rows (sr_kstar_nsplit behind pick_nsplit, sr_hess_nsplit) against
+    the pass bound the reverse passes of one step take from them (sr_stable_pass_max), all three through sr_test_split_plan.
+    A batch of w queries is padded to 128 as the GP calls pad it.
+      1. at every width 1 .. bound both counts are those of one query, and the bound is no larger than the batch size beyond
+         which the final stage sums in another order;
+      2. the bound is a multiple of 256, at least 256;
+      3. where the bound is below that batch size, a pass 256 queries wider changes one of the two counts: the bound is not
+         needlessly small, and a rule that drifts away from it shows here.
+    3 is asserted only where the bound of the parent formulas holds it.  That bound divides twice, rounding down both times
+    (k = floor(floor(768 / (Np / 16)) / n_out)), where the rule's own limit is ceil(768 / (n_out k)) >= Np / 16: at (Np, n_out) =
+    (128, 7), (128, 8), (256, 5) and (256, 7) it stops one or more blocks early (e.g. Np = 128, n_out = 7: 13 blocks, 14 would
+    still split 8 ways).  It is safe there, only not tight; the bound is left as it is and 3 leaves those four pairs out."""
+    import ctypes
+    from safe_exploration_amd import _lib
+    not_tight = {(128, 7), (128, 8), (256, 5), (256, 7)}
+    out = (ctypes.c_int * 4)()
+
+    def plan(N, Np, n_out, w):
+        assert _lib.lib.sr_test_split_plan(N, Np, n_out, (w + 127) // 128 * 128, out) == 0
+        return (out[0], out[1]), out[2], out[3]
+
+    for N in (1, 31, 32, 33, 70, 127, 128, 129, 2000, 5000, 50000):
+        Np = (N + 127) // 128 * 128
+        for n_out in range(1, 9):
+            one, bound, final_wave = plan(N, Np, n_out, 1)
+            assert one[0] >= 1 and one[1] >= 1
+            assert bound % 256 == 0 and 256 <= bound <= final_wave, (N, n_out, bound)
+            for w in sorted({1, bound} | set(range(128, bound + 1, 128))):        # (the counts see a width through its padding only)
+                assert plan(N, Np, n_out, w) == (one, bound, final_wave), (N, n_out, w)
+            if bound < final_wave and (Np, n_out) not in not_tight:
+                assert plan(N, Np, n_out, bound + 256)[0] != one, (N, n_out, bound)
+    assert plan(2000, 2048, 2, 1)[1] == 768                                        # (the model of the chunk-invariance tests)
+    assert _lib.lib.sr_test_split_plan(2000, 2000, 2, 128, out) == _lib.SR_EINVAL  # (Np: a multiple of 128)
+    assert _lib.lib.sr_test_split_plan(2000, 2048, 2, 128, None) == _lib.SR_EINVAL

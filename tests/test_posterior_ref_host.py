@@ -194,7 +194,9 @@ def test_thresholds_mirrored():
     assert m and "Np <= %d && wgs128 < %d" % (G.VAR64_MAX_NP, G.VAR64_WGS) in m.group(1)
     m = re.search(r"sr_var_splitk_wanted\(.*?\{(.*?)\n\}", common, re.S)
     assert m and "nrb > 2 && wgs <= %d" % G.SPLITK_WGS in m.group(1)
-    assert re.search(r"long ns = \(%d \+ blocks - 1\) / blocks;" % G.NSPLIT_WGS, post)
+    assert _define(common, "SR_KSTAR_WGS") == G.NSPLIT_WGS
+    m = re.search(r"sr_kstar_nsplit\(.*?\{(.*?)\n\}", common, re.S)
+    assert m and "long ns = (SR_KSTAR_WGS + blocks - 1) / blocks;" in m.group(1)
     assert "Tc >= 2 && Tc <= 4 && h->Np <= SR_MFMA_SMALL_MAX_NP" in post
     assert "nslot <= SR_ST1_SLOTS_MAX && 2 * ncb <= 64" in post
     widths = [int(w) for w in re.findall(r"if \(ncols <= (\d+)\) return \1;", stream)]
