@@ -3,7 +3,8 @@ x+ = a x + b (K x + k_ff) + g([x; u]), against the two approximations (first-ord
 
     python examples/moment_matching.py
 
-Needs a GPU: the GP is evaluated by sr_gp_moment_match (mean, FULL output covariance and expected Jacobian in closed form)."""
+Needs a GPU: the GP is evaluated by sr_gp_moment_match (mean, FULL output covariance and expected Jacobian in closed form), for
+an ARD-RBF model and for a "lin_rbf" model."""
 import os
 import sys
 
@@ -47,6 +48,18 @@ def main():
         torch.as_tensor(-0.3 * np.ones((T, H - 1, n_u, n_s)), device=dev), a, b,
         sigma_0=torch.as_tensor(np.tile(sigma_0, (T, 1, 1)), device=dev))
     print("\nbatch:", tuple(mu_all.shape), tuple(sigma_all.shape), tuple(cov_all.shape))
+
+    # the same roll-out with the reference's "lin_rbf" kernel (linear x RBF on input dimension 1 + ARD linear): a near-linear
+    # plant, whose linear part the kernel carries; the closed form exists for it too (a Matern kernel has none)
+    Yl = Y + Z.dot(np.array([[0.1, 0.0], [0.0, 0.1], [0.05, -0.05]]))
+    hyp_l = [{"prod.rbf.lengthscale": 0.8, "prod.rbf.variance": 0.05, "prod.linear.variances": 1.0,
+              "linear.variances": np.full(n_s + n_u, 0.02), "noise_variance": 1e-4} for _ in range(n_s)]
+    gp_l = SimpleGPModel(n_s, n_s, n_u, kern_types=["lin_rbf"] * n_s, hyp=hyp_l)
+    gp_l.train(Z, Yl, opt_hyp=False)
+    ml_mu, ml_sigma, _ = up.multi_step_moment_matching(mu_0, gp_l, k_ff, k_fb, sigma_0, a, b)
+    print("\nlin_rbf model:  step  mean                      trace Sigma")
+    for i in range(H):
+        print("%20d  %-24s  %.6f" % (i, np.array2string(ml_mu[i], precision=4), np.trace(ml_sigma[i].reshape(n_s, n_s))))
 
 
 if __name__ == "__main__":

@@ -385,14 +385,19 @@ int sr_onestep_moments_vjp(sr_gp_t h, long T, int mode, const double* mu_x, cons
 
 /* ---- exact moment matching: the GP at Gaussian inputs (beyond the reference, which has the two approximations above) ----
  * For T inputs z ~ N(m[t], S[t]) (m T x D; S T x D x D symmetric PSD, may be singular; NULL = all zero) the exact mean,
- * the FULL covariance across outputs and the expected Jacobian of an ARD-RBF model (Deisenroth's closed forms):
+ * the FULL covariance across outputs and the expected Jacobian of an ARD-RBF model (Deisenroth's closed forms), or of a
+ * general-family model (sr_gp_set_data_general) whose radial part is the RBF (kappa id 0) on EVERY output -- the reference's
+ * lin_rbf, and rbf outputs beside it: a polynomial of degree <= 1 times a Gaussian plus a bilinear term, whose expectations are
+ * Gaussian moments of order <= 2 (entries of s may be zero; nothing inverts S or diag(s^2)):
  *   mu T x n_out ; cov T x n_out x n_out (exactly symmetric, diagonal clipped at 1e-15; exactly zero off the diagonal where
  *   S[t] == 0) ; V T x n_out x D (may be NULL): cov(z, g_a) = S V_a, and V_a -> d mu_a/dx as S -> 0.
  * inv_k n_out x N x N: the matrices sr_gp_inv_k writes, back to back (on a sparse handle: P P^T, the matrix of its variance).
- * Cost: T n_out (n_out + 1) / 2 N^2 evaluations of exp; queries go through in chunks of sr_gp_set_chunk with a grow-only
- * scratch owned by the handle (freed by sr_gp_release_scratch).  Asynchronous on `stream`; the same inputs give the same bits.
- * SR_ESTATE not factorized; SR_EUNSUPPORTED a general-family model (the closed form is for ARD-RBF only);
- * SR_EINVAL NULL argument or T < 0; T == 0 is a no-op. */
+ * Cost: T n_out (n_out + 1) / 2 N^2 evaluations of exp (general family: about twice the time per evaluation, and once per call
+ * the products inv_k Z, O(n_out N^2 D)); queries go through in chunks of sr_gp_set_chunk with a grow-only scratch owned by the
+ * handle (freed by sr_gp_release_scratch).  Asynchronous on `stream` (the first call after sr_gp_set_data_general reads the
+ * radial identifiers back: one blocking copy); the same inputs give the same bits, for any chunk size.
+ * SR_ESTATE not factorized; SR_EUNSUPPORTED a general-family model with a Matern output (no closed form; the error text names
+ * ARD-RBF); SR_EINVAL NULL argument or T < 0; T == 0 is a no-op. */
 int sr_gp_moment_match(sr_gp_t h, const double* m, const double* S, long T, const double* inv_k,
                        double* mu, double* cov, double* V, void* stream);
 /* Its reverse pass (vector-Jacobian product): for seeds mu_bar T x n_out, cov_bar T x n_out x n_out, V_bar T x n_out x D (any of
@@ -404,7 +409,8 @@ int sr_gp_moment_match(sr_gp_t h, const double* m, const double* S, long T, cons
  * diagonal at 1e-15 is ignored by the derivative, and so is the exact zero the forward writes off the diagonal at S == 0:
  * d cov_ab / dS is not zero there, so the pair sums run for every pair.  Nothing inverts S: singular and zero S are fine.
  * Cost: T n_out^2 N^2 evaluations of exp (about four forward calls); chunks, scratch, determinism (the same bits for any
- * chunk size) and refusals as sr_gp_moment_match; SR_EINVAL also when both outputs are NULL.  Asynchronous on `stream`. */
+ * chunk size) and refusals as sr_gp_moment_match, except that EVERY general-family handle is SR_EUNSUPPORTED: the reverse pass
+ * of the family is not provided.  SR_EINVAL also when both outputs are NULL.  Asynchronous on `stream`. */
 int sr_gp_moment_match_vjp(sr_gp_t h, const double* m, const double* S, long T, const double* inv_k,
                            const double* mu_bar, const double* cov_bar, const double* V_bar,
                            double* m_bar, double* S_bar, void* stream);

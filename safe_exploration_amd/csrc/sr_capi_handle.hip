@@ -311,7 +311,7 @@ extern "C" int sr_gp_set_data_general(sr_gp_t h, const double* Z, const double* 
     hipLaunchKernelGGL(sr_pack_y_kernel, dim3((h->Np + 255) / 256, h->n_out), dim3(256), 0, s, Y,
                        h->yT, h->N, h->Np, h->n_out);
     SR_HIP(hipGetLastError());
-    h->general = 1;
+    h->general = 1; h->gen_rbf = -1;
     h->sf2_host.clear(); h->noise_host.clear();
     h->have_data = 1;
     h->factorized = 0; h->logdet_valid = 0; h->sparse = 0;

@@ -343,21 +343,61 @@ extern "C" int sr_multistep_moments(sr_gp_t h, long T, int H, int mode, const do
                           gp_var_all, nullptr, (hipStream_t)stream);
 }
 
-// exact moment matching (sr_moment_match.hip).  Reads the model where the handle holds it (alpha may be a slid view: single
+// sr_gp_set_data_general leaves the radial identifiers on the device: read them once per data set (one blocking copy of the
+// packed parameters behind `s`) -> h->gen_rbf = every output has kappa id 0
+static int general_radial_is_rbf(sr_gp_t h, hipStream_t s) {
+    if (h->gen_rbf >= 0) return SR_OK;
+    std::vector<double> kp((size_t)h->n_out * SR_KP(h->D));
+    SR_HIP(hipMemcpyAsync(kp.data(), h->kp, sizeof(double) * kp.size(), hipMemcpyDeviceToHost, s));
+    SR_HIP(hipStreamSynchronize(s));
+    int rbf = 1;
+    for (int o = 0; o < h->n_out; ++o)
+        if (kp[(size_t)o * SR_KP(h->D)] != 0.0) rbf = 0;
+    h->gen_rbf = rbf;
+    return SR_OK;
+}
+
+// the general family with the RBF radial part (sr_moment_match_gen.hip): the scratch holds the per-call block (Kinv Z,
+// Z^T Kinv Z, Z^T alpha of every output) in front of the chunk's records
+static int moment_match_general(sr_gp_t h, const double* m, const double* S, long T, const double* inv_k, double* mu,
+                                double* cov, double* V, hipStream_t s) {
+    const long per = sr_mmx_ws_per_query(h->N, h->D, h->n_out), head = sr_mmx_call_ws(h->N, h->D, h->n_out);
+    const long chunk = std::max(1L, std::min({h->chunk, sr_mmx_max_queries(h->N, h->n_out), ((long)1 << 28) / per}));
+    const long DD = (long)h->D * h->D, nn = (long)h->n_out * h->n_out;
+    SR_TRY(h->mm_ws.grow((size_t)(head + std::min(chunk, T) * per), wait::stream(s)));
+    double* call = h->mm_ws.get();
+    SR_TRY(sr_launch_moment_match_gen_call(h->Z, h->alpha, h->kp, h->N, h->Np, h->D, h->n_out, inv_k, call, s));
+    for (long t0 = 0; t0 < T; t0 += chunk) {
+        const long Tc = std::min(chunk, T - t0);
+        SR_TRY(sr_launch_moment_match_gen(h->Z, h->alpha, h->kp, h->N, h->Np, h->D, h->n_out, m + t0 * h->D,
+                                          S ? S + t0 * DD : nullptr, Tc, inv_k, mu + t0 * h->n_out, cov + t0 * nn,
+                                          V ? V + t0 * h->n_out * h->D : nullptr, call, call + head, s));
+    }
+    return SR_OK;
+}
+
+// exact moment matching (sr_moment_match.hip; sr_moment_match_gen.hip for a general-family handle whose outputs all have the
+// RBF radial part).  Reads the model where the handle holds it (alpha may be a slid view: single
 // doubles are loaded, no unslide()); writes nothing into the handle but the grow-only scratch.
 extern "C" int sr_gp_moment_match(sr_gp_t h, const double* m, const double* S, long T, const double* inv_k, double* mu,
                                   double* cov, double* V, void* stream) {
     SR_CHECK(h != nullptr, SR_EINVAL, "sr_gp_moment_match: NULL handle");
     SR_CHECK(h->factorized, SR_ESTATE, "sr_gp_moment_match: model not factorized");
+    hipStream_t s = (hipStream_t)stream;
     if (h->general) {
-        sr_set_error("sr_gp_moment_match: the closed form is for ARD-RBF models only (data set with sr_gp_set_data)");
-        return SR_EUNSUPPORTED;
+        SR_DEVICE(h->device);
+        SR_TRY(general_radial_is_rbf(h, s));
+        if (!h->gen_rbf) {
+            sr_set_error("sr_gp_moment_match: the closed form is for ARD-RBF models and the general family with the RBF "
+                         "radial part only (a Matern output has none)");
+            return SR_EUNSUPPORTED;
+        }
     }
     SR_CHECK(T >= 0, SR_EINVAL, "sr_gp_moment_match: T=%ld", T);
     if (T == 0) return SR_OK;
     SR_CHECK(m && inv_k && mu && cov, SR_EINVAL, "sr_gp_moment_match: NULL argument");
-    hipStream_t s = (hipStream_t)stream;
     SR_DEVICE(h->device);
+    if (h->general) return moment_match_general(h, m, S, T, inv_k, mu, cov, V, s);
     const long per = sr_mm_ws_per_query(h->N, h->D, h->n_out);
     // a chunk: the handle's, what the launch grid takes, and at most 2^28 doubles (2 GB) of scratch
     const long chunk = std::max(1L, std::min({h->chunk, sr_mm_max_queries(h->N, h->n_out), ((long)1 << 28) / per}));
@@ -379,7 +419,7 @@ extern "C" int sr_gp_moment_match_vjp(sr_gp_t h, const double* m, const double* 
     SR_CHECK(h != nullptr, SR_EINVAL, "sr_gp_moment_match_vjp: NULL handle");
     SR_CHECK(h->factorized, SR_ESTATE, "sr_gp_moment_match_vjp: model not factorized");
     if (h->general) {
-        sr_set_error("sr_gp_moment_match_vjp: the closed form is for ARD-RBF models only (data set with sr_gp_set_data)");
+        sr_set_error("sr_gp_moment_match_vjp: the reverse pass is for ARD-RBF models only (data set with sr_gp_set_data)");
         return SR_EUNSUPPORTED;
     }
     SR_CHECK(T >= 0, SR_EINVAL, "sr_gp_moment_match_vjp: T=%ld", T);

@@ -192,6 +192,17 @@ int sr_launch_moment_match_vjp(const double* Z, const double* alpha, const doubl
                                int D, int n_out, const double* m, const double* S, long T, const double* inv_k,
                                const double* mu_bar, const double* cov_bar, const double* V_bar, double* m_bar,
                                double* S_bar, double* ws, hipStream_t s);
+// the same for the general family with the RBF radial part on every output (sr_moment_match_gen.hip; kp n_out x SR_KP(D)):
+// once per call the query-independent block `call` (sr_mmx_call_ws doubles), then chunks of T <= sr_mmx_max_queries queries
+// with ws: T x sr_mmx_ws_per_query doubles
+long sr_mmx_call_ws(int N, int D, int n_out);
+long sr_mmx_ws_per_query(int N, int D, int n_out);
+long sr_mmx_max_queries(int N, int n_out);
+int sr_launch_moment_match_gen_call(const double* Z, const double* alpha, const double* kp, int N, int Np, int D, int n_out,
+                                    const double* inv_k, double* call, hipStream_t s);
+int sr_launch_moment_match_gen(const double* Z, const double* alpha, const double* kp, int N, int Np, int D, int n_out,
+                               const double* m, const double* S, long T, const double* inv_k, double* mu, double* cov,
+                               double* V, const double* call, double* ws, hipStream_t s);
 int sr_launch_fill(double* p, size_t n, double v, hipStream_t s);
 // Wt = J U^T J from the factor as the model update leaves it (diagonal 128-blocks in U, block rows in W; sr_sparse.hip);
 // nbatch members, U / W sS and Wt sD doubles apart

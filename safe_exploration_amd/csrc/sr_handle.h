@@ -107,6 +107,7 @@ struct sr_gp {
     int chain_test_drop = 0;                                              // sr_test_chain_drop
     unsigned* call_ticket = nullptr;        // sr_gp_call1: workgroups done (reset by the last one)
     int general = 0;
+    int gen_rbf = -1;        // general: every output has the RBF radial part (kappa id 0); -1 = not read yet (sr_gp_moment_match)
     int have_data = 0, factorized = 0;
     int sparse = 0;          // the posterior is that of sr_gp_fit_sparse: Wt Wt^T = K_uu^-1 - Sigma^-1, not K_y^-1
     int import_open = 0;     // between sr_gp_import_begin and sr_gp_import_end
@@ -136,7 +137,8 @@ struct sr_gp {
     srh::scratch<double> sel_L, sel_ws;
     // sr_gp_moment_match: per query of a chunk the D x D algebra of every output and pair of outputs, and the row tiles'
     // partial sums of the double sum (sr_mm_ws_per_query doubles each); sr_gp_moment_match_vjp: the same records, mu, V, the
-    // contribution records and the row tiles' sums (sr_mmg_ws_per_query doubles each)
+    // contribution records and the row tiles' sums (sr_mmg_ws_per_query doubles each); a general-family handle: the per-call
+    // block (sr_mmx_call_ws doubles) in front of the chunk's records (sr_mmx_ws_per_query doubles per query)
     srh::scratch<double> mm_ws;
     // sr_onestep_reach_vjp, sr_onestep_moments_vjp: per query of a chunk z, the outputs of sr_gp_linearize_batch at z, the seeds on (mu, var, jac) and the
     // two transformed Jacobians (sr_reach_vjp_ws_per_query doubles each)

@@ -912,10 +912,13 @@ class SimpleGPModel(StateSpaceModel):
             self._inv_K_dev = t
         return self._inv_K_dev
 
-    def _mm_inputs(self, m, S):
+    def _mm_inputs(self, m, S, reverse=False):
         self._need_trained()
-        if any(kt != "rbf" for kt in self.kern_types):
-            raise NotImplementedError("moment matching: the closed form is for ARD-RBF models only")
+        if any(kt not in ("rbf", "lin_rbf") for kt in self.kern_types):
+            raise NotImplementedError("moment matching: the closed form is for ARD-RBF and lin_rbf models only "
+                                      "(a Matern kernel has none)")
+        if reverse and any(kt != "rbf" for kt in self.kern_types):
+            raise NotImplementedError("moment matching: the reverse pass is for ARD-RBF models only")
         hd = self._handle
         tm = B.as_dev(m, hd.device)
         if tm.dim() != 2 or tm.shape[1] != hd.D:
@@ -928,10 +931,14 @@ class SimpleGPModel(StateSpaceModel):
         """Exact moment matching on device tensors (``sr_gp_moment_match``): the GP at T Gaussian inputs z ~ N(m[t], S[t]).
         m (T, D); S (T, D, D) symmetric PSD (may be singular) or None = point inputs.
         Returns mu (T, n), cov (T, n, n) -- the full covariance across outputs -- and V (T, n, D) with cov(z, g_a) = S V_a
-        (V -> the mean Jacobian as S -> 0).  ARD-RBF models only (NotImplementedError otherwise).  Asynchronous.
+        (V -> the mean Jacobian as S -> 0).  Models whose kernels are all "rbf" or "lin_rbf" (NotImplementedError for a Matern
+        kernel, which has no closed form); a model with a "lin_rbf" output goes through the general-family route.  Asynchronous.
         ``differentiable=True``: the same three tensors (the same bits), hanging on a ``torch.autograd.Function`` whose
-        backward is ``moment_match_vjp_device`` (once differentiable; gradients in m and S, not in the model)."""
+        backward is ``moment_match_vjp_device`` (once differentiable; gradients in m and S, not in the model).  ARD-RBF
+        models only: the reverse pass of the general family is not provided (NotImplementedError before any launch)."""
         if differentiable:
+            if any(kt != "rbf" for kt in self.kern_types):
+                raise NotImplementedError("moment matching: the reverse pass is for ARD-RBF models only")
             return _MomentMatchFn.apply(self, m, S)
         hd, tm, tS, T = self._mm_inputs(m, S)
         kinv = self.inv_K_device()
@@ -946,7 +953,7 @@ class SimpleGPModel(StateSpaceModel):
         V_bar (T, n, D) (None = zero) the derivatives m_bar (T, D) and S_bar (T, D, D) of
         sum(mu_bar * mu) + sum(cov_bar * cov) + sum(V_bar * V) in m and S (S None = zero; S_bar is returned all the same: it is
         not zero there).  S_bar is exactly symmetric; the clip of the covariance diagonal is ignored.  Asynchronous."""
-        hd, tm, tS, T = self._mm_inputs(m, S)
+        hd, tm, tS, T = self._mm_inputs(m, S, reverse=True)
         n, D = hd.n_out, hd.D
         seeds = [None if x is None else B.as_dev(x, hd.device, shp)
                  for x, shp in ((mu_bar, (T, n)), (cov_bar, (T, n, n)), (V_bar, (T, n, D)))]

@@ -14,7 +14,8 @@ Beyond the reference: EXACT moment matching (``MOMENT_MATCHING``; ``one_step_mom
 the Gaussian input z = G x + g0, G = [a_gp_inp_x; K], g0 = [0; k_ff] (``SimpleGPModel.moment_match_device``: mean, full
 covariance across outputs and expected Jacobian V in closed form), and with A = a + b K
 ``mu_new = A mu + b k_ff + mu_g``, ``Sigma_new = (A + V G) Sigma (A + V G)^T + Cov - (V G) Sigma (V G)^T``.
-An initial covariance ``sigma_0`` is supported there.
+An initial covariance ``sigma_0`` is supported there.  Models whose kernels are all "rbf" or "lin_rbf" (a Matern kernel has no
+closed form: NotImplementedError); ``differentiable=True`` needs an ARD-RBF model.
 
 Beyond the reference as well: the reverse pass of ONE Taylor / mean-equivalent step on the device (``moment_step_vjp_batch`` /
 ``sr_moment_step_vjp``, ``onestep_moments_vjp_batch`` / ``sr_onestep_moments_vjp``), the one-step call from a Gaussian state with
