@@ -42,6 +42,8 @@ def main():
     mc = MonteCarloSafetyVerification(gp)
     _, consistent = mc.sample_n_step(x0, K, k, n=n, n_samples=S, consistent=True)     # uses the S paths drawn above
     _, marginal = mc.sample_n_step(x0, K, k, n=n, n_samples=S)
+    _, fused = mc.rollout_paths(x0, K, k, n=n, n_samples=S)                           # the same roll-out in one launch
+    print("one launch against the chained steps: max difference %.2e" % np.abs(fused - consistent).max())
     print("\nstep  spread of the particles (trace of their covariance): consistent | marginal")
     for i in range(n):
         print("%4d  %.5f | %.5f" % (i, np.trace(np.cov(consistent[i].T)), np.trace(np.cov(marginal[i].T))))

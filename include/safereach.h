@@ -51,7 +51,7 @@ typedef struct sr_gp* sr_gp_t;
 #define SR_K_SPARSE_GEMM  10 /* sr_gp_fit_sparse: streamed G += K_fu^T K_fu on the fp64 MFMA tile                 */
 #define SR_K_PATHS_DRAW   11 /* sr_gp_paths_draw: feature slab, residual, the two triangular products              */
 #define SR_K_PATHS_EVAL   12 /* sr_gp_paths_eval[_grad]: feature (and derivative) slabs of the chunk + the two-range MFMA tile (K* pass: SR_K_KSTAR) */
-#define SR_K_PATHS_STEP   13 /* sr_gp_paths_step[_grad]: split pass + ordered sum                                  */
+#define SR_K_PATHS_STEP   13 /* sr_gp_paths_step[_grad]: split pass + ordered sum; sr_gp_paths_rollout: its one launch */
 #define SR_K_REACH_VJP    14 /* sr_ellipsoid_step_vjp / sr_onestep_reach_vjp, sr_onestep_moments_vjp: the reverse of the step's algebra + the GP link (its linearisation: SR_K_KSTAR, SR_K_VAR, SR_K_FINAL) */
 #define SR_K_COUNT     15
 
@@ -510,6 +510,16 @@ int sr_gp_paths_step(sr_gp_t h, const double* Xs, double* F, const double* k_fb,
 int sr_gp_paths_eval_grad(sr_gp_t h, const double* Xq, long T, double* F, double* J, void* stream);
 int sr_gp_paths_step_grad(sr_gp_t h, const double* Xs, double* F, double* J, const double* k_fb, const double* k_ff,
                           double* z_next, void* stream);
+/* sr_gp_paths_rollout: every valid path through H closed-loop steps in ONE launch (what H chained _step / _step_grad calls
+ * compute, not bit for bit: the terms are summed in another order).  n_s = n_out, n_u = D - n_out >= 1.  x0: n_s doubles
+ * (x0_per_path == 0: one start for all paths) or S x n_s (x0_per_path == 1); k_fb H x n_u x n_s, k_ff H x n_u.  Step i
+ * evaluates path s at [x_i[s], k_fb[i] x_i[s] + k_ff[i]] and x_{i+1}[s] is the result: X_all H x S x n_s holds x_1 .. x_H;
+ * A_all, NULL or H x S x n_s x n_s, A_all[i][s] = J_x + J_u k_fb[i] with J = d f_s / d(input) at step i's input.  X_all is
+ * the same bits with and without A_all, on every call, and its first h steps are the h-step call.  Device pointers, no
+ * workspace, asynchronous on `stream`.  Errors in the order of _step, before any launch: SR_EINVAL NULL h, x0, k_fb, k_ff or
+ * X_all, H < 1, x0_per_path not 0 / 1, D == n_out; then the model's SR_ESTATE / SR_EUNSUPPORTED; SR_ESTATE no valid paths. */
+int sr_gp_paths_rollout(sr_gp_t h, const double* x0, int x0_per_path, int H, const double* k_fb, const double* k_ff,
+                        double* X_all, double* A_all, void* stream);
 
 /* ---- tuning / measurement -------------------------------------------------------------------- */
 /* max queries processed per internal pass (workspace = n_out * Np * chunk * 8 B); default 65536. */

@@ -1,6 +1,7 @@
 // sr_capi_paths.hip -- posterior function samples by pathwise conditioning: sr_gp_paths_draw / _count / _eval / _step and
-// their Jacobians sr_gp_paths_eval_grad / _step_grad (the same plans with J: one body each).
-// The algebra: include/safereach.h; the kernels: sr_paths.hip.  Host-side orchestration only.
+// their Jacobians sr_gp_paths_eval_grad / _step_grad (the same plans with J: one body each), and the closed-loop roll-out in one
+// launch, sr_gp_paths_rollout.  The algebra: include/safereach.h; the kernels: sr_paths.hip, sr_paths_rollout.hip.
+// Host-side orchestration only.
 #include "sr_handle.h"
 using namespace srh;
 
@@ -191,4 +192,26 @@ extern "C" int sr_gp_paths_step(sr_gp_t h, const double* Xs, double* F, const do
 extern "C" int sr_gp_paths_step_grad(sr_gp_t h, const double* Xs, double* F, double* J, const double* k_fb, const double* k_ff,
                                      double* z_next, void* stream) {
     return paths_step(h, Xs, F, J, true, k_fb, k_ff, z_next, stream, "sr_gp_paths_step_grad");
+}
+
+// the checks in the order of paths_step; no workspace: the launch reads the handle's paths and writes the caller's buffers
+extern "C" int sr_gp_paths_rollout(sr_gp_t h, const double* x0, int x0_per_path, int H, const double* k_fb, const double* k_ff,
+                                   double* X_all, double* A_all, void* stream) {
+    const char* who = "sr_gp_paths_rollout";
+    SR_CHECK(h != nullptr, SR_EINVAL, "%s: NULL handle", who);
+    SR_CHECK(x0 && k_fb && k_ff && X_all, SR_EINVAL, "%s: NULL argument", who);
+    SR_CHECK(H >= 1 && (x0_per_path == 0 || x0_per_path == 1), SR_EINVAL, "%s: H=%d x0_per_path=%d", who, H, x0_per_path);
+    SR_CHECK(h->D > h->n_out, SR_EINVAL, "%s: the closed loop needs D = n_out + n_u (D=%d, n_out=%d)", who, h->D, h->n_out);
+    SR_TRY(model_checks(h, who));
+    SR_CHECK(paths_valid(h), SR_ESTATE, "%s: no valid paths (sr_gp_paths_draw after the last model update)", who);
+    hipStream_t s = (hipStream_t)stream;
+    SR_DEVICE(h->device);
+    const paths_layout L(h, h->paths_S, h->paths_M);
+    sr_paths_rollout_args a;
+    a.m = feat_args(h, L);
+    a.Z = h->Z; a.Wk = h->paths.get() + L.o_w; a.C = h->paths.get() + L.o_c;
+    a.x0 = x0; a.x0_per_path = x0_per_path; a.H = H; a.k_fb = k_fb; a.k_ff = k_ff; a.X_all = X_all; a.A_all = A_all;
+    a.N = h->N; a.Np = h->Np; a.S = L.S; a.Sp = L.Sp;
+    sr_prof_scope ps(&h->prof, SR_K_PATHS_STEP, s);
+    return sr_launch_paths_rollout(a, s);
 }

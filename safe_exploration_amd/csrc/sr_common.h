@@ -595,6 +595,16 @@ struct sr_paths_step_args {
     int N, Np, S, Sp, nsplit;
 };
 int sr_launch_paths_step(const sr_paths_step_args& a, hipStream_t s);
+// the closed-loop roll-out of every path in one launch (sr_paths_rollout.hip): H steps from x0 (n_out, or S x n_out with
+// x0_per_path) under the gains k_fb (H x n_u x n_out), k_ff (H x n_u)
+struct sr_paths_rollout_args {
+    sr_paths_feat m; const double* Z; const double* Wk; const double* C;
+    const double* x0; int x0_per_path, H; const double* k_fb; const double* k_ff;
+    double* X_all;                    // H x S x n_out
+    double* A_all;                    // H x S x n_out x n_out, or NULL: the states alone
+    int N, Np, S, Sp;
+};
+int sr_launch_paths_rollout(const sr_paths_rollout_args& a, hipStream_t s);
 
 struct sr_final_args {
     const double* mu_part; const double* jac_part; const double* var_part; const double* sf2;

@@ -104,6 +104,26 @@ class MonteCarloSafetyVerification(object):
         out = tuple(B.to_numpy(t) for t in res[1:])
         return (out[0][n - 1].squeeze(),) + out
 
+    def rollout_paths(self, x0, K, k, n=1, n_samples=1000, generator=None, as_tensor=False, n_features=1024, jacobians=False):
+        """The consistent roll-out in ONE launch (SimpleGPModel.paths_rollout_device): what sample_n_step(consistent=True)
+        computes step by step -- to rounding, not bit for bit -- and returns as it does, S (n_samples, n_s) and S_all
+        (n, n_samples, n_s); with jacobians=True what sample_n_step_jacobians returns, (S, S_all, A_all).  x0 may also be
+        (n_samples, n_s): one start per particle.  The model's valid paths are used if there are n_samples of them,
+        otherwise they are drawn here."""
+        n_s, n_u = self.n_s, self.n_u
+        assert n > 0, "The time horizon n for the multi-step sampling must be positive!"
+        assert np.shape(K) == (n, n_u, n_s), "Required shape of K is ({},{},{})".format(n, n_u, n_s)
+        assert np.shape(k) == (n, n_u), "Required shape of k is ({},{})".format(n, n_u)
+        if self.GP.paths_count()[0] != n_samples:
+            self.GP.draw_paths(n_samples, n_features, generator)
+        out = self.GP.paths_rollout_device(x0, K, k, jacobians=jacobians)
+        S_all = out[0] if jacobians else out
+        res = (S_all[n - 1], S_all) + ((out[1],) if jacobians else ())
+        if as_tensor:
+            return res
+        out = tuple(B.to_numpy(t) for t in res[1:])
+        return (out[0][n - 1].squeeze(),) + out
+
     def inside_ellipsoid_ratio(self, S, Q, p):
         """Ratio of samples inside the ellipsoid of each time step  (sampling_models.py:82-107).
 

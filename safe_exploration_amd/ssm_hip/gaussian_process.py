@@ -1564,6 +1564,34 @@ class SimpleGPModel(StateSpaceModel):
         check(lib.sr_gp_paths_step(hd.h, B.ptr(x), B.ptr(F), B.ptr(tk), B.ptr(tf), B.ptr(z), B.stream_ptr(hd.device)))
         return F if z is None else (F, z)
 
+    def paths_rollout_device(self, x0, K, k, jacobians=False):
+        """Every drawn path through the closed loop u_i = K[i] x_i + k[i] in ONE launch (sr_gp_paths_rollout): x0 (n_s,) or
+        (n_s, 1) is the start of every path, (size, n_s) one start per path; K (H, n_u, n_s), k (H, n_u).  Returns the tensor
+        X_all (H, size, n_s) of the states after steps 1 .. H -- what H chained paths_step_device calls give, to rounding --
+        and with jacobians=True (X_all, A_all), A_all (H, size, n_s, n_s) = J_x + J_u K[i] per step and path."""
+        self._need_trained()
+        hd = self._handle
+        n_s, n_u = hd.n_out, hd.D - hd.n_out
+        if n_u < 1:
+            raise ValueError("the closed loop needs D = n_s_out + n_u")
+        K, k = B.as_dev(K, hd.device), B.as_dev(k, hd.device)
+        H = K.shape[0] if K.dim() == 3 else 0
+        if H < 1 or tuple(K.shape) != (H, n_u, n_s) or tuple(k.shape) != (H, n_u):
+            raise ValueError("K must be (H, {}, {}) and k (H, {}) with H >= 1".format(n_u, n_s, n_u))
+        S = self._need_paths()
+        x = B.as_dev(x0, hd.device)
+        if tuple(x.shape) in ((n_s,), (n_s, 1)):
+            x, per_path = x.reshape(n_s), 0
+        elif tuple(x.shape) == (S, n_s):
+            per_path = 1
+        else:
+            raise ValueError("x0 must be ({0},), ({0}, 1) or ({1}, {0})".format(n_s, S))
+        X_all = B.empty((H, S, n_s), hd.device)
+        A_all = B.empty((H, S, n_s, n_s), hd.device) if jacobians else None
+        check(lib.sr_gp_paths_rollout(hd.h, B.ptr(x), per_path, H, B.ptr(K), B.ptr(k), B.ptr(X_all), B.ptr(A_all),
+                                      B.stream_ptr(hd.device)))
+        return (X_all, A_all) if jacobians else X_all
+
     def information_gain(self, x=None):
         """Mutual information between the training samples and the system  gaussian_process.py:621-634:
         per output log det(I + K/sigma_n^2) = log det(K + sigma_n^2 I) - N log sigma_n^2, sigma_n^2 being the
