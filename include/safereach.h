@@ -520,6 +520,26 @@ int sr_gp_paths_step_grad(sr_gp_t h, const double* Xs, double* F, double* J, con
  * X_all, H < 1, x0_per_path not 0 / 1, D == n_out; then the model's SR_ESTATE / SR_EUNSUPPORTED; SR_ESTATE no valid paths. */
 int sr_gp_paths_rollout(sr_gp_t h, const double* x0, int x0_per_path, int H, const double* k_fb, const double* k_ff,
                         double* X_all, double* A_all, void* stream);
+/* sr_gp_paths_rollout_vjp: the reverse pass of sr_gp_paths_rollout in the gains and the start.  x0, x0_per_path, H, k_fb, k_ff
+ * as the forward took them, X_all (H x S x n_s) the states it returned (X_all[H-1] is not read), X_bar (H x S x n_s) the seeds:
+ * with L = sum_{i,s} X_bar[i][s] . x_{i+1}[s], z_i[s] = [x_i[s], k_fb[i] x_i[s] + k_ff[i]] and J_i[s] = d f_s / d z at z_i[s]
+ * (n_s x D = [J_x | J_u], the closed form of sr_gp_paths_step_grad over the w and c the draw keeps: nothing is drawn or solved),
+ * per path, lambda = X_bar[H-1][s], for i = H-1 .. 0:
+ *   g = J_i[s]^T lambda = [g_x, g_u];  k_ff_bar[i] += g_u;  k_fb_bar[i] += g_u x_i[s]^T;
+ *   lambda = (i >= 1 ? X_bar[i-1][s] : 0) + g_x + k_fb[i]^T g_u;                      x0_bar[s] = lambda at the end.
+ * k_fb_bar H x n_u x n_s and k_ff_bar H x n_u are summed over the paths; x0_bar is S x n_s with x0_per_path == 1 and n_s doubles,
+ * the sum over the paths, with x0_per_path == 0.  J_all, NULL or H x S x n_s x D, receives every J_i[s] (the J_u that A_all
+ * folds away); the three gradients are the same bits with and without it.  Gradients in the model or the draws: out of scope.
+ * Device pointers, asynchronous on `stream`, deterministic: no floating-point atomics, every sum in a fixed order (the splits
+ * of the N + M terms ascending, the paths in a fixed tree per block of 256 and the blocks ascending), the same bits on every
+ * call.  Workspace: the handle's grow-only block of the path calls (freed by sr_gp_release_scratch) -- J when J_all is NULL,
+ * the splits' partial sums (the split rule of _step for H S evaluations; n_s D H Sp doubles each), one record per block; SR_EHIP
+ * if it cannot be had.  Errors in the forward's order, before any launch, the paths and the other calls' results untouched:
+ * SR_EINVAL NULL h, x0, k_fb, k_ff, X_all, X_bar, x0_bar, k_fb_bar or k_ff_bar, H < 1, x0_per_path not 0 / 1, D == n_out; then
+ * the model's SR_ESTATE / SR_EUNSUPPORTED; SR_ESTATE no valid paths. */
+int sr_gp_paths_rollout_vjp(sr_gp_t h, const double* x0, int x0_per_path, int H, const double* k_fb, const double* k_ff,
+                            const double* X_all, const double* X_bar, double* x0_bar, double* k_fb_bar, double* k_ff_bar,
+                            double* J_all, void* stream);
 
 /* ---- tuning / measurement -------------------------------------------------------------------- */
 /* max queries processed per internal pass (workspace = n_out * Np * chunk * 8 B); default 65536. */

@@ -95,6 +95,7 @@ SIGNATURES = {
     "sr_gp_paths_eval_grad": (_I, [_H, _P, _L, _P, _P, _P]),
     "sr_gp_paths_step_grad": (_I, [_H, _P, _P, _P, _P, _P, _P, _P]),
     "sr_gp_paths_rollout": (_I, [_H, _P, _I, _I, _P, _P, _P, _P, _P]),
+    "sr_gp_paths_rollout_vjp": (_I, [_H, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "sr_gp_set_chunk": (_I, [_H, _L]),
     "sr_gp_set_var_group": (_I, [_H, _I]),
     "sr_gp_set_var_variant": (_I, [_H, _I]),

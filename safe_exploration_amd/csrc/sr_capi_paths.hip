@@ -1,6 +1,7 @@
 // sr_capi_paths.hip -- posterior function samples by pathwise conditioning: sr_gp_paths_draw / _count / _eval / _step and
 // their Jacobians sr_gp_paths_eval_grad / _step_grad (the same plans with J: one body each), and the closed-loop roll-out in one
-// launch, sr_gp_paths_rollout.  The algebra: include/safereach.h; the kernels: sr_paths.hip, sr_paths_rollout.hip.
+// launch, sr_gp_paths_rollout, with its reverse pass sr_gp_paths_rollout_vjp.  The algebra: include/safereach.h; the kernels:
+// sr_paths.hip, sr_paths_rollout.hip, sr_paths_rollout_vjp.hip.
 // Host-side orchestration only.
 #include "sr_handle.h"
 using namespace srh;
@@ -214,4 +215,37 @@ extern "C" int sr_gp_paths_rollout(sr_gp_t h, const double* x0, int x0_per_path,
     a.N = h->N; a.Np = h->Np; a.S = L.S; a.Sp = L.Sp;
     sr_prof_scope ps(&h->prof, SR_K_PATHS_STEP, s);
     return sr_launch_paths_rollout(a, s);
+}
+
+// the forward's checks in the forward's order; then the workspace (before it is there nothing of the handle has changed)
+extern "C" int sr_gp_paths_rollout_vjp(sr_gp_t h, const double* x0, int x0_per_path, int H, const double* k_fb, const double* k_ff,
+                                       const double* X_all, const double* X_bar, double* x0_bar, double* k_fb_bar, double* k_ff_bar,
+                                       double* J_all, void* stream) {
+    const char* who = "sr_gp_paths_rollout_vjp";
+    SR_CHECK(h != nullptr, SR_EINVAL, "%s: NULL handle", who);
+    SR_CHECK(x0 && k_fb && k_ff && X_all && X_bar && x0_bar && k_fb_bar && k_ff_bar, SR_EINVAL, "%s: NULL argument", who);
+    SR_CHECK(H >= 1 && (x0_per_path == 0 || x0_per_path == 1), SR_EINVAL, "%s: H=%d x0_per_path=%d", who, H, x0_per_path);
+    SR_CHECK(h->D > h->n_out, SR_EINVAL, "%s: the closed loop needs D = n_out + n_u (D=%d, n_out=%d)", who, h->D, h->n_out);
+    SR_TRY(model_checks(h, who));
+    SR_CHECK(paths_valid(h), SR_ESTATE, "%s: no valid paths (sr_gp_paths_draw after the last model update)", who);
+    hipStream_t s = (hipStream_t)stream;
+    SR_DEVICE(h->device);
+    const paths_layout L(h, h->paths_S, h->paths_M);
+    const int n_s = h->n_out, D = h->D, n_u = D - n_s;
+    sr_paths_rollout_vjp_args a;
+    a.m = feat_args(h, L);
+    a.Z = h->Z; a.Wk = h->paths.get() + L.o_w; a.C = h->paths.get() + L.o_c;
+    a.x0 = x0; a.x0_per_path = x0_per_path; a.H = H; a.k_fb = k_fb; a.k_ff = k_ff; a.X_all = X_all; a.X_bar = X_bar;
+    a.x0_bar = x0_bar; a.k_fb_bar = k_fb_bar; a.k_ff_bar = k_ff_bar;
+    a.N = h->N; a.Np = h->Np; a.S = L.S; a.Sp = L.Sp;
+    a.nsplit = sr_hess_nsplit(h->N + L.M, n_s, (long)H * L.S);     // (the rule of _step, for all H S evaluations at once)
+    // [J, path index fastest, unless the caller takes it | the splits' partial sums | the sweep's records]
+    const size_t n_j = J_all ? 0 : (size_t)H * n_s * D * L.Sp, n_part = (size_t)a.nsplit * n_s * D * H * L.Sp;
+    const size_t n_rec = (size_t)sr_paths_rollout_vjp_blocks(L.S) * ((size_t)H * n_u * (1 + n_s) + n_s);
+    SR_TRY(h->paths_ws.grow(n_j + n_part + n_rec, wait::device()));
+    if (J_all) { a.J = J_all; a.j_si = (long)L.S * n_s * D; a.j_ss = (long)n_s * D; a.j_se = 1; }
+    else { a.J = h->paths_ws.get(); a.j_si = (long)n_s * D * L.Sp; a.j_ss = 1; a.j_se = L.Sp; }
+    a.part = h->paths_ws.get() + n_j; a.rec = a.part + n_part;
+    sr_prof_scope ps(&h->prof, SR_K_PATHS_STEP, s);
+    return sr_launch_paths_rollout_vjp(a, s);
 }

@@ -390,7 +390,10 @@ int sr_launch_var_bal(const double* Wt, const double* Ks, double* Vt, double* pa
 //                                            the variance tile, not swept (profiles/r12_paths.txt holds the times they give);
 //                                            Jacobians: the same tile, strips and split count (F keeps its bits), derivative slabs
 //                                            in strips of 16 rows x 256 columns, the ordered sum one thread per (path, element of
-//                                            J) (profiles/r13_paths_grad.txt)
+//                                            J) (profiles/r13_paths_grad.txt); reverse pass of the roll-out: the Jacobians of all
+//                                            H S (step, path) pairs in one launch split by sr_hess_nsplit(N + M, n_out, H S), the
+//                                            adjoint sweep one lane per path in blocks of SR_RVJP_BLOCK (256) paths; neither swept
+//                                            (profiles/r19_paths_rollout_vjp.txt)
 //  row append (sr_capi_append.hip)           one launch for +1 point with Np <= 512 (SR_APPEND1_MAX_NP0, r03_exploration_step), <= 16
 //                                            points matrix-vector shaped, 17 .. 128 on the MFMA tile (r03_append_bench); the Python layer
 //                                            appends up to N / 5 points and refactorises beyond (break-even r03_growing_model)
@@ -605,6 +608,21 @@ struct sr_paths_rollout_args {
     int N, Np, S, Sp;
 };
 int sr_launch_paths_rollout(const sr_paths_rollout_args& a, hipStream_t s);
+// its reverse pass (sr_paths_rollout_vjp.hip): the Jacobians of all H S (step, path) pairs at the stored states, the adjoint
+// sweep one lane per path, the sums over the paths in a fixed order
+#define SR_RVJP_BLOCK 256            /* paths per workgroup of the sweep = per partial record; not swept */
+static inline int sr_paths_rollout_vjp_blocks(int S) { return (S + SR_RVJP_BLOCK - 1) / SR_RVJP_BLOCK; }
+struct sr_paths_rollout_vjp_args {
+    sr_paths_feat m; const double* Z; const double* Wk; const double* C;
+    const double* x0; int x0_per_path, H; const double* k_fb; const double* k_ff;
+    const double* X_all; const double* X_bar;            // H x S x n_out each (X_all[H - 1] is not read)
+    double* x0_bar; double* k_fb_bar; double* k_ff_bar;  // n_out (S x n_out with x0_per_path), H x n_u x n_out, H x n_u
+    double* J; long j_si, j_ss, j_se;                    // J_i[s][d][j] at J[i j_si + s j_ss + (d D + j) j_se]
+    double* part;                     // nsplit x n_out x D x H x Sp
+    double* rec;                      // blocks x H x n_u (1 + n_out), then blocks x n_out (shared start), blocks = .._vjp_blocks(S)
+    int N, Np, S, Sp, nsplit;
+};
+int sr_launch_paths_rollout_vjp(const sr_paths_rollout_vjp_args& a, hipStream_t s);
 
 struct sr_final_args {
     const double* mu_part; const double* jac_part; const double* var_part; const double* sf2;

@@ -124,6 +124,21 @@ class MonteCarloSafetyVerification(object):
         out = tuple(B.to_numpy(t) for t in res[1:])
         return (out[0][n - 1].squeeze(),) + out
 
+    def rollout_paths_diff(self, x0, K, k, n=1, n_samples=1000, generator=None, n_features=1024):
+        """rollout_paths as a node of torch's autograd graph (SimpleGPModel.paths_rollout_diff_device): returns the tensors
+        S (n_samples, n_s), a view of S_all[n - 1], and S_all (n, n_samples, n_s) -- the bits of rollout_paths -- and a cost
+        of them can be differentiated once in those of x0, K, k that are tensors requiring a gradient (the reverse pass on
+        the device, sr_gp_paths_rollout_vjp; the model and the draws get none).  The paths are drawn under rollout_paths'
+        rule: the model's valid ones if there are n_samples of them."""
+        n_s, n_u = self.n_s, self.n_u
+        assert n > 0, "The time horizon n for the multi-step sampling must be positive!"
+        assert tuple(np.shape(K)) == (n, n_u, n_s), "Required shape of K is ({},{},{})".format(n, n_u, n_s)
+        assert tuple(np.shape(k)) == (n, n_u), "Required shape of k is ({},{})".format(n, n_u)
+        if self.GP.paths_count()[0] != n_samples:
+            self.GP.draw_paths(n_samples, n_features, generator)
+        S_all = self.GP.paths_rollout_diff_device(x0, K, k)
+        return S_all[n - 1], S_all
+
     def inside_ellipsoid_ratio(self, S, Q, p):
         """Ratio of samples inside the ellipsoid of each time step  (sampling_models.py:82-107).
 

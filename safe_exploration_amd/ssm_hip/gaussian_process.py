@@ -179,6 +179,29 @@ class _MomentMatchFn(torch.autograd.Function):
         return None, m_bar, (None if S is None else S_bar)
 
 
+class _PathsRolloutFn(torch.autograd.Function):
+    """``SimpleGPModel.paths_rollout_diff_device(x0, K, k)``: the forward is ``paths_rollout_device``, the backward
+    ``paths_rollout_vjp_device`` at the saved inputs and states.  An output nobody used has a zero seed: zero gradients."""
+
+    @staticmethod
+    def forward(ctx, model, x0, K, k):
+        X_all = model.paths_rollout_device(x0, K, k)
+        ctx.model = model
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(x0, K, k, X_all)
+        return X_all
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, X_bar):
+        x0, K, k, X_all = ctx.saved_tensors
+        if X_bar is None:
+            X_bar = torch.zeros_like(X_all)
+        x0_bar, K_bar, k_bar = ctx.model.paths_rollout_vjp_device(x0, K, k, X_all, X_bar)
+        need = ctx.needs_input_grad
+        return None, (x0_bar if need[1] else None), (K_bar if need[2] else None), (k_bar if need[3] else None)
+
+
 class SimpleGPModel(StateSpaceModel):
     """GP dynamics model x_{t+1} - prior(x_t,u_t) ~ GP, one output per state dimension.
 
@@ -1591,6 +1614,51 @@ class SimpleGPModel(StateSpaceModel):
         check(lib.sr_gp_paths_rollout(hd.h, B.ptr(x), per_path, H, B.ptr(K), B.ptr(k), B.ptr(X_all), B.ptr(A_all),
                                       B.stream_ptr(hd.device)))
         return (X_all, A_all) if jacobians else X_all
+
+    def paths_rollout_vjp_device(self, x0, K, k, X_all, X_bar, jacobians=False):
+        """The reverse pass of paths_rollout_device (sr_gp_paths_rollout_vjp): x0, K, k as the forward took them, X_all
+        (H, size, n_s) the states it returned, X_bar (H, size, n_s) the seeds of L = sum X_bar * X_all.  Returns the tensors
+        (x0_bar, K_bar, k_bar) -- x0_bar in the shape of x0 (a shared start: the sum over the paths), K_bar (H, n_u, n_s),
+        k_bar (H, n_u), both summed over the paths -- and with jacobians=True J_all (H, size, n_s, D) behind them, the
+        Jacobian of every step and path in its input [x_i, K[i] x_i + k[i]].  Deterministic: the same bits on every call, with
+        and without J_all.  The model and the draws get no gradient."""
+        self._need_trained()
+        hd = self._handle
+        n_s, n_u = hd.n_out, hd.D - hd.n_out
+        if n_u < 1:
+            raise ValueError("the closed loop needs D = n_s_out + n_u")
+        K, k = B.as_dev(K, hd.device), B.as_dev(k, hd.device)
+        H = K.shape[0] if K.dim() == 3 else 0
+        if H < 1 or tuple(K.shape) != (H, n_u, n_s) or tuple(k.shape) != (H, n_u):
+            raise ValueError("K must be (H, {}, {}) and k (H, {}) with H >= 1".format(n_u, n_s, n_u))
+        S = self._need_paths()
+        x = B.as_dev(x0, hd.device)
+        shape0 = tuple(x.shape)
+        if shape0 in ((n_s,), (n_s, 1)):
+            x, per_path = x.reshape(n_s), 0
+        elif shape0 == (S, n_s):
+            per_path = 1
+        else:
+            raise ValueError("x0 must be ({0},), ({0}, 1) or ({1}, {0})".format(n_s, S))
+        X_all, X_bar = B.as_dev(X_all, hd.device), B.as_dev(X_bar, hd.device)
+        if tuple(X_all.shape) != (H, S, n_s) or tuple(X_bar.shape) != (H, S, n_s):
+            raise ValueError("X_all and X_bar must be ({}, {}, {})".format(H, S, n_s))
+        x0_bar = B.empty((S, n_s) if per_path else (n_s,), hd.device)
+        K_bar, k_bar = B.empty((H, n_u, n_s), hd.device), B.empty((H, n_u), hd.device)
+        J_all = B.empty((H, S, n_s, hd.D), hd.device) if jacobians else None
+        check(lib.sr_gp_paths_rollout_vjp(hd.h, B.ptr(x), per_path, H, B.ptr(K), B.ptr(k), B.ptr(X_all), B.ptr(X_bar),
+                                          B.ptr(x0_bar), B.ptr(K_bar), B.ptr(k_bar), B.ptr(J_all), B.stream_ptr(hd.device)))
+        x0_bar = x0_bar.reshape(shape0)
+        return (x0_bar, K_bar, k_bar, J_all) if jacobians else (x0_bar, K_bar, k_bar)
+
+    def paths_rollout_diff_device(self, x0, K, k):
+        """paths_rollout_device(x0, K, k) -- the same bits -- as a node of torch's autograd graph: the backward is
+        paths_rollout_vjp_device at the stored states, once differentiable, with gradients for those of x0, K, k that
+        require them (not for the model or the draws)."""
+        self._need_trained()
+        self._need_paths()
+        dev = self._handle.device
+        return _PathsRolloutFn.apply(self, B.as_dev(x0, dev), B.as_dev(K, dev), B.as_dev(k, dev))
 
     def information_gain(self, x=None):
         """Mutual information between the training samples and the system  gaussian_process.py:621-634:
