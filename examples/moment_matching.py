@@ -49,6 +49,22 @@ def main():
         sigma_0=torch.as_tensor(np.tile(sigma_0, (T, 1, 1)), device=dev))
     print("\nbatch:", tuple(mu_all.shape), tuple(sigma_all.shape), tuple(cov_all.shape))
 
+    # the roll-out in ONE launch (sr_gp_moment_match_rollout): a workgroup owns a trajectory for the whole horizon.  The same
+    # arguments and results as moment_matching_batch, equal to rounding; outside the kernel's domain (a lin_rbf model, N > 1024)
+    # the call goes through moment_matching_batch
+    mu0 = 0.2 * rng.standard_normal((T, n_s))
+    kff_T, kfb_T = 0.1 * rng.standard_normal((T, H, n_u)), -0.3 * np.ones((T, H - 1, n_u, n_s))
+    s0_T = np.tile(sigma_0, (T, 1, 1))
+    fused = up.moment_matching_rollout_batch(mu0, gp, kff_T, kfb_T, a, b, sigma_0=s0_T)
+    chained = up.moment_matching_batch(mu0, gp, kff_T, kfb_T, a, b, sigma_0=s0_T)
+    print("roll-out in one launch against the per-step route: max |difference| of (mu_all, sigma_all, gp_cov_all) =",
+          ["%.1e" % np.abs(x - y).max() for x, y in zip(fused, chained)])
+    # on device tensors, one policy for all trajectories, without the GP's output covariances
+    mu_d, sigma_d, _ = gp.moment_match_rollout_device(torch.as_tensor(mu0, device=dev), k_ff, np.stack(k_fb), a, b,
+                                                      sigma0=s0_T, with_cov=False)
+    print("shared policy:", tuple(mu_d.shape), tuple(sigma_d.shape), " trace Sigma_H of trajectory 0 = %.6f"
+          % float(torch.trace(sigma_d[0, -1])))
+
     # the same roll-out with the reference's "lin_rbf" kernel (linear x RBF on input dimension 1 + ARD linear): a near-linear
     # plant, whose linear part the kernel carries; the closed form exists for it too (a Matern kernel has none)
     Yl = Y + Z.dot(np.array([[0.1, 0.0], [0.0, 0.1], [0.05, -0.05]]))

@@ -414,6 +414,26 @@ int sr_gp_moment_match(sr_gp_t h, const double* m, const double* S, long T, cons
 int sr_gp_moment_match_vjp(sr_gp_t h, const double* m, const double* S, long T, const double* inv_k,
                            const double* mu_bar, const double* cov_bar, const double* V_bar,
                            double* m_bar, double* S_bar, void* stream);
+/* sr_gp_moment_match_rollout: T trajectories through H closed-loop steps of exact moment matching in ONE launch (a workgroup
+ * owns a trajectory for the whole horizon; what H rounds of sr_gp_moment_match with the algebra between them compute, to
+ * rounding, not bit for bit).  n_s = n_out, n_u = D - n_x_in >= 1.  State N(mu, Sigma), control u = K x + k_ff, G = [tz; K]:
+ *   GP input m_z = [tz mu; K mu + k_ff], S_z = G Sigma G^T (step 0: K = 0; a point start: no S_z); mu_g, Cov, V as above;
+ *   mu+ = (a + b K) mu + b k_ff + mu_g ; Sigma+ = Hm Sigma Hm^T + Cov - (V G) Sigma (V G)^T, Hm = a + b K + V G (Cov from a point).
+ * mu0 T x n_s; sigma0 NULL (points) or T x n_s x n_s; k_ff [T x] H x n_u; k_fb [T x] (H - 1) x n_u x n_s (may be NULL when H == 1;
+ * step i >= 1 uses k_fb[i - 1]); gains_per_traj 0: one policy for all trajectories, 1: one per trajectory; a n_s x n_s; b n_s x n_u;
+ * tz NULL (identity: n_x_in == n_s) or n_x_in x n_s; inv_k as above.  Outputs: mu_all T x H x n_s; sigma_all T x H x n_s x n_s
+ * (exactly symmetric); cov_all NULL or T x H x n_s x n_s, the GP's output covariance per step (diagonal clipped at 1e-15, exact
+ * zeros off it at step 0 from a point).  The same bits on every call, with and without cov_all; the first h steps equal the
+ * h-step call; a trajectory's result does not depend on the other trajectories of the batch nor on sr_gp_set_chunk (which only
+ * sizes the scratch: one step's records per trajectory, freed by sr_gp_release_scratch).  Asynchronous on `stream`.
+ * Errors, before any launch: SR_EINVAL NULL where required, T < 0, H < 1, gains_per_traj outside {0, 1}, n_x_in outside
+ * 1 .. D - 1, tz NULL with n_x_in != n_s; SR_ESTATE not factorized; SR_EUNSUPPORTED any general-family handle, N > 1024 (a
+ * step is milliseconds of double sum there), D > 12, a state block beyond the workgroup's LDS (n_s of about 20): the error text
+ * names the per-step route.  T == 0 is a no-op. */
+int sr_gp_moment_match_rollout(sr_gp_t h, long T, int H, int n_x_in, int gains_per_traj,
+        const double* mu0, const double* sigma0, const double* k_ff, const double* k_fb,
+        const double* a, const double* b, const double* tz, const double* inv_k,
+        double* mu_all, double* sigma_all, double* cov_all, void* stream);
 
 /* replaces: utils.compute_remainder_overapproximations  utils.py:108-144 (batched)
  * q T x n_s x n_s, k_fb T x n_u x n_s -> u_mu T x n_s, u_sigma T x n_s */

@@ -1,7 +1,7 @@
 // sr_capi_reach.hip -- reachability entry points: one-step and multi-step ellipsoid propagation (mode 0) and Gaussian moment
 // propagation (modes 1 / 2) through one forward step (ell_args, reach_step) and one driver each (onestep_impl, multistep_impl);
-// the reverse pass of one step of either through one driver (onestep_vjp_impl); exact moment matching and its reverse pass; the
-// stateless per-query steps (ellipsoid, moments, their reverse passes, remainder, safety distance, distance to centre, sampling);
+// the reverse pass of one step of either through one driver (onestep_vjp_impl); exact moment matching, its reverse pass and
+// its roll-out in one launch; the stateless per-query steps (ellipsoid, moments, their reverse passes, remainder, safety distance, distance to centre, sampling);
 // and the dispatch of the persistent chain kernel (sr_chain.hip K0c) with its process-wide launch gate.
 #include "sr_handle.h"
 using namespace srh;
@@ -438,6 +438,50 @@ extern "C" int sr_gp_moment_match_vjp(sr_gp_t h, const double* m, const double* 
                                           cov_bar ? cov_bar + t0 * n * n : nullptr, V_bar ? V_bar + t0 * n * Dl : nullptr,
                                           m_bar ? m_bar + t0 * Dl : nullptr, S_bar ? S_bar + t0 * DD : nullptr,
                                           h->mm_ws.get(), s));
+    }
+    return SR_OK;
+}
+
+// T trajectories through H closed-loop steps of exact moment matching in one launch per chunk (sr_moment_match_rollout.hip).
+// Every refusal comes before the first launch; the scratch holds one step's records per trajectory of a chunk.  A workgroup
+// owns a trajectory, so the chunk decides nothing but the size of the scratch.
+extern "C" int sr_gp_moment_match_rollout(sr_gp_t h, long T, int H, int n_x_in, int gains_per_traj, const double* mu0,
+                                          const double* sigma0, const double* k_ff, const double* k_fb, const double* a,
+                                          const double* b, const double* tz, const double* inv_k, double* mu_all,
+                                          double* sigma_all, double* cov_all, void* stream) {
+    const char* who = "sr_gp_moment_match_rollout";
+    SR_CHECK(h != nullptr, SR_EINVAL, "%s: NULL handle", who);
+    SR_CHECK(h->factorized, SR_ESTATE, "%s: model not factorized", who);
+    SR_CHECK(!h->general, SR_EUNSUPPORTED, "%s: ARD-RBF models only (data set with sr_gp_set_data): use the per-step route", who);
+    SR_CHECK(h->N <= 1024, SR_EUNSUPPORTED, "%s: N=%d > 1024: use the per-step route", who, h->N);
+    SR_CHECK(h->D <= 12, SR_EUNSUPPORTED, "%s: D=%d > 12: use the per-step route", who, h->D);
+    SR_CHECK(T >= 0 && H >= 1 && (gains_per_traj == 0 || gains_per_traj == 1), SR_EINVAL, "%s: T=%ld H=%d gains_per_traj=%d",
+             who, T, H, gains_per_traj);
+    SR_CHECK(n_x_in >= 1 && n_x_in <= h->D - 1, SR_EINVAL, "%s: n_x_in=%d outside 1 .. D - 1 (D=%d)", who, n_x_in, h->D);
+    SR_CHECK(tz != nullptr || n_x_in == h->n_out, SR_EINVAL, "%s: tz NULL needs n_x_in == n_out (%d, %d)", who, n_x_in,
+             h->n_out);
+    if (T == 0) return SR_OK;
+    SR_CHECK(mu0 && k_ff && a && b && inv_k && mu_all && sigma_all && (k_fb || H == 1), SR_EINVAL, "%s: NULL argument", who);
+    hipStream_t s = (hipStream_t)stream;
+    SR_DEVICE(h->device);
+    const long per = sr_mmr_ws_per_traj(h->D, h->n_out);
+    const long chunk = std::max(1L, std::min({h->chunk, 0x7fffffffL, ((long)1 << 28) / per}));
+    SR_TRY(h->mm_ws.grow((size_t)(std::min(chunk, T) * per), wait::stream(s)));
+    const long n = h->n_out, n_u = h->D - n_x_in;
+    sr_mmr_args r;
+    r.Z = h->Z; r.alpha = h->alpha; r.ls = h->ls; r.sf2 = h->sf2; r.inv_k = inv_k; r.a = a; r.b = b; r.tz = tz;
+    r.ws = h->mm_ws.get();
+    r.N = h->N; r.Np = h->Np; r.D = h->D; r.n_out = h->n_out; r.n_x_in = n_x_in; r.H = H; r.gains_per_traj = gains_per_traj;
+    for (long t0 = 0; t0 < T; t0 += chunk) {
+        r.T = std::min(chunk, T - t0);
+        r.mu0 = mu0 + t0 * n;
+        r.sigma0 = sigma0 ? sigma0 + t0 * n * n : nullptr;
+        r.k_ff = k_ff + (gains_per_traj ? t0 * H * n_u : 0);
+        r.k_fb = k_fb ? k_fb + (gains_per_traj ? t0 * (H - 1) * n_u * n : 0) : nullptr;
+        r.mu_all = mu_all + t0 * H * n;
+        r.sigma_all = sigma_all + t0 * H * n * n;
+        r.cov_all = cov_all ? cov_all + t0 * H * n * n : nullptr;
+        SR_TRY(sr_launch_moment_match_rollout(r, s));
     }
     return SR_OK;
 }

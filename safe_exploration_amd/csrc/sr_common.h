@@ -203,6 +203,21 @@ int sr_launch_moment_match_gen_call(const double* Z, const double* alpha, const 
 int sr_launch_moment_match_gen(const double* Z, const double* alpha, const double* kp, int N, int Np, int D, int n_out,
                                const double* m, const double* S, long T, const double* inv_k, double* mu, double* cov,
                                double* V, const double* call, double* ws, hipStream_t s);
+// the closed-loop roll-out of T trajectories through H steps of exact moment matching in one launch
+// (sr_moment_match_rollout.hip): one workgroup per trajectory; ws: T x sr_mmr_ws_per_traj doubles (the records of one step)
+struct sr_mmr_args {
+    const double *Z, *alpha, *ls, *sf2, *inv_k;      // the model as the handle holds it; n_out x N x N
+    const double *mu0, *sigma0;                      // T x n_out; T x n_out x n_out | NULL (points)
+    const double *k_ff, *k_fb;                       // [T x] H x n_u; [T x] (H - 1) x n_u x n_out | NULL (H == 1)
+    const double *a, *b, *tz;                        // n_out x n_out, n_out x n_u, n_x_in x n_out | NULL (identity)
+    double *mu_all, *sigma_all, *cov_all;            // T x H x n_out, T x H x n_out x n_out, the same | NULL
+    double* ws;
+    int N, Np, D, n_out, n_x_in, H, gains_per_traj;
+    int stage_rec, stage_model;                      // set by the launch: the records resp. Z and alpha live in LDS
+    long T;
+};
+long sr_mmr_ws_per_traj(int D, int n_out);
+int sr_launch_moment_match_rollout(const sr_mmr_args& a, hipStream_t s);
 int sr_launch_fill(double* p, size_t n, double v, hipStream_t s);
 // Wt = J U^T J from the factor as the model update leaves it (diagonal 128-blocks in U, block rows in W; sr_sparse.hip);
 // nbatch members, U / W sS and Wt sD doubles apart

@@ -971,6 +971,61 @@ class SimpleGPModel(StateSpaceModel):
                                      B.stream_ptr(hd.device)))
         return mu, cov, V
 
+    MM_ROLLOUT_MAX_N = 1024          # sr_gp_moment_match_rollout refuses larger models (and D > 12)
+
+    def moment_match_rollout_supported(self):
+        """Whether ``moment_match_rollout_device`` takes this (trained) model: ARD-RBF kernels on every output, exact or
+        sparse, N <= 1024 rows (inducing rows of a sparse model), D <= 12."""
+        self._need_trained()
+        hd = self._handle
+        return all(kt == "rbf" for kt in self.kern_types) and hd.N <= self.MM_ROLLOUT_MAX_N and hd.D <= 12
+
+    def moment_match_rollout_device(self, mu0, k_ff, k_fb, a, b, sigma0=None, a_gp_inp_x=None, with_cov=True):
+        """T trajectories through H closed-loop steps of exact moment matching in ONE launch (``sr_gp_moment_match_rollout``):
+        what ``uncertainty_propagation_casadi.moment_matching_batch`` computes in H rounds, to rounding.  Device tensors in and
+        out.  mu0 (T, n_s); sigma0 (T, n_s, n_s) or None (points); k_ff (H, n_u) and k_fb (H-1, n_u, n_s) -- one policy for all
+        trajectories -- or (T, H, n_u) and (T, H-1, n_u, n_s), one per trajectory (k_fb may be None when H == 1; step 0 has no
+        feedback, step i >= 1 uses k_fb[i-1]); a (n_s, n_s), b (n_s, n_u); a_gp_inp_x (n_x_in, n_s) or None (the GP sees the
+        whole state).  Returns mu_all (T, H, n_s), sigma_all (T, H, n_s, n_s) and, with_cov, the GP's output covariance per
+        step (T, H, n_s, n_s), else None.  The same bits on every call, with and without with_cov.  ARD-RBF models with
+        N <= 1024 and D <= 12 only: NotImplementedError otherwise, before anything is prepared on the device (the per-step
+        route, ``moment_matching_batch``, takes those).  Asynchronous."""
+        if not self.moment_match_rollout_supported():
+            raise NotImplementedError("moment_match_rollout_device: ARD-RBF models with N <= {} and D <= 12 only; "
+                                      "use the per-step route (moment_matching_batch)".format(self.MM_ROLLOUT_MAX_N))
+        hd = self._handle
+        n_s, dev = hd.n_out, hd.device
+        tz = None if a_gp_inp_x is None else B.as_dev(a_gp_inp_x, dev)
+        if tz is not None and (tz.dim() != 2 or tz.shape[1] != n_s or not 1 <= tz.shape[0] <= hd.D - 1):
+            raise ValueError("a_gp_inp_x must be (n_x_in, {}) with 1 <= n_x_in <= {}".format(n_s, hd.D - 1))
+        n_x_in = n_s if tz is None else tz.shape[0]
+        n_u = hd.D - n_x_in
+        if n_u < 1:
+            raise ValueError("the closed loop needs D = n_x_in + n_u with n_u >= 1")
+        mu = B.as_dev(mu0, dev)
+        if mu.dim() != 2 or mu.shape[1] != n_s:
+            raise ValueError("mu0 must be (T, {})".format(n_s))
+        T = mu.shape[0]
+        kff = B.as_dev(k_ff, dev)
+        if kff.dim() not in (2, 3) or kff.shape[-1] != n_u or (kff.dim() == 3 and kff.shape[0] != T):
+            raise ValueError("k_ff must be (H, {0}) or (T, H, {0})".format(n_u))
+        per_traj = int(kff.dim() == 3)
+        H = kff.shape[-2]
+        if H < 1:
+            raise ValueError("k_ff needs H >= 1 steps")
+        kfb = None
+        if H > 1:
+            kfb = B.as_dev(k_fb, dev, ((T,) if per_traj else ()) + (H - 1, n_u, n_s))
+        sig = B.as_dev(sigma0, dev, (T, n_s, n_s)) if sigma0 is not None else None
+        ta, tb = B.as_dev(a, dev, (n_s, n_s)), B.as_dev(b, dev, (n_s, n_u))
+        kinv = self.inv_K_device()
+        mu_all, sigma_all = B.empty((T, H, n_s), dev), B.empty((T, H, n_s, n_s), dev)
+        cov_all = B.empty((T, H, n_s, n_s), dev) if with_cov else None
+        check(lib.sr_gp_moment_match_rollout(hd.h, T, H, n_x_in, per_traj, B.ptr(mu), B.ptr(sig), B.ptr(kff), B.ptr(kfb),
+                                             B.ptr(ta), B.ptr(tb), B.ptr(tz), B.ptr(kinv), B.ptr(mu_all), B.ptr(sigma_all),
+                                             B.ptr(cov_all), B.stream_ptr(dev)))
+        return mu_all, sigma_all, cov_all
+
     def moment_match_vjp_device(self, m, S, mu_bar=None, cov_bar=None, V_bar=None):
         """Reverse pass of ``moment_match_device`` (``sr_gp_moment_match_vjp``): for seeds mu_bar (T, n), cov_bar (T, n, n),
         V_bar (T, n, D) (None = zero) the derivatives m_bar (T, D) and S_bar (T, D, D) of

@@ -10,7 +10,8 @@ The input transform ``a_gp_inp_x`` of the reference (the GP sees ``a_gp_inp_x @ 
 the state Jacobian is chain-ruled through the constant matrix.
 
 Beyond the reference: EXACT moment matching (``MOMENT_MATCHING``; ``one_step_moment_matching``,
-``multi_step_moment_matching``, ``moment_matching_batch``), the scheme the two above approximate.  The GP is evaluated at
+``multi_step_moment_matching``, ``moment_matching_batch``; ``moment_matching_rollout_batch``: the whole horizon in one launch),
+the scheme the two above approximate.  The GP is evaluated at
 the Gaussian input z = G x + g0, G = [a_gp_inp_x; K], g0 = [0; k_ff] (``SimpleGPModel.moment_match_device``: mean, full
 covariance across outputs and expected Jacobian V in closed form), and with A = a + b K
 ``mu_new = A mu + b k_ff + mu_g``, ``Sigma_new = (A + V G) Sigma (A + V G)^T + Cov - (V G) Sigma (V G)^T``.
@@ -437,6 +438,30 @@ def moment_matching_batch(mu_0, ssm, k_ff, k_fb, a=None, b=None, sigma_0=None, a
         mu, sigma, cov = _mm_step(ssm, mu, sigma, kff[:, i], None if i == 0 else kfb[:, i - 1], ta, tb, tz)
         mu_all[:, i], sigma_all[:, i], cov_all[:, i] = mu, sigma, cov
     outs = (mu_all, sigma_all, cov_all)
+    return outs if as_t else tuple(B.to_numpy(o) for o in outs)
+
+
+def moment_matching_rollout_batch(mu_0, ssm, k_ff, k_fb, a=None, b=None, sigma_0=None, a_gp_inp_x=None):
+    """``moment_matching_batch`` with all H steps of every trajectory in ONE launch (``sr_gp_moment_match_rollout``,
+    ``SimpleGPModel.moment_match_rollout_device``): the same arguments (mu_0 (T,n_s); k_ff (T,H,n_u); k_fb (T,H-1,n_u,n_s);
+    sigma_0 (T,n_s,n_s) or None) and the same three results, mu_all (T,H,n_s), sigma_all (T,H,n_s,n_s), gp_cov_all
+    (T,H,n_s,n_s), equal to those of ``moment_matching_batch`` to rounding (the double sum is added in another order).
+    NumPy in -> NumPy out; device tensors in -> device tensors out.
+    Inside the fused kernel's domain -- ARD-RBF models, exact or sparse, with N <= 1024 and D <= 12 -- it calls the fused
+    kernel; outside of it (a ``lin_rbf`` model, a larger model) it calls ``moment_matching_batch`` and returns what that
+    returns."""
+    dev, n_s, n_u, ta, tb, tz = _mm_setup(ssm, a, b, a_gp_inp_x)
+    if not ssm.moment_match_rollout_supported():
+        return moment_matching_batch(mu_0, ssm, k_ff, k_fb, a, b, sigma_0, a_gp_inp_x)
+    as_t = B.is_tensor(mu_0)
+    mu = B.as_dev(mu_0, dev)
+    T = mu.shape[0]
+    kff = B.as_dev(k_ff, dev)
+    if mu.dim() != 2 or mu.shape[1] != n_s or kff.dim() != 3 or kff.shape[0] != T or kff.shape[2] != n_u:
+        raise ValueError("mu_0 must be (T, {}) and k_ff (T, H, {})".format(n_s, n_u))
+    H = kff.shape[1]
+    kfb = B.as_dev(k_fb, dev, (T, H - 1, n_u, n_s)) if H > 1 else None
+    outs = ssm.moment_match_rollout_device(mu, kff, kfb, ta, tb, sigma_0, None if a_gp_inp_x is None else tz)
     return outs if as_t else tuple(B.to_numpy(o) for o in outs)
 
 
