@@ -48,6 +48,23 @@ def main():
     for i in range(n):
         print("%4d  %.5f | %.5f" % (i, np.trace(np.cov(consistent[i].T)), np.trace(np.cov(marginal[i].T))))
 
+    # the same with the reference's "lin_rbf" kernel on the second state (linear x RBF on input dimension 1 + ARD linear): a
+    # model of the general kernel family, whose prior sample is a sum over products of features (G M + D weights per path)
+    hyp[1] = {"prod.rbf.lengthscale": 0.9, "prod.rbf.variance": 0.5, "prod.linear.variances": 1.0,
+              "linear.variances": np.array([0.3, 0.6, 0.1]), "noise_variance": 1e-3}
+    gl = SimpleGPModel(n_s, n_s, n_u, kern_types=["rbf", "lin_rbf"], hyp=hyp)
+    gl.train(Z, Y, opt_hyp=False)
+    print("\nrbf / lin_rbf model: %d weights per path for 1024 features" % gl.paths_weight_count(1024))
+    ml = MonteCarloSafetyVerification(gl)
+    _, consistent, A = ml.sample_n_step_jacobians(x0, K, k, n=n, n_samples=S)           # draws the paths itself
+    _, marginal = ml.sample_n_step(x0, K, k, n=n, n_samples=S)
+    _, chained = ml.rollout_paths(x0, K, k, n=n, n_samples=S)                           # no one-launch form: the chained steps
+    print("rollout_paths on the family: max difference to the chained steps %.1e" % np.abs(chained - consistent).max())
+    print("step  spread: consistent | marginal      mean |d x_(i+1) / d x_i| over the particles")
+    for i in range(n):
+        print("%4d  %.5f | %.5f      %.3f" % (i, np.trace(np.cov(consistent[i].T)), np.trace(np.cov(marginal[i].T)),
+                                             np.abs(A[i]).mean()))
+
 
 if __name__ == "__main__":
     main()

@@ -484,7 +484,8 @@ int sr_gp_sample(int device, long T, int size, int n_out, int n_u, const double*
                  void* stream);
 
 /* ---- posterior FUNCTION samples: pathwise conditioning (Matheron's rule on a random-Fourier-feature prior) ----------
- * S whole posterior functions of an ARD-RBF model that can be evaluated anywhere, consistently, in O(N + M) per value:
+ * S whole posterior functions of an ARD-RBF model (or of a general-family model with the RBF radial part: further down)
+ * that can be evaluated anywhere, consistently, in O(N + M) per value:
  * per output d and path s, with l_d, sf2_d the kernel's parameters and n_d the diagonal term as sr_gp_set_data received it,
  *   phi_d(x)_i = sqrt(2 sf2_d / M) cos(sum_j omega[i][j] x_j / l_d[j] + tau[i])                         i < M
  *   c_{d,s}    = K_y,d^-1 (y_d - Phi_d(Z) w_{d,s} - sqrt(n_d) eps_{d,s}) = U^-1 (U^-T r_{d,s})            (N)
@@ -510,8 +511,9 @@ int sr_gp_sample(int device, long T, int size, int n_out, int n_u, const double*
  * calls, not the paths.
  * All errors are found on the host before any launch, and invalid arguments leave paths drawn earlier intact: SR_EINVAL NULL
  * where not allowed, S < 0, M < 1 or M > 1048560 with S > 0, T < 0; SR_ESTATE not factorized, a sparse handle (Wt is not the factor of K_y),
- * between sr_gp_import_begin and sr_gp_import_end, no valid paths; SR_EUNSUPPORTED a general-family model (the feature map
- * is the Gaussian spectral density: mat52 / lin_* are out of scope) or D > 8, as the other batched entry points.
+ * between sr_gp_import_begin and sr_gp_import_end, no valid paths; SR_EUNSUPPORTED a general-family model with a Matern
+ * output (the feature map is the Gaussian spectral density: mat52 / lin_mat52 are out of scope; nothing is read from the
+ * caller's arrays) or D > 8, as the other batched entry points.
  * sr_gp_paths_eval_grad / _step_grad: the same calls with the Jacobian of every value in the input,
  *   d f_{d,s}(x) / d x_j = -sqrt(2 sf2_d / M) / l_d[j] sum_i sin(omega_i . x / l_d + tau_i) omega[i][j] w_{d,s,i}
  *                          + sf2_d / l_d[j]^2 sum_i exp(-r_i^2 / 2) (z_ij - x_j) c_{d,s,i}
@@ -520,10 +522,25 @@ int sr_gp_sample(int device, long T, int size, int n_out, int n_u, const double*
  * SR_EINVAL), the states and the invalidation are theirs.  Deterministic, no atomics.  Workspace (grow-only, freed by
  * sr_gp_release_scratch): _eval_grad one more feature slab and one K*-sized slab per chunk, n_out (2 Mp + Np) Tp doubles in
  * all; _step_grad 1 + D times the partial sums of _step.
- * Out of scope: Hessians of the paths, replication of paths to other ranks, general kernels. */
+ * The general family (sr_gp_set_data_general) with the RBF radial part on every output, k = (c0 + sum_j a_j x_j y_j) v kappa(r)
+ * + sum_j b_j x_j y_j, r^2 = sum_j (s_j (x_j - y_j))^2: a sum of products of PSD kernels, so a prior sample is a sum over
+ * products of their features.  With base_i(x) = sqrt(2 v / M) cos(sum_j omega[i][j] s_j x_j + tau[i]) (omega, tau as above),
+ * A_0(x) = sqrt(c0), A_l(x) = sqrt(a_l) x_l (l = 1 .. D) and the G active groups -- the l, ascending, whose c0 resp. a_l is
+ * non-zero on at least one output of the handle --
+ *   f_prior(x) = sum_{g < G} A_{l_g}(x) sum_{i < M} w[g M + i] base_i(x) + sum_j sqrt(b_j) x_j w[G M + j]
+ * takes n_w = G M + D weights per path and output: w is n_out x S x n_w (sr_gp_paths_weight_count; M for an ARD-RBF handle),
+ * c and f(x) = phi(x) . w + k(x, Z) c are as above and sr_gp_paths_count keeps returning the base M.  The Jacobian: the
+ * features' d/dx_j [A_l base_i] = [l == j + 1] sqrt(a_j) base_i - A_l sqrt(2 v / M) sin(..) omega[i][j] s_j and sqrt(b_j)
+ * w[G M + j], plus sum_i c_i dk(x, z_i)/dx_j with dk/dx_j = a_j z_j v kappa - (c0 + sum a x z) v kappa s_j^2 (x_j - z_j)
+ * + b_j z_j.  Layouts, chunks, invalidation, errors, determinism and F of the _grad forms are those above; v, c0, a_j and b_j
+ * sit under square roots: a negative one is SR_EINVAL at the draw (named in the error text; paths drawn earlier stay).
+ * sr_gp_paths_weight_count: n_w for M features, with the refusals of sr_gp_paths_draw in its order (M, the model, the signs).
+ * Out of scope: Hessians of the paths, replication of paths to other ranks, Matern radial parts (their spectral draw is a
+ * Student-t, a rule for the caller's omega), the roll-out in one launch for the general family (below). */
 int sr_gp_paths_draw(sr_gp_t h, int S, int M, const double* omega, const double* tau, const double* w, const double* eps,
                      void* stream);
 int sr_gp_paths_count(sr_gp_t h, int* S, int* M);
+int sr_gp_paths_weight_count(sr_gp_t h, int M, int* n_w);
 int sr_gp_paths_eval(sr_gp_t h, const double* Xq, long T, double* F, void* stream);
 int sr_gp_paths_step(sr_gp_t h, const double* Xs, double* F, const double* k_fb, const double* k_ff, double* z_next,
                      void* stream);

@@ -91,6 +91,7 @@ SIGNATURES = {
     "sr_gp_sample": (_I, [_I, _L, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "sr_gp_paths_draw": (_I, [_H, _I, _I, _P, _P, _P, _P, _P]),
     "sr_gp_paths_count": (_I, [_H, _PI, _PI]),
+    "sr_gp_paths_weight_count": (_I, [_H, _I, _PI]),
     "sr_gp_paths_eval": (_I, [_H, _P, _L, _P, _P]),
     "sr_gp_paths_step": (_I, [_H, _P, _P, _P, _P, _P, _P]),
     "sr_gp_paths_eval_grad": (_I, [_H, _P, _L, _P, _P, _P]),

@@ -318,6 +318,37 @@ extern "C" int sr_gp_set_data_general(sr_gp_t h, const double* Z, const double* 
     return SR_OK;
 }
 
+int srh::general_info(sr_gp* h, hipStream_t s) {
+    if (h->gen_rbf >= 0) return SR_OK;
+    const int D = h->D, KP = SR_KP(D);
+    std::vector<double> kp((size_t)h->n_out * KP);
+    SR_HIP(hipMemcpyAsync(kp.data(), h->kp, sizeof(double) * kp.size(), hipMemcpyDeviceToHost, s));
+    SR_HIP(hipStreamSynchronize(s));
+    int rbf = 1;
+    unsigned groups = 0;
+    h->gen_negative[0] = 0;
+    auto negative = [&](int o, const char* name, int j, double val) {
+        if (!(val < 0.0) || h->gen_negative[0]) return;
+        if (j < 0) snprintf(h->gen_negative, sizeof h->gen_negative, "output %d: %s = %g", o, name, val);
+        else snprintf(h->gen_negative, sizeof h->gen_negative, "output %d: %s[%d] = %g", o, name, j, val);
+    };
+    for (int o = 0; o < h->n_out; ++o) {
+        const double* q = kp.data() + (size_t)o * KP;
+        if (q[0] != 0.0) rbf = 0;
+        negative(o, "v", -1, q[1]);
+        negative(o, "c0", -1, q[2]);
+        if (q[2] != 0.0) groups |= 1u;
+        for (int j = 0; j < D; ++j) {
+            negative(o, "a", j, q[3 + D + j]);
+            negative(o, "b", j, q[3 + 2 * D + j]);
+            if (q[3 + D + j] != 0.0 && j < 31) groups |= 2u << j;
+        }
+    }
+    h->gen_groups = groups;
+    h->gen_rbf = rbf;
+    return SR_OK;
+}
+
 extern "C" int sr_gp_dims(sr_gp_t h, int* N, int* D, int* n_out, long* Np) {
     SR_CHECK(h != nullptr, SR_EINVAL, "sr_gp_dims: NULL handle");
     if (N) *N = h->N;

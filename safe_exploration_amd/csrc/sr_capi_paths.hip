@@ -1,18 +1,34 @@
 // sr_capi_paths.hip -- posterior function samples by pathwise conditioning: sr_gp_paths_draw / _count / _eval / _step and
 // their Jacobians sr_gp_paths_eval_grad / _step_grad (the same plans with J: one body each), and the closed-loop roll-out in one
 // launch, sr_gp_paths_rollout, with its reverse pass sr_gp_paths_rollout_vjp.  The algebra: include/safereach.h; the kernels:
-// sr_paths.hip, sr_paths_rollout.hip, sr_paths_rollout_vjp.hip.
+// sr_paths.hip, sr_paths_rollout.hip, sr_paths_rollout_vjp.hip; for a general-family handle with the RBF radial part the
+// feature slab, dK* and the step of sr_paths_gen.hip in their places (draw, _eval, _step and their Jacobians; the roll-out in
+// one launch is refused), with G M + D weights per path instead of M (sr_gp_paths_weight_count).
 // Host-side orchestration only.
 #include "sr_handle.h"
 using namespace srh;
 
 namespace {
 
+// the feature map of a general-family handle (after model_checks: the groups are read, D <= SR_PATHS_MAX_D)
+sr_paths_gen gen_args(const sr_gp* h, int M) {
+    sr_paths_gen g;
+    g.kp = h->kp; g.G = 0;
+    for (int l = 0; l <= h->D; ++l)
+        if (h->gen_groups >> l & 1u) g.grp[g.G++] = l;
+    for (int q = g.G; q <= SR_PATHS_MAX_D; ++q) g.grp[q] = -1;
+    g.n_w = g.G * M + h->D;
+    return g;
+}
+// weights per path and output: the M features of the ARD-RBF kernel, G M + D for the general family
+int weight_count(const sr_gp* h, int M) { return h->general ? gen_args(h, M).n_w : M; }
+
 // the handle's block of drawn paths: [omega M x D | tau M | w n_out x Mp x Sp | c n_out x Np x Sp], every part 16-byte aligned
+// (Mp: the weights per path, to 16)
 struct paths_layout {
     int S, M, Sp, Mp; size_t o_tau, o_w, o_c, total;
     paths_layout(const sr_gp* h, int S_, int M_) : S(S_), M(M_) {
-        Sp = (int)round_up(S, srt::BN); Mp = (int)round_up(M, srt::BK);
+        Sp = (int)round_up(S, srt::BN); Mp = (int)round_up(weight_count(h, M), srt::BK);
         o_tau = (size_t)round_up((long)M * h->D, 2);
         o_w = o_tau + (size_t)round_up(M, 2);
         o_c = o_w + (size_t)h->n_out * Mp * Sp;
@@ -29,13 +45,36 @@ sr_paths_feat feat_args(const sr_gp* h, const paths_layout& L) {
     return m;
 }
 
-// what all three calls ask of the model (after their own arguments, before the question whether paths exist)
-int model_checks(const sr_gp* h, const char* who) {
+// the feature slab (jg >= 0: its derivative in input dimension jg) by the handle's kernel
+int launch_features(const sr_gp* h, const paths_layout& L, const double* X, long T, long col0, long ncols, double* Phi,
+                    hipStream_t s, int jg = -1) {
+    const sr_paths_feat fm = feat_args(h, L);
+    if (h->general) return sr_launch_paths_gen_features(fm, gen_args(h, L.M), X, h->D, T, col0, ncols, Phi, s, jg);
+    return sr_launch_paths_features(fm, X, h->D, T, col0, ncols, Phi, s, jg);
+}
+
+// what all calls ask of the model (after their own arguments, before the question whether paths exist).  A general-family
+// handle: its packed parameters are read back once per data set (behind `s`); fused: the roll-out in one launch, which the
+// family does not have.
+int model_checks(sr_gp* h, const char* who, hipStream_t s, bool fused = false) {
     SR_CHECK(h->factorized && !h->import_open, SR_ESTATE, "%s: model not factorized%s", who,
              h->import_open ? " (between sr_gp_import_begin and sr_gp_import_end)" : "");
     SR_CHECK(!h->sparse, SR_ESTATE, "%s: sparse model (U^-1 is not the factor of K_y)", who);
-    SR_CHECK(!h->general, SR_EUNSUPPORTED, "%s: general kernel family (the feature map is that of the ARD-RBF kernel)", who);
+    SR_CHECK(!(h->general && fused), SR_EUNSUPPORTED,
+             "%s: general kernel family (the roll-out in one launch is that of the ARD-RBF kernel: chain sr_gp_paths_step)", who);
     SR_CHECK(h->D <= SR_PATHS_MAX_D, SR_EUNSUPPORTED, "%s: D=%d > %d", who, h->D, SR_PATHS_MAX_D);
+    if (!h->general) return SR_OK;
+    SR_DEVICE(h->device);
+    SR_TRY(general_info(h, s));
+    SR_CHECK(h->gen_rbf, SR_EUNSUPPORTED,
+             "%s: general kernel family with a Matern output (the feature map is the Gaussian spectral density)", who);
+    return SR_OK;
+}
+// ... and the draw of its parameters: each sits under a square root (and its slab has one more strip along grid.y)
+int sign_check(const sr_gp* h, const char* who, int M) {
+    if (!h->general) return SR_OK;
+    SR_CHECK(!h->gen_negative[0], SR_EINVAL, "%s: negative kernel parameter (%s)", who, h->gen_negative);
+    SR_CHECK(M <= 65534 * SR_PATHS_FROWS, SR_EINVAL, "%s: M=%d outside 1..%d (general family)", who, M, 65534 * SR_PATHS_FROWS);
     return SR_OK;
 }
 
@@ -46,6 +85,22 @@ extern "C" int sr_gp_paths_count(sr_gp_t h, int* S, int* M) {
     const bool ok = paths_valid(h);
     if (S) *S = ok ? h->paths_S : 0;
     if (M) *M = ok ? h->paths_M : 0;
+    return SR_OK;
+}
+
+// the refusals of the draw in its order (M, the model, the signs); the one-off readback of a general handle's parameters waits
+// for the device, as this call has no stream
+extern "C" int sr_gp_paths_weight_count(sr_gp_t h, int M, int* n_w) {
+    const char* who = "sr_gp_paths_weight_count";
+    SR_CHECK(h != nullptr && n_w != nullptr, SR_EINVAL, "%s: NULL argument", who);
+    SR_CHECK(M >= 1 && M <= 65535 * SR_PATHS_FROWS, SR_EINVAL, "%s: M=%d outside 1..%d", who, M, 65535 * SR_PATHS_FROWS);
+    if (h->general && h->gen_rbf < 0 && h->factorized && !h->import_open && !h->sparse && h->D <= SR_PATHS_MAX_D) {
+        SR_DEVICE(h->device);
+        SR_HIP(device_sync());
+    }
+    SR_TRY(model_checks(h, who, nullptr));
+    SR_TRY(sign_check(h, who, M));
+    *n_w = weight_count(h, M);
     return SR_OK;
 }
 
@@ -64,8 +119,9 @@ extern "C" int sr_gp_paths_draw(sr_gp_t h, int S, int M, const double* omega, co
     // (the feature slab takes 16 features per workgroup along grid.y)
     SR_CHECK(M >= 1 && M <= 65535 * SR_PATHS_FROWS, SR_EINVAL, "sr_gp_paths_draw: M=%d outside 1..%d", M, 65535 * SR_PATHS_FROWS);
     SR_CHECK(omega && tau && w && eps, SR_EINVAL, "sr_gp_paths_draw: NULL argument");
-    SR_TRY(model_checks(h, "sr_gp_paths_draw"));
     hipStream_t s = (hipStream_t)stream;
+    SR_TRY(model_checks(h, "sr_gp_paths_draw", s));
+    SR_TRY(sign_check(h, "sr_gp_paths_draw", M));
     SR_DEVICE(h->device);
     SR_TRY(tile_route_alignment(h));                     // (the two triangular products read U^-1 in 16-byte pieces)
     const int N = h->N, Np = h->Np, off = Np - N, n_out = h->n_out;
@@ -80,9 +136,8 @@ extern "C" int sr_gp_paths_draw(sr_gp_t h, int S, int M, const double* omega, co
     sr_prof_scope ps(&h->prof, SR_K_PATHS_DRAW, s);
     SR_HIP(hipMemcpyAsync(P, omega, sizeof(double) * M * h->D, hipMemcpyDeviceToDevice, s));
     SR_HIP(hipMemcpyAsync(P + L.o_tau, tau, sizeof(double) * M, hipMemcpyDeviceToDevice, s));
-    SR_TRY(sr_launch_paths_pack(w, Wk, nullptr, nullptr, M, 0, L.Mp, S, L.Sp, n_out, s));
-    const sr_paths_feat fm = feat_args(h, L);
-    SR_TRY(sr_launch_paths_features(fm, h->Z, h->D, N, off, Np, Phi, s));
+    SR_TRY(sr_launch_paths_pack(w, Wk, nullptr, nullptr, weight_count(h, M), 0, L.Mp, S, L.Sp, n_out, s));
+    SR_TRY(launch_features(h, L, h->Z, N, off, Np, Phi, s));
     // the prior at the training rows, P = Phi(Z)^T w (Np x Sp per output), then R = y - P - sqrt(n_d) eps^T in its place
     sr_batch bp; bp.n = n_out; bp.sA = (long)L.Mp * Np; bp.sB = (long)L.Mp * L.Sp; bp.sC = (long)Np * L.Sp;
     SR_TRY(sr_launch_gemm_tn(Phi, Np, Wk, L.Sp, R, L.Sp, Np, L.Sp, L.Mp, 1.0, 0.0, 0, s, 0, &bp));
@@ -105,14 +160,13 @@ int paths_eval(sr_gp_t h, const double* Xq, long T, double* F, double* J, bool g
     SR_CHECK(T >= 0, SR_EINVAL, "%s: T=%ld", who, T);
     SR_CHECK(grad ? J != nullptr : true, SR_EINVAL, "%s: NULL J", who);
     SR_CHECK(T == 0 || (Xq && (F || grad)), SR_EINVAL, "%s: NULL argument", who);
-    SR_TRY(model_checks(h, who));
+    hipStream_t s = (hipStream_t)stream;
+    SR_TRY(model_checks(h, who, s));
     SR_CHECK(paths_valid(h), SR_ESTATE, "%s: no valid paths (sr_gp_paths_draw after the last model update)", who);
     if (T == 0) return SR_OK;
-    hipStream_t s = (hipStream_t)stream;
     SR_DEVICE(h->device);
     const paths_layout L(h, h->paths_S, h->paths_M);
     const double *P = h->paths.get(), *Wk = P + L.o_w, *C = P + L.o_c;
-    const sr_paths_feat fm = feat_args(h, L);
     for (long t0 = 0; t0 < T; t0 += h->chunk) {
         const long Tc = std::min(h->chunk, T - t0);
         const long Tp = round_up(Tc, srt::BN);
@@ -129,15 +183,18 @@ int paths_eval(sr_gp_t h, const double* Xq, long T, double* F, double* J, bool g
         }
         sr_prof_scope ps(&h->prof, SR_K_PATHS_EVAL, s);
         if (F) {
-            SR_TRY(sr_launch_paths_features(fm, Xc, h->D, Tc, 0, Tp, h->paths_ws.get(), s));
+            SR_TRY(launch_features(h, L, Xc, Tc, 0, Tp, h->paths_ws.get(), s));
             SR_TRY(sr_launch_paths_eval(h->paths_ws.get(), Wk, h->Ks, C, F + t0 * L.S * h->n_out, h->N, h->Np, L.Mp, Tc, Tp, L.S,
                                         L.Sp, h->n_out, s));
         }
         if (!grad) continue;
         double *dPhi = h->paths_ws.get() + n_phi, *dKs = dPhi + n_phi;
         for (int j = 0; j < h->D; ++j) {
-            SR_TRY(sr_launch_paths_features(fm, Xc, h->D, Tc, 0, Tp, dPhi, s, j));
-            SR_TRY(sr_launch_paths_dkstar(h->Ks, dKs, h->Z, Xc, h->ls, h->N, h->Np, h->D, h->n_out, Tc, Tp, j, s));
+            SR_TRY(launch_features(h, L, Xc, Tc, 0, Tp, dPhi, s, j));
+            if (h->general)                              // (from Z, X and kp: not K* times a factor)
+                SR_TRY(sr_launch_paths_gen_dkstar(dKs, h->Z, Xc, h->kp, h->N, h->Np, h->D, h->n_out, Tc, Tp, j, s));
+            else
+                SR_TRY(sr_launch_paths_dkstar(h->Ks, dKs, h->Z, Xc, h->ls, h->N, h->Np, h->D, h->n_out, Tc, Tp, j, s));
             SR_TRY(sr_launch_paths_eval(dPhi, Wk, dKs, C, J + t0 * L.S * h->n_out * h->D + j, h->N, h->Np, L.Mp, Tc, Tp, L.S, L.Sp,
                                         h->n_out, s, h->n_out * h->D, h->D));
         }
@@ -166,9 +223,9 @@ int paths_step(sr_gp_t h, const double* Xs, double* F, double* J, bool grad, con
              "%s: k_fb, k_ff and z_next come together", who);
     SR_CHECK(!k_fb || h->D > h->n_out, SR_EINVAL, "%s: the closed loop needs D = n_out + n_u (D=%d, n_out=%d)", who, h->D,
              h->n_out);
-    SR_TRY(model_checks(h, who));
-    SR_CHECK(paths_valid(h), SR_ESTATE, "%s: no valid paths (sr_gp_paths_draw after the last model update)", who);
     hipStream_t s = (hipStream_t)stream;
+    SR_TRY(model_checks(h, who, s));
+    SR_CHECK(paths_valid(h), SR_ESTATE, "%s: no valid paths (sr_gp_paths_draw after the last model update)", who);
     SR_DEVICE(h->device);
     const paths_layout L(h, h->paths_S, h->paths_M);
     sr_paths_step_args a;
@@ -180,7 +237,7 @@ int paths_step(sr_gp_t h, const double* Xs, double* F, double* J, bool grad, con
     SR_TRY(h->paths_ws.grow((size_t)a.nsplit * h->n_out * (grad ? 1 + h->D : 1) * L.Sp, wait::device()));
     a.part = h->paths_ws.get();
     sr_prof_scope ps(&h->prof, SR_K_PATHS_STEP, s);
-    return sr_launch_paths_step(a, s);
+    return h->general ? sr_launch_paths_gen_step(a, gen_args(h, L.M), s) : sr_launch_paths_step(a, s);
 }
 
 }  // namespace
@@ -203,7 +260,7 @@ extern "C" int sr_gp_paths_rollout(sr_gp_t h, const double* x0, int x0_per_path,
     SR_CHECK(x0 && k_fb && k_ff && X_all, SR_EINVAL, "%s: NULL argument", who);
     SR_CHECK(H >= 1 && (x0_per_path == 0 || x0_per_path == 1), SR_EINVAL, "%s: H=%d x0_per_path=%d", who, H, x0_per_path);
     SR_CHECK(h->D > h->n_out, SR_EINVAL, "%s: the closed loop needs D = n_out + n_u (D=%d, n_out=%d)", who, h->D, h->n_out);
-    SR_TRY(model_checks(h, who));
+    SR_TRY(model_checks(h, who, (hipStream_t)stream, true));
     SR_CHECK(paths_valid(h), SR_ESTATE, "%s: no valid paths (sr_gp_paths_draw after the last model update)", who);
     hipStream_t s = (hipStream_t)stream;
     SR_DEVICE(h->device);
@@ -226,7 +283,7 @@ extern "C" int sr_gp_paths_rollout_vjp(sr_gp_t h, const double* x0, int x0_per_p
     SR_CHECK(x0 && k_fb && k_ff && X_all && X_bar && x0_bar && k_fb_bar && k_ff_bar, SR_EINVAL, "%s: NULL argument", who);
     SR_CHECK(H >= 1 && (x0_per_path == 0 || x0_per_path == 1), SR_EINVAL, "%s: H=%d x0_per_path=%d", who, H, x0_per_path);
     SR_CHECK(h->D > h->n_out, SR_EINVAL, "%s: the closed loop needs D = n_out + n_u (D=%d, n_out=%d)", who, h->D, h->n_out);
-    SR_TRY(model_checks(h, who));
+    SR_TRY(model_checks(h, who, (hipStream_t)stream, true));
     SR_CHECK(paths_valid(h), SR_ESTATE, "%s: no valid paths (sr_gp_paths_draw after the last model update)", who);
     hipStream_t s = (hipStream_t)stream;
     SR_DEVICE(h->device);

@@ -343,20 +343,6 @@ extern "C" int sr_multistep_moments(sr_gp_t h, long T, int H, int mode, const do
                           gp_var_all, nullptr, (hipStream_t)stream);
 }
 
-// sr_gp_set_data_general leaves the radial identifiers on the device: read them once per data set (one blocking copy of the
-// packed parameters behind `s`) -> h->gen_rbf = every output has kappa id 0
-static int general_radial_is_rbf(sr_gp_t h, hipStream_t s) {
-    if (h->gen_rbf >= 0) return SR_OK;
-    std::vector<double> kp((size_t)h->n_out * SR_KP(h->D));
-    SR_HIP(hipMemcpyAsync(kp.data(), h->kp, sizeof(double) * kp.size(), hipMemcpyDeviceToHost, s));
-    SR_HIP(hipStreamSynchronize(s));
-    int rbf = 1;
-    for (int o = 0; o < h->n_out; ++o)
-        if (kp[(size_t)o * SR_KP(h->D)] != 0.0) rbf = 0;
-    h->gen_rbf = rbf;
-    return SR_OK;
-}
-
 // the general family with the RBF radial part (sr_moment_match_gen.hip): the scratch holds the per-call block (Kinv Z,
 // Z^T Kinv Z, Z^T alpha of every output) in front of the chunk's records
 static int moment_match_general(sr_gp_t h, const double* m, const double* S, long T, const double* inv_k, double* mu,
@@ -386,7 +372,7 @@ extern "C" int sr_gp_moment_match(sr_gp_t h, const double* m, const double* S, l
     hipStream_t s = (hipStream_t)stream;
     if (h->general) {
         SR_DEVICE(h->device);
-        SR_TRY(general_radial_is_rbf(h, s));
+        SR_TRY(general_info(h, s));
         if (!h->gen_rbf) {
             sr_set_error("sr_gp_moment_match: the closed form is for ARD-RBF models and the general family with the RBF "
                          "radial part only (a Matern output has none)");

@@ -638,6 +638,23 @@ struct sr_paths_rollout_vjp_args {
     int N, Np, S, Sp, nsplit;
 };
 int sr_launch_paths_rollout_vjp(const sr_paths_rollout_vjp_args& a, hipStream_t s);
+// ---- the same for the general family with the RBF radial part (sr_paths_gen.hip; the algebra: include/safereach.h) -----------
+// A path of one output takes n_w = G M + D weights: group g < G is the base feature map times A_grp[g](x) (A_0 = sqrt(c0),
+// A_l = sqrt(a_l) x_l; grp: the l active on at least one output, ascending), rows [g M, (g + 1) M) of the slab; the linear
+// features sqrt(b_j) x_j are rows G M + j.  m.M is the base count M, m.Mp is n_w rounded up to SR_PATHS_FROWS, m.ls and
+// m.sf2 are not read (the parameters are kp: n_out x SR_KP(D), kappa id 0 on every output, nothing negative).
+struct sr_paths_gen {
+    const double* kp; int G, n_w; int grp[SR_PATHS_MAX_D + 1];
+};
+// Phi[d][g M + i][c] = A_grp[g](x_t) sqrt(2 v_d / M) cos(sum_j omega[i][j] s_dj x_tj + tau[i]) and Phi[d][G M + j][c] =
+// sqrt(b_dj) x_tj, t = c - col0, for 0 <= t < T; zero elsewhere (rows < m.Mp, c < ncols).  jg >= 0: the derivative in x_jg
+int sr_launch_paths_gen_features(const sr_paths_feat& m, const sr_paths_gen& g, const double* X, long ldx, long T, long col0,
+                                 long ncols, double* Phi, hipStream_t s, int jg = -1);
+// dKs[d][k][c] = d k_d(x_c, z_{k - (Np - N)}) / d x_jg (sr_dk) on the real rows and the columns c < T, zero elsewhere
+int sr_launch_paths_gen_dkstar(double* dKs, const double* Z, const double* X, const double* kp, int N, int Np, int D, int n_out,
+                               long T, long Tp, int jg, hipStream_t s);
+// the step: a.part in the layout of sr_launch_paths_step (whose ordered sum runs behind it), a.Wk n_out x m.Mp x Sp
+int sr_launch_paths_gen_step(const sr_paths_step_args& a, const sr_paths_gen& g, hipStream_t s);
 
 struct sr_final_args {
     const double* mu_part; const double* jac_part; const double* var_part; const double* sf2;

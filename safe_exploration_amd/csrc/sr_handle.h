@@ -9,7 +9,8 @@
 //                          input transform, completion mailbox
 //   sr_capi_reach.hip      reachability / moment / sampling entry points and the persistent-chain dispatch
 //   sr_capi_server.hip     resident single-query server: start / stop / blocking call
-//   sr_capi_paths.hip      posterior function samples by pathwise conditioning (sr_gp_paths_draw / _count / _eval / _step)
+//   sr_capi_paths.hip      posterior function samples by pathwise conditioning (sr_gp_paths_draw / _count / _weight_count /
+//                          _eval / _step ...)
 #pragma once
 #include "sr_mfma_tile.h"
 #include <atomic>
@@ -107,7 +108,10 @@ struct sr_gp {
     int chain_test_drop = 0;                                              // sr_test_chain_drop
     unsigned* call_ticket = nullptr;        // sr_gp_call1: workgroups done (reset by the last one)
     int general = 0;
-    int gen_rbf = -1;        // general: every output has the RBF radial part (kappa id 0); -1 = not read yet (sr_gp_moment_match)
+    // general: what srh::general_info read back from the packed parameters of this data set (gen_rbf == -1: not read yet) --
+    // every output has the RBF radial part (kappa id 0); the groups of the paths' feature map, bit l set where c0 (l = 0) or
+    // a_l is non-zero on at least one output (l <= D, D <= SR_PATHS_MAX_D); the first negative v, c0, a_j or b_j by name
+    int gen_rbf = -1; unsigned gen_groups = 0; char gen_negative[48] = "";
     int have_data = 0, factorized = 0;
     int sparse = 0;          // the posterior is that of sr_gp_fit_sparse: Wt Wt^T = K_uu^-1 - Sigma^-1, not K_y^-1
     int import_open = 0;     // between sr_gp_import_begin and sr_gp_import_end
@@ -266,6 +270,9 @@ static inline double* wt_alloc_of(const sr_gp* h) { return h->Wt ? h->Wt - (size
 static inline double* alpha_alloc_of(const sr_gp* h) { return h->alpha ? h->alpha - h->slide : nullptr; }
 static inline double* yT_alloc_of(const sr_gp* h) { return h->yT ? h->yT - h->slide : nullptr; }
 static inline void model_rewritten(sr_gp* h) { ++h->model_gen; }     // (see sr_gp::model_gen)
+// sr_gp_set_data_general leaves the packed parameters on the device: read them once per data set (one blocking copy behind
+// `s`) -> h->gen_rbf, gen_groups, gen_negative.  Users: sr_gp_moment_match, sr_gp_paths_*.
+int general_info(sr_gp* h, hipStream_t s);
 int unslide(sr_gp* h);               // back to plain buffers (fresh allocations, two contiguous copies); no-op when slide == 0
 
 // The chain of launches of sr_gp_factorize on the caller's matrices (sr_capi_update.hip; the sparse fit, sr_sparse.hip):

@@ -27,6 +27,7 @@ class MonteCarloSafetyVerification(object):
         consistent=True: every particle is rolled through ITS OWN posterior function (SimpleGPModel.draw_paths: pathwise
         conditioning on n_features random features) instead of meeting an unrelated marginal draw at every step; the
         model's valid paths are used if there are n_samples of them, otherwise they are drawn here (eps is not read).
+        Models of "rbf" and "lin_rbf" kernels (NotImplementedError for a Matern kernel).
         Returns S (n_samples, n_s) and S_all (n, n_samples, n_s).  With the transition Jacobians of the consistent rollout:
         sample_n_step_jacobians."""
         if consistent:
@@ -109,11 +110,17 @@ class MonteCarloSafetyVerification(object):
         computes step by step -- to rounding, not bit for bit -- and returns as it does, S (n_samples, n_s) and S_all
         (n, n_samples, n_s); with jacobians=True what sample_n_step_jacobians returns, (S, S_all, A_all).  x0 may also be
         (n_samples, n_s): one start per particle.  The model's valid paths are used if there are n_samples of them,
-        otherwise they are drawn here."""
+        otherwise they are drawn here.  A model with a "lin_rbf" output has no one-launch roll-out: it goes through the
+        chained route of sample_n_step(consistent=True) (a single start x0 only)."""
         n_s, n_u = self.n_s, self.n_u
         assert n > 0, "The time horizon n for the multi-step sampling must be positive!"
         assert np.shape(K) == (n, n_u, n_s), "Required shape of K is ({},{},{})".format(n, n_u, n_s)
         assert np.shape(k) == (n, n_u), "Required shape of k is ({},{})".format(n, n_u)
+        if not self.GP._paths_fused_rollout_supported():
+            if np.ndim(x0) == 2 and np.shape(x0) == (n_samples, n_s) and np.shape(x0) != (n_s, 1):
+                raise NotImplementedError("rollout_paths: one start per particle needs the roll-out in one launch, which is for "
+                                          "ARD-RBF models only; a model with a lin_rbf output takes a single start x0")
+            return self._consistent_rollout(x0, K, k, n, n_samples, generator, as_tensor, n_features, jacobians)
         if self.GP.paths_count()[0] != n_samples:
             self.GP.draw_paths(n_samples, n_features, generator)
         out = self.GP.paths_rollout_device(x0, K, k, jacobians=jacobians)
@@ -129,7 +136,10 @@ class MonteCarloSafetyVerification(object):
         S (n_samples, n_s), a view of S_all[n - 1], and S_all (n, n_samples, n_s) -- the bits of rollout_paths -- and a cost
         of them can be differentiated once in those of x0, K, k that are tensors requiring a gradient (the reverse pass on
         the device, sr_gp_paths_rollout_vjp; the model and the draws get none).  The paths are drawn under rollout_paths'
-        rule: the model's valid ones if there are n_samples of them."""
+        rule: the model's valid ones if there are n_samples of them.  "rbf" models only: NotImplementedError for a model
+        with a "lin_rbf" output, before anything is drawn."""
+        if not self.GP._paths_fused_rollout_supported():
+            raise NotImplementedError("rollout_paths_diff: the reverse pass of the roll-out is for ARD-RBF models only")
         n_s, n_u = self.n_s, self.n_u
         assert n > 0, "The time horizon n for the multi-step sampling must be positive!"
         assert tuple(np.shape(K)) == (n, n_u, n_s), "Required shape of K is ({},{},{})".format(n, n_u, n_s)

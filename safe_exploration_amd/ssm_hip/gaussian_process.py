@@ -1553,15 +1553,18 @@ class SimpleGPModel(StateSpaceModel):
     def draw_paths(self, size, n_features=1024, generator=None, omega=None, tau=None, w=None, eps=None):
         """Draw `size` whole posterior FUNCTIONS (Matheron's rule on n_features random Fourier features of the ARD-RBF
         kernel; include/safereach.h) and keep them with the model until its next update.  The reference has no
-        counterpart: sample_from_gp draws marginal samples only.  The draws -- omega (M, D) and w (n_s_out, size, M) and
+        counterpart: sample_from_gp draws marginal samples only.  The draws -- omega (M, D) and w (n_s_out, size, n_w) and
         eps (n_s_out, size, N) standard normal, tau (M,) uniform in [0, 2 pi) -- come from torch's device generator where
-        not supplied."""
+        not supplied.  n_w = paths_weight_count(M): M for "rbf" models; a model with a "lin_rbf" output (the general family
+        with the RBF radial part) takes G M + D weights per path, G the number of its active groups.  Matern kernels:
+        NotImplementedError."""
         self._need_trained()
         hd = self._handle
         S, M = int(size), int(n_features)
         if S < 1 or M < 1:
             raise ValueError("draw_paths: size and n_features must be positive (got {}, {})".format(size, n_features))
         dev, n_out, N = hd.device, hd.n_out, hd.N
+        n_w = self.paths_weight_count(M)       # (the model's refusals come from here: before any shape is looked at)
 
         def draw(given, shape, uniform=False):
             if given is not None:
@@ -1571,8 +1574,20 @@ class SimpleGPModel(StateSpaceModel):
             return torch.randn(shape, dtype=torch.float64, device=dev, generator=generator)
 
         t_om, t_tau = draw(omega, (M, hd.D)), draw(tau, (M,), uniform=True)
-        t_w, t_eps = draw(w, (n_out, S, M)), draw(eps, (n_out, S, N))
+        t_w, t_eps = draw(w, (n_out, S, n_w)), draw(eps, (n_out, S, N))
         check(lib.sr_gp_paths_draw(hd.h, S, M, B.ptr(t_om), B.ptr(t_tau), B.ptr(t_w), B.ptr(t_eps), B.stream_ptr(dev)))
+
+    def paths_weight_count(self, n_features=1024):
+        """Weights per path and output that draw_paths(.., n_features) takes (sr_gp_paths_weight_count), with the draw's
+        refusals: NotImplementedError for a Matern kernel or D > 8, ValueError for a negative kernel parameter."""
+        self._need_trained()
+        n_w = ctypes.c_int(0)
+        check(lib.sr_gp_paths_weight_count(self._handle.h, int(n_features), ctypes.byref(n_w)))
+        return n_w.value
+
+    def _paths_fused_rollout_supported(self):
+        """the roll-out in one launch and its reverse pass hold the ARD-RBF feature map: "rbf" models only"""
+        return all(kt == "rbf" for kt in self.kern_types)
 
     def drop_paths(self):
         """Give the memory of the drawn paths back."""
@@ -1646,8 +1661,12 @@ class SimpleGPModel(StateSpaceModel):
         """Every drawn path through the closed loop u_i = K[i] x_i + k[i] in ONE launch (sr_gp_paths_rollout): x0 (n_s,) or
         (n_s, 1) is the start of every path, (size, n_s) one start per path; K (H, n_u, n_s), k (H, n_u).  Returns the tensor
         X_all (H, size, n_s) of the states after steps 1 .. H -- what H chained paths_step_device calls give, to rounding --
-        and with jacobians=True (X_all, A_all), A_all (H, size, n_s, n_s) = J_x + J_u K[i] per step and path."""
+        and with jacobians=True (X_all, A_all), A_all (H, size, n_s, n_s) = J_x + J_u K[i] per step and path.
+        "rbf" models only: NotImplementedError for a model with a "lin_rbf" output (chain paths_step_device, as
+        MonteCarloSafetyVerification.rollout_paths does)."""
         self._need_trained()
+        if not self._paths_fused_rollout_supported():
+            raise NotImplementedError("paths_rollout_device: the roll-out in one launch is for ARD-RBF models only")
         hd = self._handle
         n_s, n_u = hd.n_out, hd.D - hd.n_out
         if n_u < 1:
@@ -1709,8 +1728,10 @@ class SimpleGPModel(StateSpaceModel):
     def paths_rollout_diff_device(self, x0, K, k):
         """paths_rollout_device(x0, K, k) -- the same bits -- as a node of torch's autograd graph: the backward is
         paths_rollout_vjp_device at the stored states, once differentiable, with gradients for those of x0, K, k that
-        require them (not for the model or the draws)."""
+        require them (not for the model or the draws).  "rbf" models only (NotImplementedError otherwise)."""
         self._need_trained()
+        if not self._paths_fused_rollout_supported():
+            raise NotImplementedError("paths_rollout_diff_device: the reverse pass of the roll-out is for ARD-RBF models only")
         self._need_paths()
         dev = self._handle.device
         return _PathsRolloutFn.apply(self, B.as_dev(x0, dev), B.as_dev(K, dev), B.as_dev(k, dev))
