@@ -314,6 +314,35 @@ int sr_onestep_reach_vjp(sr_gp_t h, long T, const double* p, const double* q, co
                          const double* a, const double* b, const double* l_mu, const double* l_sigma, double c_safety,
                          const double* p1_bar, const double* q1_bar, double* p_bar, double* q_bar, double* kff_bar,
                          double* kfb_bar, void* stream);
+/* sr_multistep_reach_vjp: the reverse pass of sr_multistep_reach, GP included.  The forward arguments are exactly those of
+ * sr_multistep_reach (q0 == NULL: step 0 is the point branch; k_fb0 required iff q0 is given; k_fb may be NULL when H == 1);
+ * p_all T x H x n_s and q_all T x H x n_s x n_s are what it returned.  Seeds p_all_bar, q_all_bar of those shapes (either NULL =
+ * zero, the same bits; not both).  With L = sum p_all_bar . p_all + sum q_all_bar . q_all the outputs are dL/dp0 (T x n_s), dL/dq0
+ * (T x n_s x n_s), dL/dk_fb0 (T x n_u x n_s), dL/dk_ff (T x H x n_u) and dL/dk_fb (T x (H-1) x n_u x n_s; may be NULL when H == 1).
+ * q0_bar and kfb0_bar may be NULL in a point start (zero-filled where given), and are required with q0.
+ * Per trajectory, for i = H-1 .. 0: the seed of step i is (p_all_bar, q_all_bar)[i] plus the (p_bar, q_bar) step i+1 produced; the
+ * step is differentiated by the formulas of sr_onestep_reach_vjp -- the same device functions -- at its inputs (p_{i-1}, q_{i-1},
+ * k_ff_i, k_fb_{i-1}), step 0 at (p0, q0, k_fb0) or in the point branch; the GP link adds Tz^T z_bar[:n_x_in] to p_bar and
+ * z_bar[n_x_in:] to kff_bar[i].  The conventions are those of sr_onestep_reach_vjp: only the symmetric part of a q seed counts (the
+ * seed is symmetrised before the carried q_bar is added: a seed and its symmetric part give the same bits), q0_bar is exactly
+ * symmetric, the variance clip is ignored, r^2 is differentiated through its top eigenvector.
+ * Structure: trajectories in groups of max(1, chunk / H) (sr_gp_set_chunk).  Per group ONE launch forms z_i = [Tz p_{i-1}; k_ff_i]
+ * of every (trajectory, step) pair -- the centres do not depend on the sweep --, sr_gp_linearize_batch runs over all of them into
+ * the grow-only scratch of sr_onestep_reach_vjp, in passes of at most min(chunk, 256 k) queries exactly as there (the split counts
+ * depend on the model alone), the Hessian of the mean included (not read at step 0 of a point start); ONE launch finds r^2 and its eigenvectors of every
+ * (trajectory, step) pair, which depend on no seed; then ONE launch sweeps, one thread per trajectory.  No atomics, no waiting
+ * between workgroups, sums in a fixed order: the same bits on every call and for ANY chunk size.
+ * A (trajectory, step) pair whose box half-widths are not all > 0 (the ones sr_multistep_reach counts in n_bad) gets NaN as in
+ * sr_onestep_reach_vjp, and the NaN reaches every gradient of that trajectory that flows through that step -- kff_bar[t][:i+1],
+ * kfb_bar[t][:i], p0_bar[t], q0_bar[t], kfb0_bar[t]; the gradients of later steps and of other trajectories are untouched.
+ * Every kernel identifier, exact and sparse handles and the input transform are accepted.  Before any launch: SR_EINVAL NULL where
+ * required, q0 without k_fb0 / q0_bar / kfb0_bar, both seeds NULL, H < 1, T < 0; SR_ESTATE not factorized; SR_EUNSUPPORTED D > 8,
+ * n_s > 8, n_u > 4; T == 0 is a no-op.  Asynchronous on `stream`. */
+int sr_multistep_reach_vjp(sr_gp_t h, long T, int H, const double* p0, const double* q0, const double* k_fb0,
+                           const double* k_ff, const double* k_fb, const double* a, const double* b, const double* l_mu,
+                           const double* l_sigma, double c_safety, const double* p_all, const double* q_all,
+                           const double* p_all_bar, const double* q_all_bar, double* p0_bar, double* q0_bar, double* kfb0_bar,
+                           double* kff_bar, double* kfb_bar, void* stream);
 
 /* ---- Gaussian moment propagation (the CautiousMPC baseline), batched -----------------------------
  * replaces: uncertainty_propagation_casadi.one_step_taylor / multi_step_taylor_symbolic (mode 1)

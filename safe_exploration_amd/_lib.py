@@ -79,6 +79,7 @@ SIGNATURES = {
                                _P, _P]),
     "sr_ellipsoid_step_vjp": (_I, [_I, _L, _I, _I] + [_P] * 11 + [_D] + [_P] * 10),
     "sr_onestep_reach_vjp": (_I, [_H, _L] + [_P] * 8 + [_D] + [_P] * 7),
+    "sr_multistep_reach_vjp": (_I, [_H, _L, _I] + [_P] * 9 + [_D] + [_P] * 10),
     "sr_moment_step_vjp": (_I, [_I, _L, _I, _I, _I] + [_P] * 19),
     "sr_onestep_moments": (_I, [_H, _L, _I] + [_P] * 10),
     "sr_onestep_moments_vjp": (_I, [_H, _L, _I] + [_P] * 14),

@@ -1,6 +1,6 @@
 // sr_capi_reach.hip -- reachability entry points: one-step and multi-step ellipsoid propagation (mode 0) and Gaussian moment
 // propagation (modes 1 / 2) through one forward step (ell_args, reach_step) and one driver each (onestep_impl, multistep_impl);
-// the reverse pass of one step of either through one driver (onestep_vjp_impl); exact moment matching, its reverse pass and
+// the reverse pass of one step of either through one driver (onestep_vjp_impl) and of a whole mode-0 roll-out (sr_multistep_reach_vjp); exact moment matching, its reverse pass and
 // its roll-out in one launch; the stateless per-query steps (ellipsoid, moments, their reverse passes, remainder, safety distance, distance to centre, sampling);
 // and the dispatch of the persistent chain kernel (sr_chain.hip K0c) with its process-wide launch gate.
 #include "sr_handle.h"
@@ -610,6 +610,87 @@ extern "C" int sr_onestep_reach_vjp(sr_gp_t h, long T, const double* p, const do
     SR_CHECK(p1_bar || q1_bar, SR_EINVAL, "sr_onestep_reach_vjp: both seeds NULL");
     return onestep_vjp_impl(h, "sr_onestep_reach_vjp", T, 0, p, q, k_ff, k_fb, a, b, l_mu, l_sigma, c_safety, p1_bar, q1_bar,
                             nullptr, p_bar, q_bar, kff_bar, kfb_bar, stream);
+}
+
+// doubles of reach_ws per (trajectory, step) pair of sr_multistep_reach_vjp: those of one step's reverse pass, and
+// q_in, kfb_in | p_seed, q_seed | p_bar, q_bar, kff_bar, kfb_bar | eig
+static long sr_reach_rollout_vjp_ws_per_query(int n_s, int n_u, int D) {
+    return sr_reach_vjp_ws_per_query(n_s, n_u, D) + 2L * n_s + 3L * n_s * n_s + 2L * n_u * n_s + n_u + (1L + 2L * n_s + n_u);
+}
+
+// The reverse pass of sr_multistep_reach (sr_reach_rollout_vjp.hip).  Per group of max(1, chunk / H) trajectories: the inputs of all
+// their steps (one launch), sr_gp_linearize_batch over them in passes bounded as onestep_vjp_impl bounds them, then the sweep, one
+// thread per trajectory.  A thread owns its trajectory: the grouping decides nothing but the size of the scratch.
+extern "C" int sr_multistep_reach_vjp(sr_gp_t h, long T, int H, const double* p0, const double* q0, const double* k_fb0,
+                                      const double* k_ff, const double* k_fb, const double* a, const double* b,
+                                      const double* l_mu, const double* l_sigma, double c_safety, const double* p_all,
+                                      const double* q_all, const double* p_all_bar, const double* q_all_bar, double* p0_bar,
+                                      double* q0_bar, double* kfb0_bar, double* kff_bar, double* kfb_bar, void* stream) {
+    const char* who = "sr_multistep_reach_vjp";
+    SR_CHECK(h != nullptr, SR_EINVAL, "%s: NULL handle", who);
+    SR_CHECK(h->factorized, SR_ESTATE, "%s: model not factorized", who);
+    SR_CHECK(T >= 0 && H >= 1, SR_EINVAL, "%s: T=%ld H=%d", who, T, H);
+    int n_s, n_u;
+    SR_TRY(check_reach_dims(h, &n_s, &n_u));
+    if (h->D > 8) {                                   // the widths sr_gp_linearize_batch is compiled for
+        sr_set_error("%s: D=%d > 8 (the batched linearisation behind it)", who, h->D);
+        return SR_EUNSUPPORTED;
+    }
+    if (T == 0) return SR_OK;
+    SR_CHECK(p0 && k_ff && a && b && l_mu && l_sigma && p_all && q_all && p0_bar && kff_bar, SR_EINVAL, "%s: NULL argument", who);
+    SR_CHECK(H == 1 || (k_fb && kfb_bar), SR_EINVAL, "%s: k_fb and kfb_bar required for H > 1", who);
+    SR_CHECK(q0 == nullptr || (k_fb0 && q0_bar && kfb0_bar), SR_EINVAL, "%s: k_fb0, q0_bar and kfb0_bar required with q0", who);
+    SR_CHECK(p_all_bar || q_all_bar, SR_EINVAL, "%s: both seeds NULL", who);
+    hipStream_t s = (hipStream_t)stream;
+    SR_DEVICE(h->device);
+    const int D = h->D, n_xin = h->n_xin ? h->n_xin : n_s;
+    const long per = sr_reach_rollout_vjp_ws_per_query(n_s, n_u, D);
+    const long nss = (long)n_s * n_s, nus = (long)n_u * n_s, nd = (long)n_s * D, nds = (long)n_s * (n_s + n_u);
+    // a group: chunk / H trajectories and at most 2^28 doubles (2 GB) of scratch; a linearisation pass: as in onestep_vjp_impl
+    const long group = std::max(1L, std::min(h->chunk / H, ((long)1 << 28) / (per * H)));
+    const long pass = std::max(1L, std::min(h->chunk, sr_stable_pass_max(h->N, h->Np, h->n_out)));
+    const long Qw = std::min(group, T) * H;
+    SR_TRY(h->reach_ws.grow((size_t)(Qw * per), wait::stream(s)));
+    double* w = h->reach_ws.get();
+    auto take = [&](long each) { double* x = w; w += Qw * each; return x; };
+    sr_rrv_args r{};
+    sr_ellvjp_args& ea = r.e;
+    r.z = take(D);
+    double* mu = take(n_s);
+    double* var = take(n_s);
+    double* jm = take(nd);
+    double* jv = take(nd);
+    double* hm = take(nd * D);
+    ea.mu_bar = take(n_s); ea.var_bar = take(n_s); ea.jac_bar = take(nds); ea.jac_s = take(nds); ea.jz = take(nd);
+    r.q_in = take(nss); r.kfb_in = take(nus); r.p_seed = take(n_s); r.q_seed = take(nss);
+    ea.p_bar = take(n_s); ea.q_bar = take(nss); ea.kff_bar = take(n_u); ea.kfb_bar = take(nus);
+    r.eig = take(1 + 2 * n_s + n_u);
+    ea.q = r.q_in; ea.k_fb = r.kfb_in; ea.var = var; ea.jac = jm;
+    ea.a = a; ea.b = b; ea.l_mu = l_mu; ea.l_sigma = l_sigma; ea.c_safety = c_safety;
+    ea.p1_bar = r.p_seed; ea.q1_bar = r.q_seed;
+    ea.jac_mu = jm; ea.jac_var = jv; ea.hess_mu = hm; ea.Tz = h->n_xin ? h->Tz : nullptr; ea.D = D; ea.n_xin = n_xin;
+    r.H = H; r.n_s = n_s; r.n_u = n_u;
+    for (long t0 = 0; t0 < T; t0 += group) {
+        const long Tg = std::min(group, T - t0), Q = Tg * H;
+        ea.T = Tg;
+        r.p0 = p0 + t0 * n_s; r.q0 = q0 ? q0 + t0 * nss : nullptr; r.k_fb0 = q0 ? k_fb0 + t0 * nus : nullptr;
+        r.k_ff = k_ff + t0 * H * n_u; r.k_fb = k_fb ? k_fb + t0 * (H - 1) * nus : nullptr;
+        r.p_all = p_all + t0 * H * n_s; r.q_all = q_all + t0 * H * nss;
+        r.p_all_bar = p_all_bar ? p_all_bar + t0 * H * n_s : nullptr; r.q_all_bar = q_all_bar ? q_all_bar + t0 * H * nss : nullptr;
+        r.p0_bar = p0_bar + t0 * n_s; r.q0_bar = q0_bar ? q0_bar + t0 * nss : nullptr;
+        r.kfb0_bar = kfb0_bar ? kfb0_bar + t0 * nus : nullptr; r.kfb_bar = kfb_bar ? kfb_bar + t0 * (H - 1) * nus : nullptr;
+        r.kff_bar = kff_bar + t0 * H * n_u;
+        SR_TRY(sr_launch_reach_rollout_prep(r, s));
+        SR_TRY(sr_launch_reach_rollout_eig(r, s));
+        for (long q1 = 0; q1 < Q; q1 += pass) {
+            const long Qc = std::min(pass, Q - q1);
+            SR_TRY(sr_gp_linearize_batch(h, r.z + q1 * D, Qc, mu + q1 * n_s, var + q1 * n_s, jm + q1 * nd, jv + q1 * nd,
+                                         hm + q1 * nd * D, stream));
+        }
+        sr_prof_scope ps(&h->prof, SR_K_REACH_VJP, s);
+        SR_TRY(sr_launch_reach_rollout_vjp(r, s));
+    }
+    return SR_OK;
 }
 
 extern "C" int sr_onestep_moments_vjp(sr_gp_t h, long T, int mode, const double* mu_x, const double* sigma_x, const double* k_ff,

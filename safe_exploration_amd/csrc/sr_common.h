@@ -708,6 +708,22 @@ struct sr_momvjp_args {
     int mode;                         // 1 Taylor, 2 mean-equivalent
 };
 int sr_launch_moments_vjp(const sr_momvjp_args& m, int n_s, int n_u, hipStream_t s);
+// reverse pass of a roll-out of H steps in mode 0 (sr_reach_rollout_vjp.hip) for a group of e.T trajectories.  Query n = t H + i is
+// step i of trajectory t; every array of `e` is dense in n (e.q = q_in, e.k_fb = kfb_in, e.p1_bar = p_seed, e.q1_bar = q_seed),
+// the GP link fields as in sr_ellvjp_args with hess_mu always set.
+struct sr_rrv_args {
+    sr_ellvjp_args e;
+    int H, n_s, n_u;
+    // the caller's arrays, from the group's first trajectory on: q0 NULL = point start; k_fb NULL where H == 1; either seed may be NULL
+    const double* p0; const double* q0; const double* k_fb0; const double* k_ff; const double* k_fb;
+    const double* p_all; const double* q_all; const double* p_all_bar; const double* q_all_bar;
+    double* p0_bar; double* q0_bar; double* kfb0_bar; double* kff_bar; double* kfb_bar;   // q0_bar, kfb0_bar may be NULL in a point start
+    // per-query scratch: z (n_xin + n_u), q_in / q_seed (n_s^2), kfb_in (n_u n_s), p_seed (n_s), eig (1 + 2 n_s + n_u: r^2, w, v, K v)
+    double* z; double* q_in; double* kfb_in; double* p_seed; double* q_seed; double* eig;
+};
+int sr_launch_reach_rollout_prep(const sr_rrv_args& r, hipStream_t s);
+int sr_launch_reach_rollout_eig(const sr_rrv_args& r, hipStream_t s);
+int sr_launch_reach_rollout_vjp(const sr_rrv_args& r, hipStream_t s);
 int sr_launch_remainder(long T, int n_s, int n_u, const double* q, const double* k_fb,
                         const double* l_mu, const double* l_sigma, double* u_mu, double* u_sigma,
                         hipStream_t s);

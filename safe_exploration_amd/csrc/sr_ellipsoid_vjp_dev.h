@@ -270,35 +270,45 @@ __device__ __forceinline__ void sr_top_eigenpair_qb(const double* q_base, const 
     }
 }
 
-// the reverse of sr_ellipsoid_one (mode 0) for query t; writes every output of the query that is not NULL
-template <int NS, int NU>
-__device__ __forceinline__ void sr_ellipsoid_vjp_one(const sr_ellvjp_args& a, long t, double* lds, int lds_stride) {
+// doubles per query of a stored eigenpair (sr_reach_rollout_vjp.hip): r^2 | w | v | K v
+constexpr int sr_vjp_eig_doubles(int ns, int nu) { return 1 + 2 * ns + nu; }
+
+// the reverse of sr_ellipsoid_one (mode 0) for query t; writes every output of the query that is not NULL.
+// PRE_EIG: r^2 and its eigenvectors are not found here but read from eig[t] (sr_vjp_eig_doubles per query), where
+// sr_top_eigenpair_qb of the same (q, k_fb) was stored: the part of the step that depends on no seed and stands apart.
+// ts (default: t) is the index of the query in the arrays the stages hand to each other and to the next step -- p1_bar, q1_bar,
+// p_bar, q_bar, kff_bar, kfb_bar, mu_bar, var_bar, jac_bar, jac_s, jz --, which a kernel with one thread per trajectory keeps in LDS, one slot
+// per thread; t indexes the query's inputs (q, k_fb, var, jac where it is not jac_s, the GP derivatives, eig).
+template <int NS, int NU, bool PRE_EIG = false>
+__device__ __forceinline__ void sr_ellipsoid_vjp_one(const sr_ellvjp_args& a, long t, double* lds, int lds_stride,
+                                                     const double* eig = nullptr, long ts_ = -1) {
+    const long ts = ts_ < 0 ? t : ts_;
     constexpr int D = NS + NU;
     const double c = a.c_safety;
-    const double* G = a.q1_bar ? a.q1_bar + t * NS * NS : nullptr;
+    const double* G = a.q1_bar ? a.q1_bar + ts * NS * NS : nullptr;
     auto g = [&](int i, int j) { return G ? 0.5 * (G[i * NS + j] + G[j * NS + i]) : 0.0; };
     double pb[NS], vb[NS];
 #pragma unroll
-    for (int i = 0; i < NS; ++i) pb[i] = a.p1_bar ? a.p1_bar[t * NS + i] : 0.0;
+    for (int i = 0; i < NS; ++i) pb[i] = a.p1_bar ? a.p1_bar[ts * NS + i] : 0.0;
     bool bad = false;
     const double qnan = __builtin_nan("");
     // linear part and var_bar, once `bad` is known
     auto store_linear = [&]() {
 #pragma unroll
         for (int i = 0; i < NS; ++i) {
-            a.mu_bar[t * NS + i] = bad ? qnan : pb[i];
-            a.var_bar[t * NS + i] = bad ? qnan : vb[i];
+            a.mu_bar[ts * NS + i] = bad ? qnan : pb[i];
+            a.var_bar[ts * NS + i] = bad ? qnan : vb[i];
             double s = 0.0;
 #pragma unroll
             for (int k = 0; k < NS; ++k) s = fma(a.a[k * NS + i], pb[k], s);
-            a.p_bar[t * NS + i] = bad ? qnan : s;
+            a.p_bar[ts * NS + i] = bad ? qnan : s;
         }
 #pragma unroll
         for (int u = 0; u < NU; ++u) {
             double s = 0.0;
 #pragma unroll
             for (int k = 0; k < NS; ++k) s = fma(a.b[k * NU + u], pb[k], s);
-            a.kff_bar[t * NU + u] = bad ? qnan : s;
+            a.kff_bar[ts * NU + u] = bad ? qnan : s;
         }
     };
 
@@ -313,20 +323,29 @@ __device__ __forceinline__ void sr_ellipsoid_vjp_one(const sr_ellvjp_args& a, lo
         const double z = bad ? qnan : 0.0;
         if (a.jac_bar)
 #pragma unroll
-            for (int e = 0; e < NS * D; ++e) a.jac_bar[t * NS * D + e] = z;
+            for (int e = 0; e < NS * D; ++e) a.jac_bar[ts * NS * D + e] = z;
         if (a.q_bar)
 #pragma unroll
-            for (int e = 0; e < NS * NS; ++e) a.q_bar[t * NS * NS + e] = z;
+            for (int e = 0; e < NS * NS; ++e) a.q_bar[ts * NS * NS + e] = z;
         if (a.kfb_bar)
 #pragma unroll
-            for (int e = 0; e < NU * NS; ++e) a.kfb_bar[t * NU * NS + e] = z;
+            for (int e = 0; e < NU * NS; ++e) a.kfb_bar[ts * NU * NS + e] = z;
         return;
     }
 
     // ---- forward quantities -------------------------------------------------------------------------------------------
     double r2, w[NS], v[NS], kv[NU];
     sr_tmat<NS, sr_vjp_in_lds<NS>()> H(lds, lds_stride);        // V first, then H: the one n_s x n_s block of this thread
-    sr_top_eigenpair_qb<NS, NU>(a.q, a.k_fb, t, r2, w, v, kv, H);
+    if constexpr (PRE_EIG) {
+        const double* e = eig + t * sr_vjp_eig_doubles(NS, NU);
+        r2 = e[0];
+#pragma unroll
+        for (int i = 0; i < NS; ++i) { w[i] = e[1 + i]; v[i] = e[1 + NS + i]; }
+#pragma unroll
+        for (int u = 0; u < NU; ++u) kv[u] = e[1 + 2 * NS + u];
+    } else {
+        sr_top_eigenpair_qb<NS, NU>(a.q, a.k_fb, t, r2, w, v, kv, H);
+    }
     double K[NU][NS];
     const double* kg = sr_opaque(a.k_fb) + t * NU * NS;
 #pragma unroll
@@ -344,7 +363,7 @@ __device__ __forceinline__ void sr_ellipsoid_vjp_one(const sr_ellvjp_args& a, lo
 #define SR_QS(i, j) qs[(i) < (j) ? (i) : (j)][(i) < (j) ? (j) : (i)]
     const double r1 = sqrt(r2);
 
-    const double* jac = a.jac + t * NS * D;
+    const double* jac = a.jac + (a.jac == a.jac_s ? ts : t) * NS * D;
     constexpr int ROW_UNROLL = sr_vjp_in_lds<NS>() ? 1 : NS;
 #pragma unroll ROW_UNROLL
     for (int i = 0; i < NS; ++i) {
@@ -460,7 +479,7 @@ __device__ __forceinline__ void sr_ellipsoid_vjp_one(const sr_ellvjp_args& a, lo
 #pragma unroll
             for (int k = 0; k < NS; ++k) s = fma(t2[k], SR_QS(k, j), s);
             hb[j] = 2.0 * s;
-            a.jac_bar[(t * NS + i) * D + j] = bad ? qnan : hb[j];
+            a.jac_bar[(ts * NS + i) * D + j] = bad ? qnan : hb[j];
 #pragma unroll
             for (int l = 0; l < NS; ++l)
                 if (l >= j) qacc[j][l] = fma(H.get(i, j), t2[l], qacc[j][l]);
@@ -470,7 +489,7 @@ __device__ __forceinline__ void sr_ellipsoid_vjp_one(const sr_ellvjp_args& a, lo
             double s = 0.0;
 #pragma unroll
             for (int j = 0; j < NS; ++j) s = fma(hb[j], sr_vjp_in_lds<NS>() ? kq[u * NS + j] : K[u][j], s);
-            a.jac_bar[(t * NS + i) * D + NS + u] = bad ? qnan : s;
+            a.jac_bar[(ts * NS + i) * D + NS + u] = bad ? qnan : s;
             const double bm = jac[i * D + NS + u] + a.b[i * NU + u];
 #pragma unroll
             for (int j = 0; j < NS; ++j) kacc[u][j] = fma(bm, hb[j], kacc[u][j]);
@@ -483,22 +502,23 @@ __device__ __forceinline__ void sr_ellipsoid_vjp_one(const sr_ellvjp_args& a, lo
         for (int j = 0; j < NS; ++j)
             if (j >= i) {
                 const double x = bad ? qnan : qacc[i][j];
-                a.q_bar[(t * NS + i) * NS + j] = x;
-                a.q_bar[(t * NS + j) * NS + i] = x;
+                a.q_bar[(ts * NS + i) * NS + j] = x;
+                a.q_bar[(ts * NS + j) * NS + i] = x;
             }
 #pragma unroll
     for (int u = 0; u < NU; ++u)
 #pragma unroll
-        for (int j = 0; j < NS; ++j) a.kfb_bar[(t * NU + u) * NS + j] = bad ? qnan : kacc[u][j];
+        for (int j = 0; j < NS; ++j) a.kfb_bar[(ts * NU + u) * NS + j] = bad ? qnan : kacc[u][j];
 }
 
 // The GP link of query t (run-time sizes, no thread-local arrays): the state-space Jacobian the step reads, from the GP's.
 //   jac_s[a][:n_s] = jac_mu[a][:n_xin] Tz,   jac_s[a][n_s:] = jac_mu[a][n_xin:]
-__device__ __forceinline__ void sr_reach_gp_jac_one(const sr_ellvjp_args& a, long t, int n_s, int n_u) {
+__device__ __forceinline__ void sr_reach_gp_jac_one(const sr_ellvjp_args& a, long t, int n_s, int n_u, long ts_ = -1) {
+    const long ts = ts_ < 0 ? t : ts_;
     const int D = a.D, nx = a.n_xin, Ds = n_s + n_u;
     for (int o = 0; o < n_s; ++o) {
         const double* gm = a.jac_mu + (t * n_s + o) * D;
-        double* js = a.jac_s + (t * n_s + o) * Ds;
+        double* js = a.jac_s + (ts * n_s + o) * Ds;
         for (int cc = 0; cc < n_s; ++cc) {
             double s = 0.0;
             for (int i = 0; i < nx; ++i) s = fma(gm[i], a.Tz[i * n_s + cc], s);
@@ -513,16 +533,17 @@ __device__ __forceinline__ void sr_reach_gp_jac_one(const sr_ellvjp_args& a, lon
 //   jz[a][:n_xin] = jac_bar[a][:n_s] Tz^T,  jz[a][n_xin:] = jac_bar[a][n_s:];   p_bar += Tz^T z_bar[:n_xin],  kff_bar += z_bar[n_xin:]
 // The sums run in ascending order of a and d by one thread: deterministic, no atomics.  hess_mu == NULL (the host leaves it so
 // where jac_bar is zero: a point start, the mean-equivalent mode): no second-order term, neither jac_bar nor the Hessian is read.
-__device__ __forceinline__ void sr_reach_gp_vjp_one(const sr_ellvjp_args& a, long t, int n_s, int n_u) {
+__device__ __forceinline__ void sr_reach_gp_vjp_one(const sr_ellvjp_args& a, long t, int n_s, int n_u, long ts_ = -1) {
+    const long ts = ts_ < 0 ? t : ts_;
     const int D = a.D, Ds = n_s + n_u;
     const int nx = a.Tz ? a.n_xin : n_s;
-    const double* mb = a.mu_bar + t * n_s;
-    const double* vb = a.var_bar + t * n_s;
-    const double* jb = a.jac_bar + t * n_s * Ds;
+    const double* mb = a.mu_bar + ts * n_s;
+    const double* vb = a.var_bar + ts * n_s;
+    const double* jb = a.jac_bar + ts * n_s * Ds;
     const bool second = a.hess_mu != nullptr;
     const double* jz = jb;                      // identity transform: the same layout
     if (second && a.Tz) {
-        double* w = a.jz + t * n_s * D;
+        double* w = a.jz + ts * n_s * D;
         for (int o = 0; o < n_s; ++o) {
             for (int d = 0; d < nx; ++d) {
                 double s = 0.0;
@@ -545,11 +566,11 @@ __device__ __forceinline__ void sr_reach_gp_vjp_one(const sr_ellvjp_args& a, lon
                 for (int d = 0; d < D; ++d) zb = fma(jz[o * D + d], hm[d * D + e], zb);
             }
         if (e >= nx) {
-            a.kff_bar[t * n_u + (e - nx)] += zb;
+            a.kff_bar[ts * n_u + (e - nx)] += zb;
         } else if (a.Tz) {
-            for (int j = 0; j < n_s; ++j) a.p_bar[t * n_s + j] = fma(a.Tz[e * n_s + j], zb, a.p_bar[t * n_s + j]);
+            for (int j = 0; j < n_s; ++j) a.p_bar[ts * n_s + j] = fma(a.Tz[e * n_s + j], zb, a.p_bar[ts * n_s + j]);
         } else {
-            a.p_bar[t * n_s + e] += zb;
+            a.p_bar[ts * n_s + e] += zb;
         }
     }
 }

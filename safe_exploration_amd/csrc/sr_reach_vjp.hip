@@ -8,8 +8,9 @@
 // The link is told by two fields of sr_ellvjp_args: jac_mu == NULL, no link (sr_ellipsoid_step_vjp); hess_mu == NULL, no second-order
 // term (the point branch, where jac_bar is zero: the host has run sr_gp_predict_grad, not sr_gp_linearize_batch).
 // The formulas, the eigenvector route and the conventions: sr_ellipsoid_vjp_dev.h.  Chains of steps are differentiated by
-// torch autograd over this one step (gp_reachability.multistep_reachability_batch(differentiable=True)); there is no
-// persistent reverse chain.
+// torch autograd over this one step (gp_reachability.multistep_reachability_batch(differentiable=True)), or in one call by
+// sr_multistep_reach_vjp (sr_reach_rollout_vjp.hip: one linearisation pass over every step, then a sweep over the same device
+// functions).
 #include "sr_common.h"
 #include "sr_ellipsoid_vjp_dev.h"
 

@@ -14,7 +14,9 @@ Beyond the reference: the reverse pass of ONE step on the device (``ellipsoid_st
 ``onestep_reachability_vjp_batch`` / ``sr_onestep_reach_vjp``) and, on top of it, ``differentiable=True`` on the three batched
 entry points: the forward stays the plain call (the same bits), the backward is the device reverse pass, steps are chained by
 torch autograd.  Gradients reach the centres, shape matrices and controls (and mu, var, jac of ``ellipsoid_step_batch``), not
-the model.  Mode 0 here (the moment modes: uncertainty_propagation_casadi); D <= 8; no persistent reverse chain.
+the model.  Mode 0 here (the moment modes: uncertainty_propagation_casadi); D <= 8.  A whole roll-out is differentiated in one
+call by ``multistep_reachability_vjp_batch`` / ``sr_multistep_reach_vjp`` (one linearisation pass over all T*H steps, then a
+sweep); ``multistep_reachability_diff_batch`` is the autograd surface over it, its forward the plain one-launch roll-out.
 """
 import ctypes
 
@@ -394,7 +396,8 @@ def multistep_reachability_batch(p_0, gp, k_fb, k_ff, L_mu, L_sigm, q_0=None, c_
     (``gp.set_chain(False)``: a K* pass, the variance contraction and the ellipsoid kernel per step), to the bit, wherever one
     step takes that route itself: for n_s >= 3 always, for n_s <= 2 with ``gp.set_chain(False)`` around this call as well (a
     one-step call of a small model with n_s <= 2 otherwise runs posterior and step in one launch of its own and agrees with the
-    per-step route to rounding).  There is no persistent reverse chain.
+    per-step route to rounding).  The reverse pass of the whole roll-out in one call, behind the one-launch forward:
+    ``multistep_reachability_diff_batch`` (``multistep_reachability_vjp_batch``).
     """
     if not isinstance(gp, SimpleGPModel):
         raise TypeError("multistep_reachability_batch needs the HIP SimpleGPModel")
@@ -478,6 +481,105 @@ def multistep_reachability_batch(p_0, gp, k_fb, k_ff, L_mu, L_sigm, q_0=None, c_
     _raise_if_bad(n_bad)
     _raise_if_chain_failed(hd, dev, n_bad is not None)
     return B.to_numpy(p_all), B.to_numpy(q_all)
+
+
+def multistep_reachability_vjp_batch(p_0, gp, k_fb, k_ff, L_mu, L_sigm, p_all, q_all, p_all_bar=None, q_all_bar=None, q_0=None,
+                                     c_safety=1., a=None, b=None, k_fb_init=None, t_z_gp=None):
+    """Reverse pass of ``multistep_reachability_batch`` in one call (``sr_multistep_reach_vjp``): one batched linearisation at the
+    inputs of all T*H steps -- the centres p_all are known --, then a sweep over the steps, one thread per trajectory.
+
+    The forward arguments as ``multistep_reachability_batch`` takes them; p_all (T,H,n_s), q_all (T,H,n_s,n_s) are what it
+    returned; seeds p_all_bar, q_all_bar of those shapes (None = zero, not both).  Returns the gradients of
+    sum(p_all_bar * p_all) + sum(q_all_bar * q_all): (p0_bar, q0_bar, kfb_init_bar, kff_bar, kfb_bar), shaped like p_0, q_0,
+    k_fb_init, k_ff and k_fb; q0_bar and kfb_init_bar are None in a point start (q_0 None).  Only the symmetric part of q_all_bar
+    counts, q0_bar is exactly symmetric, a step the forward would count as a bound violation turns the gradients that flow
+    through it into NaN.  The same bits on every call and for any ``set_chunk``.  Models as ``linearize_device_batch`` takes
+    them (D <= 8: NotImplementedError beyond).  numpy in -> numpy out, tensors in -> tensors out."""
+    if not isinstance(gp, SimpleGPModel):
+        raise TypeError("multistep_reachability_vjp_batch needs the HIP SimpleGPModel")
+    as_t = B.is_tensor(p_0)
+    hd = gp._handle
+    gp._need_trained()
+    dev = hd.device
+    n_s, n_u = _reach_dims(hd, t_z_gp)
+    if q_0 is not None and k_fb_init is None:
+        raise ValueError("k_fb_init is required when q_0 is given")
+    if p_all_bar is None and q_all_bar is None:
+        raise ValueError("at least one of p_all_bar, q_all_bar is needed")
+    p0 = B.as_dev(p_0, dev)
+    T = p0.shape[0]
+    if p0.dim() != 2 or p0.shape[1] != n_s:
+        raise ValueError("p_0 must be (T, {})".format(n_s))
+    kff = B.as_dev(k_ff, dev)
+    if kff.dim() != 3 or kff.shape[0] != T or kff.shape[2] != n_u:
+        raise ValueError("k_ff must be (T, H, {})".format(n_u))
+    H = kff.shape[1]
+    if H < 1:
+        raise ValueError("k_ff must hold at least one step")
+    def shaped(x, shape, name):
+        try:
+            return B.as_dev(x, dev, shape)
+        except RuntimeError:
+            raise ValueError("{} must be {}".format(name, shape))
+    kfb = shaped(k_fb, (T, H - 1, n_u, n_s), "k_fb") if H > 1 else None
+    q0 = shaped(q_0, (T, n_s, n_s), "q_0")
+    kfb0 = shaped(k_fb_init, (T, n_u, n_s), "k_fb_init") if q0 is not None else None
+    pa, qa = shaped(p_all, (T, H, n_s), "p_all"), shaped(q_all, (T, H, n_s, n_s), "q_all")
+    pab, qab = shaped(p_all_bar, (T, H, n_s), "p_all_bar"), shaped(q_all_bar, (T, H, n_s, n_s), "q_all_bar")
+    a, b = _lin_model(a, b, n_s, n_u)
+    ta, tb = B.const_dev(a, dev, (n_s, n_s)), B.const_dev(b, dev, (n_s, n_u))
+    tlm, tls = B.const_dev(L_mu, dev, (n_s,)), B.const_dev(L_sigm, dev, (n_s,))
+    ell = q0 is not None
+    outs = [B.empty((T, n_s), dev), B.empty((T, n_s, n_s), dev) if ell else None, B.empty((T, n_u, n_s), dev) if ell else None,
+            B.empty((T, H, n_u), dev), B.empty((T, H - 1, n_u, n_s), dev)]
+    with _input_transform(gp, t_z_gp):
+        check(lib.sr_multistep_reach_vjp(hd.h, T, H, B.ptr(p0), B.ptr(q0), B.ptr(kfb0), B.ptr(kff), B.ptr(kfb), B.ptr(ta),
+                                         B.ptr(tb), B.ptr(tlm), B.ptr(tls), float(c_safety), B.ptr(pa), B.ptr(qa), B.ptr(pab),
+                                         B.ptr(qab), *[B.ptr(o) if o is not None and o.numel() else None for o in outs],
+                                         B.stream_ptr(dev)))
+    return tuple(outs) if as_t else tuple(None if o is None else B.to_numpy(o) for o in outs)
+
+
+class _MultistepReachFn(torch.autograd.Function):
+    """``multistep_reachability_diff_batch``: the forward is the plain one-launch ``multistep_reachability_batch``, the backward
+    ``multistep_reachability_vjp_batch`` at the saved p_all, q_all.  Seeds of outputs nobody used arrive as None."""
+
+    @staticmethod
+    def forward(ctx, gp, cfg, p_0, q_0, k_fb_init, k_ff, k_fb):
+        L_mu, L_sigm, c_safety, a, b, check_bounds, t_z_gp = cfg
+        p_all, q_all = multistep_reachability_batch(p_0, gp, k_fb, k_ff, L_mu, L_sigm, q_0, c_safety, a, b, k_fb_init,
+                                                    check_bounds, t_z_gp)
+        ctx.gp, ctx.cfg = gp, cfg
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(p_0, q_0, k_fb_init, k_ff, k_fb, p_all, q_all)
+        return p_all, q_all
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, p_all_bar, q_all_bar):
+        p_0, q_0, k_fb_init, k_ff, k_fb, p_all, q_all = ctx.saved_tensors
+        L_mu, L_sigm, c_safety, a, b, _, t_z_gp = ctx.cfg
+        if p_all_bar is None and q_all_bar is None:
+            return (None,) * 7
+        g = multistep_reachability_vjp_batch(p_0, ctx.gp, k_fb, k_ff, L_mu, L_sigm, p_all, q_all, p_all_bar, q_all_bar, q_0,
+                                             c_safety, a, b, k_fb_init, t_z_gp)
+        return None, None, g[0], g[1], g[2], g[3], (g[4].reshape(k_fb.shape) if k_fb is not None else None)
+
+
+def multistep_reachability_diff_batch(p_0, gp, k_fb, k_ff, L_mu, L_sigm, q_0=None, c_safety=1., a=None, b=None, k_fb_init=None,
+                                      check_bounds=False, t_z_gp=None):
+    """``multistep_reachability_batch`` (tensors only) with an autograd graph to p_0, q_0, k_fb_init, k_ff and k_fb: the forward IS
+    the plain call (the persistent one-launch chain where it applies; the same bits, ``check_bounds`` honoured), the backward is
+    ONE ``multistep_reachability_vjp_batch`` call at the saved p_all, q_all (once differentiable; no gradient to the model).
+    ``multistep_reachability_batch(differentiable=True)`` chains H one-step nodes instead and stays as it is."""
+    if not isinstance(gp, SimpleGPModel):
+        raise TypeError("multistep_reachability_diff_batch needs the HIP SimpleGPModel")
+    if not B.is_tensor(p_0):
+        raise TypeError("multistep_reachability_diff_batch needs tensors")
+    if q_0 is not None and k_fb_init is None:
+        raise ValueError("k_fb_init is required when q_0 is given")
+    return _MultistepReachFn.apply(gp, (L_mu, L_sigm, c_safety, a, b, check_bounds, t_z_gp), p_0, q_0,
+                                   k_fb_init if q_0 is not None else None, k_ff, k_fb if k_ff.shape[1] > 1 else None)
 
 
 def multistep_reachability(p_0, gp, k_fb, k_ff, L_mu, L_sigm, q_0=None, c_safety=1., verbose=1,
