@@ -3,9 +3,12 @@ x+ = a x + b (K_i x + k_ff,i) + g([x; u]) in the feed-forward controls and the f
 
     python examples/moment_matching_gradient.py
 
-Needs a GPU: every step's GP call is sr_gp_moment_match, and its backward is sr_gp_moment_match_vjp (the reverse pass in the
-Gaussian input's mean and covariance); the small closed-loop algebra between the calls is batched torch, differentiated by
-autograd."""
+Needs a GPU.  Two routes to the same gradient:
+  chained   every step's GP call is sr_gp_moment_match, and its backward is sr_gp_moment_match_vjp (the reverse pass in the
+            Gaussian input's mean and covariance); the small closed-loop algebra between the calls is batched torch,
+            differentiated by autograd: H autograd nodes;
+  one call  the whole roll-out is ONE autograd node (moment_matching_rollout_diff_batch): the forward is the fused roll-out
+            (sr_gp_moment_match_rollout), the backward one call of sr_gp_moment_match_rollout_vjp."""
 import os
 import sys
 
@@ -50,6 +53,12 @@ def main():
     c0 = c0.detach()
     print("expected cost of %d roll-outs over %d steps: %.6f" % (T, H, float(c0)))
     print("|d cost / d k_ff| = %.4f, |d cost / d k_fb| = %.4f" % (float(g_ff.norm()), float(g_fb.norm())))
+    # the same gradient with the whole roll-out as one autograd node
+    mu_all, sigma_all, _ = up.moment_matching_rollout_diff_batch(mu_0, gp, k_ff, k_fb, a, b, sigma_0)
+    r_ff, r_fb = torch.autograd.grad(expected_cost(mu_all, sigma_all, target, Qc), (k_ff, k_fb))
+    off = max(float((r_ff - g_ff).abs().max() / g_ff.abs().max()), float((r_fb - g_fb).abs().max() / g_fb.abs().max()))
+    print("one call for the whole roll-out: the two gradients agree to %.1e of their largest element" % off)
+    assert off < 1e-8
     # one descent step; the step length is a backtracking search from 1
     step = 1.0
     with torch.no_grad():

@@ -463,6 +463,34 @@ int sr_gp_moment_match_rollout(sr_gp_t h, long T, int H, int n_x_in, int gains_p
         const double* mu0, const double* sigma0, const double* k_ff, const double* k_fb,
         const double* a, const double* b, const double* tz, const double* inv_k,
         double* mu_all, double* sigma_all, double* cov_all, void* stream);
+/* sr_gp_moment_match_rollout_vjp: the reverse pass of that roll-out, the gradient of
+ *   L = sum mu_all_bar . mu_all + sum sigma_all_bar . sigma_all + sum cov_all_bar . cov_all      (cov the unclipped closed form)
+ * in mu0, sigma0, k_ff and k_fb; a, b and the model get no derivative.  The forward inputs are those of
+ * sr_gp_moment_match_rollout (the same shapes, the same gains_per_traj reading of k_ff / k_fb, tz NULL = identity).  mu_all
+ * T x H x n_s and sigma_all T x H x n_s x n_s are what a forward returned -- the fused call or H rounds of sr_gp_moment_match,
+ * which agree to rounding --: step i is differentiated at the stored (mu_{i-1}, Sigma_{i-1}), step 0 at (mu0, sigma0) or in the
+ * point branch when sigma0 is NULL.  Seeds mu_all_bar, sigma_all_bar, cov_all_bar shaped like the three forward outputs; any of
+ * them may be NULL (= zero, the same bits as a zero array), not all three; only the symmetric parts of the two matrix seeds
+ * count.  Outputs: mu0_bar T x n_s; sigma0_bar T x n_s x n_s, exactly symmetric (required iff sigma0 is given, else unread);
+ * kff_bar T x H x n_u; kfb_bar T x (H - 1) x n_u x n_s (may be NULL when H == 1).  The two gain gradients are ALWAYS per
+ * trajectory, also with gains_per_traj == 0: a shared policy's gradient is their sum over T.
+ * Trajectories go in groups of max(1, min(chunk, what the launch grid takes) / H), chunk from sr_gp_set_chunk.  Per group the
+ * records of sr_gp_moment_match_vjp, the GP's mean and V and the O(N^2) sums of its pair kernel are computed ONCE for all
+ * (trajectory, step) pairs -- nothing of that reads the seeds --; then, for i = H-1 .. 0, four small launches carry the adjoint
+ * through step i.  No atomics: the same bits on every call, for any chunk size and whatever other trajectories are in the
+ * batch.  Scratch: grow-only, the handle's, freed by sr_gp_release_scratch.  Cost: about H calls of sr_gp_moment_match_vjp on T
+ * queries in exp evaluations, in 5 + 4 H launches per group.  Asynchronous on `stream`.
+ * Domain: that of sr_gp_moment_match_vjp (ARD-RBF handles, exact or sparse, any N, D <= 12), not that of the fused forward.
+ * Errors, before any launch: SR_EINVAL NULL where required, sigma0 without sigma0_bar, all seeds NULL, T < 0, H < 1,
+ * gains_per_traj outside {0, 1}, n_x_in outside 1 .. D - 1, tz NULL with n_x_in != n_s; SR_ESTATE not factorized;
+ * SR_EUNSUPPORTED any general-family handle (the reverse pass is for ARD-RBF models only), D > 12, n_s > 12 (the sweep kernel
+ * keeps its n_s x n_s matrices in LDS at that size), H beyond the launch grid.  T == 0 is a no-op. */
+int sr_gp_moment_match_rollout_vjp(sr_gp_t h, long T, int H, int n_x_in, int gains_per_traj,
+        const double* mu0, const double* sigma0, const double* k_ff, const double* k_fb,
+        const double* a, const double* b, const double* tz, const double* inv_k,
+        const double* mu_all, const double* sigma_all,
+        const double* mu_all_bar, const double* sigma_all_bar, const double* cov_all_bar,
+        double* mu0_bar, double* sigma0_bar, double* kff_bar, double* kfb_bar, void* stream);
 
 /* replaces: utils.compute_remainder_overapproximations  utils.py:108-144 (batched)
  * q T x n_s x n_s, k_fb T x n_u x n_s -> u_mu T x n_s, u_sigma T x n_s */

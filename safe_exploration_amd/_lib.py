@@ -74,6 +74,7 @@ SIGNATURES = {
     "sr_gp_moment_match": (_I, [_H, _P, _P, _L, _P, _P, _P, _P, _P]),
     "sr_gp_moment_match_vjp": (_I, [_H, _P, _P, _L, _P, _P, _P, _P, _P, _P, _P]),
     "sr_gp_moment_match_rollout": (_I, [_H, _L, _I, _I, _I] + [_P] * 12),
+    "sr_gp_moment_match_rollout_vjp": (_I, [_H, _L, _I, _I, _I] + [_P] * 18),
     "sr_moment_step": (_I, [_I, _L, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "sr_ellipsoid_step": (_I, [_I, _L, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _D, _P, _P,
                                _P, _P]),

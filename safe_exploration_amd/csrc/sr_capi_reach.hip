@@ -472,6 +472,65 @@ extern "C" int sr_gp_moment_match_rollout(sr_gp_t h, long T, int H, int n_x_in, 
     return SR_OK;
 }
 
+// The reverse pass of that roll-out (sr_moment_match_rollout_vjp.hip) at the states a forward stored.  Its domain is that of
+// sr_gp_moment_match_vjp (any N), not of the fused forward.  Every refusal comes before the first launch.  Trajectories go in
+// groups of max(1, min(chunk, sr_mmg_max_queries) / H): a trajectory's results depend on nothing but its own rows, so the
+// group size decides the size of the scratch and how full the one-off pass runs, not a bit of the results.
+extern "C" int sr_gp_moment_match_rollout_vjp(sr_gp_t h, long T, int H, int n_x_in, int gains_per_traj, const double* mu0,
+                                              const double* sigma0, const double* k_ff, const double* k_fb, const double* a,
+                                              const double* b, const double* tz, const double* inv_k, const double* mu_all,
+                                              const double* sigma_all, const double* mu_all_bar, const double* sigma_all_bar,
+                                              const double* cov_all_bar, double* mu0_bar, double* sigma0_bar, double* kff_bar,
+                                              double* kfb_bar, void* stream) {
+    const char* who = "sr_gp_moment_match_rollout_vjp";
+    SR_CHECK(h != nullptr, SR_EINVAL, "%s: NULL handle", who);
+    SR_CHECK(h->factorized, SR_ESTATE, "%s: model not factorized", who);
+    SR_CHECK(!h->general, SR_EUNSUPPORTED, "%s: the reverse pass is for ARD-RBF models only (data set with sr_gp_set_data)", who);
+    SR_CHECK(h->D <= SR_MAX_D, SR_EUNSUPPORTED, "%s: D=%d > %d", who, h->D, SR_MAX_D);
+    SR_CHECK(h->n_out <= SR_MMRV_MAX_NS, SR_EUNSUPPORTED, "%s: n_s=%d > %d (the sweep kernel's matrices in LDS)", who, h->n_out,
+             SR_MMRV_MAX_NS);
+    SR_CHECK(T >= 0 && H >= 1 && (gains_per_traj == 0 || gains_per_traj == 1), SR_EINVAL, "%s: T=%ld H=%d gains_per_traj=%d",
+             who, T, H, gains_per_traj);
+    SR_CHECK(n_x_in >= 1 && n_x_in <= h->D - 1, SR_EINVAL, "%s: n_x_in=%d outside 1 .. D - 1 (D=%d)", who, n_x_in, h->D);
+    SR_CHECK(tz != nullptr || n_x_in == h->n_out, SR_EINVAL, "%s: tz NULL needs n_x_in == n_out (%d, %d)", who, n_x_in,
+             h->n_out);
+    SR_CHECK(H <= sr_mmg_max_queries(h->N, h->n_out), SR_EUNSUPPORTED, "%s: H=%d steps of N=%d, n_out=%d outside the launch grid",
+             who, H, h->N, h->n_out);
+    if (T == 0) return SR_OK;
+    SR_CHECK(mu0 && k_ff && a && b && inv_k && mu_all && sigma_all && mu0_bar && kff_bar && (H == 1 || (k_fb && kfb_bar)),
+             SR_EINVAL, "%s: NULL argument", who);
+    SR_CHECK(sigma0 == nullptr || sigma0_bar != nullptr, SR_EINVAL, "%s: sigma0 without sigma0_bar", who);
+    SR_CHECK(mu_all_bar || sigma_all_bar || cov_all_bar, SR_EINVAL, "%s: all seeds NULL", who);
+    hipStream_t s = (hipStream_t)stream;
+    SR_DEVICE(h->device);
+    const long per = sr_mmrv_ws_per_traj(h->N, h->D, h->n_out, H);
+    const long queries = std::max(1L, std::min(h->chunk, sr_mmg_max_queries(h->N, h->n_out)));
+    const long group = std::max(1L, std::min(queries / H, ((long)1 << 28) / per));
+    SR_TRY(h->mm_ws.grow((size_t)(std::min(group, T) * per), wait::stream(s)));
+    const long n = h->n_out, n_u = h->D - n_x_in;
+    sr_mmrv_args r{};
+    r.Z = h->Z; r.alpha = h->alpha; r.ls = h->ls; r.sf2 = h->sf2; r.inv_k = inv_k; r.a = a; r.b = b; r.tz = tz;
+    r.N = h->N; r.Np = h->Np; r.D = h->D; r.n_s = h->n_out; r.n_x_in = n_x_in; r.H = H; r.gains_per_traj = gains_per_traj;
+    for (long t0 = 0; t0 < T; t0 += group) {
+        r.Tg = std::min(group, T - t0);
+        r.mu0 = mu0 + t0 * n;
+        r.sigma0 = sigma0 ? sigma0 + t0 * n * n : nullptr;
+        r.k_ff = k_ff + (gains_per_traj ? t0 * H * n_u : 0);
+        r.k_fb = k_fb ? k_fb + (gains_per_traj ? t0 * (H - 1) * n_u * n : 0) : nullptr;
+        r.mu_all = mu_all + t0 * H * n;
+        r.sigma_all = sigma_all + t0 * H * n * n;
+        r.mu_all_bar = mu_all_bar ? mu_all_bar + t0 * H * n : nullptr;
+        r.sigma_all_bar = sigma_all_bar ? sigma_all_bar + t0 * H * n * n : nullptr;
+        r.cov_all_bar = cov_all_bar ? cov_all_bar + t0 * H * n * n : nullptr;
+        r.mu0_bar = mu0_bar + t0 * n;
+        r.sigma0_bar = sigma0 ? sigma0_bar + t0 * n * n : nullptr;
+        r.kff_bar = kff_bar + t0 * H * n_u;
+        r.kfb_bar = H > 1 ? kfb_bar + t0 * (H - 1) * n_u * n : nullptr;
+        SR_TRY(sr_launch_moment_match_rollout_vjp(r, h->mm_ws.get(), s));
+    }
+    return SR_OK;
+}
+
 extern "C" int sr_moment_step(int device, long T, int n_s, int n_u, int mode, const double* mu_x,
                               const double* sigma_x, const double* k_ff, const double* k_fb, const double* mu_g,
                               const double* var_g, const double* jac_g, const double* a, const double* b,

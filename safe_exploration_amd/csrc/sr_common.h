@@ -192,6 +192,40 @@ int sr_launch_moment_match_vjp(const double* Z, const double* alpha, const doubl
                                int D, int n_out, const double* m, const double* S, long T, const double* inv_k,
                                const double* mu_bar, const double* cov_bar, const double* V_bar, double* m_bar,
                                double* S_bar, double* ws, hipStream_t s);
+// its two halves on their own (the same kernels, the same sums): everything that does not read the seeds -- the D x D records,
+// mu, V and the O(N^2) sums of the pair kernel -- once for Tq <= sr_mmg_max_queries queries into ws (Tq x sr_mmg_ws_per_query
+// doubles); then the seeds of the queries q0 .. q0 + T of that block (m: all Tq rows; seeds and results: the T rows of the slice)
+int sr_launch_moment_match_vjp_records(const double* Z, const double* alpha, const double* ls, const double* sf2, int N,
+                                       int Np, int D, int n_out, const double* m, const double* S, long Tq,
+                                       const double* inv_k, double* ws, hipStream_t s);
+int sr_launch_moment_match_vjp_seeded(const double* Z, const double* alpha, const double* ls, const double* sf2, int N,
+                                      int Np, int D, int n_out, const double* m, long q0, long T, long Tq,
+                                      const double* mu_bar, const double* cov_bar, const double* V_bar, double* m_bar,
+                                      double* S_bar, double* ws, hipStream_t s);
+double* sr_mmg_ws_mu(double* ws, long Tq, int D, int n_out);     // mu (Tq x n_out) and V (Tq x n_out x D) of the records half
+double* sr_mmg_ws_v(double* ws, long Tq, int D, int n_out);
+// the reverse pass of the closed-loop roll-out (sr_moment_match_rollout_vjp.hip): one group of Tg trajectories through H steps,
+// Tg H <= sr_mmg_max_queries; ws: Tg x sr_mmrv_ws_per_traj doubles.  The pointers of the group's own rows; the scratch
+// pointers (V .. carry_sig) are set by the launch.
+struct sr_mmrv_args {
+    const double *Z, *alpha, *ls, *sf2, *inv_k;      // the model as the handle holds it; n_s x N x N
+    const double *mu0, *sigma0;                      // Tg x n_s; Tg x n_s x n_s | NULL (points)
+    const double *k_ff, *k_fb;                       // [Tg x] H x n_u; [Tg x] (H - 1) x n_u x n_s | NULL (H == 1)
+    const double *a, *b, *tz;                        // n_s x n_s, n_s x n_u, n_x_in x n_s | NULL (identity)
+    const double *mu_all, *sigma_all;                // Tg x H x n_s, Tg x H x n_s x n_s: what the forward stored
+    const double *mu_all_bar, *sigma_all_bar, *cov_all_bar;      // the seeds, shaped like the forward's outputs; NULL = zero
+    double *mu0_bar, *sigma0_bar, *kff_bar, *kfb_bar;            // Tg x n_s, Tg x n_s x n_s | NULL, Tg x H x n_u, Tg x (H-1) x n_u x n_s | NULL
+    const double* V;                                 // Q x n_s x D of the one-off pass, Q = H Tg queries, step-major
+    double *m_z, *S_z;                               // Q x D, Q x D x D: the GP's inputs
+    double *mu_bar, *cov_bar, *V_bar;                // Tg x n_s, Tg x n_s x n_s, Tg x n_s x D: the GP's seeds of one step
+    double *mz_bar, *Sz_bar;                         // Tg x D, Tg x D x D: what the GP's reverse pass returns for them
+    double *carry_mu, *carry_sig;                    // Tg x n_s, Tg x n_s x n_s: (mu_bar, Sigma_bar) handed to the step before
+    int N, Np, D, n_s, n_x_in, H, gains_per_traj;
+    long Tg;
+};
+#define SR_MMRV_MAX_NS 12                            // the sweep kernel keeps its n_s x n_s matrices in LDS at this size
+long sr_mmrv_ws_per_traj(int N, int D, int n_s, int H);
+int sr_launch_moment_match_rollout_vjp(sr_mmrv_args r, double* ws, hipStream_t s);
 // the same for the general family with the RBF radial part on every output (sr_moment_match_gen.hip; kp n_out x SR_KP(D)):
 // once per call the query-independent block `call` (sr_mmx_call_ws doubles), then chunks of T <= sr_mmx_max_queries queries
 // with ws: T x sr_mmx_ws_per_query doubles

@@ -144,6 +144,8 @@ struct sr_gp {
     // contribution records and the row tiles' sums (sr_mmg_ws_per_query doubles each); a general-family handle: the per-call
     // block (sr_mmx_call_ws doubles) in front of the chunk's records (sr_mmx_ws_per_query doubles per query)
     // sr_gp_moment_match_rollout: one step's records per trajectory of a chunk (sr_mmr_ws_per_traj doubles each)
+    // sr_gp_moment_match_rollout_vjp: per trajectory of a group the reverse pass's scratch of its H queries, their inputs, one
+    // step's seeds and results, and the carried adjoint (sr_mmrv_ws_per_traj doubles each)
     srh::scratch<double> mm_ws;
     // sr_onestep_reach_vjp, sr_onestep_moments_vjp: per query of a chunk z, the outputs of sr_gp_linearize_batch at z, the seeds on (mu, var, jac) and the
     // two transformed Jacobians (sr_reach_vjp_ws_per_query doubles each)

@@ -33,6 +33,9 @@ struct sr_mm_args {
     double* ws;                              // [mean records | pair records | partial sums] of this chunk
     int N, Np, D, n_out, npairs, nit;
     long T;
+    // the seed-dependent kernels of the reverse pass (KG1, KG3) may run on a slice of a larger record block: queries
+    // q0 .. q0 + T of the Tq whose records ws holds (every other pointer is then the slice's own).  Elsewhere q0 = 0, Tq = T.
+    long q0, Tq;
 };
 
 __host__ __device__ static inline long mm_mean_rec(int D) { return 1 + (long)D * D; }       // [c0, W (D x D)]
@@ -363,7 +366,7 @@ int sr_launch_moment_match(const double* Z, const double* alpha, const double* l
     sr_mm_args a;
     a.Z = Z; a.alpha = alpha; a.ls = ls; a.sf2 = sf2; a.m = m; a.S = S; a.inv_k = inv_k; a.mu = mu; a.cov = cov; a.V = V;
     a.ws = ws; a.N = N; a.Np = Np; a.D = D; a.n_out = n_out; a.npairs = n_out * (n_out + 1) / 2; a.nit = mm_nit(N);
-    a.T = T;
+    a.T = T; a.q0 = 0; a.Tq = T;
     SR_CHECK(a.npairs < 65536 && a.nit < 65536 && T <= sr_mm_max_queries(N, n_out), SR_EUNSUPPORTED,
              "moment_match: n_out=%d N=%d T=%ld outside the launch grid", n_out, N, T);
     return sr_pick_le<4, 8, 12>("moment_match", D, [&](auto dt) { return mm_launch<decltype(dt)::value>(a, s); });
@@ -436,7 +439,7 @@ __global__ __launch_bounds__(256) void sr_mmg_mean_kernel(sr_mmg_args g) {
     const sr_mm_args& a = g.f;
     const int D = a.D, n = a.n_out, tid = threadIdx.x, o = blockIdx.y, off = a.Np - a.N;
     const long t = blockIdx.x;
-    const double* rec = a.ws + (t * n + o) * mm_mean_rec(D);
+    const double* rec = a.ws + ((a.q0 + t) * n + o) * mm_mean_rec(D);
     const double c0 = rec[0];
     mm_load_mat<DT>(W, rec + 1, D);
     if (tid < DT) mq[tid] = tid < D ? a.m[t * D + tid] : 0.0;
@@ -689,7 +692,7 @@ __global__ __launch_bounds__(256) void sr_mmg_pairfin_kernel(sr_mmg_args g) {
         for (int it = 0; it < a.nit; ++it) s += pp[(long)it * NS];
         stc[tid] = s;
     }
-    const double* P = a.ws + a.T * n * mm_mean_rec(D) + (t * a.npairs + p) * mm_pair_rec(D) + 2;
+    const double* P = a.ws + a.Tq * n * mm_mean_rec(D) + ((a.q0 + t) * a.npairs + p) * mm_pair_rec(D) + 2;
     if (tid < D * D) {
         const int i = tid / D, j = tid % D;
         const double xi = a.ls[oa * D + i], yi = a.ls[ob * D + i], xj = a.ls[oa * D + j], yj = a.ls[ob * D + j];
@@ -761,18 +764,61 @@ __global__ __launch_bounds__(256) void sr_mmg_final_kernel(sr_mmg_args g) {
     }
 }
 
+// the seed-independent half: KM0, KM1 (mu and V into the scratch) and KG2 (the tiles' sums into part) over all a.T queries
 template <int DT>
-static int mmg_launch(const sr_mmg_args& g, hipStream_t s) {
+static int mmg_launch_records(const sr_mmg_args& g, hipStream_t s) {
     const sr_mm_args& a = g.f;
     const long nprep = a.T * (a.n_out + a.npairs);
     constexpr int BT = mm_prep_bt<DT>::value;
     hipLaunchKernelGGL((sr_mm_prep_kernel<DT>), dim3((unsigned)((nprep + BT - 1) / BT)), dim3(BT), 0, s, a);
     hipLaunchKernelGGL((sr_mm_mean_kernel<DT>), dim3((unsigned)a.T, a.n_out), dim3(256), 0, s, a);
-    hipLaunchKernelGGL((sr_mmg_mean_kernel<DT>), dim3((unsigned)a.T, a.n_out), dim3(256), 0, s, g);
     hipLaunchKernelGGL((sr_mmg_pair_kernel<DT>), dim3((unsigned)a.T, a.nit, a.n_out * a.n_out), dim3(256), 0, s, g);
+    SR_HIP(hipGetLastError());
+    return SR_OK;
+}
+
+// the seed-dependent half: KG1, KG3, KG4 on the a.T queries from a.q0 on (nothing of size N^2)
+template <int DT>
+static int mmg_launch_seeded(const sr_mmg_args& g, hipStream_t s) {
+    const sr_mm_args& a = g.f;
+    hipLaunchKernelGGL((sr_mmg_mean_kernel<DT>), dim3((unsigned)a.T, a.n_out), dim3(256), 0, s, g);
     hipLaunchKernelGGL(sr_mmg_pairfin_kernel, dim3((unsigned)a.T, a.npairs), dim3(256), 0, s, g);
     hipLaunchKernelGGL(sr_mmg_final_kernel, dim3((unsigned)((a.T * mmg_crec(a.D) + 255) / 256)), dim3(256), 0, s, g);
     SR_HIP(hipGetLastError());
+    return SR_OK;
+}
+
+// the arguments of both halves for a block of Tq queries whose scratch is ws (Tq x sr_mmg_ws_per_query doubles:
+// [records | mu | V | contribution records | part]); then the slice q0 .. q0 + T of it for the seed-dependent half
+static sr_mmg_args mmg_block(const double* Z, const double* alpha, const double* ls, const double* sf2, int N, int Np, int D,
+                             int n_out, const double* m, const double* S, long Tq, const double* inv_k, double* ws) {
+    sr_mmg_args g;
+    sr_mm_args& a = g.f;
+    a.Z = Z; a.alpha = alpha; a.ls = ls; a.sf2 = sf2; a.m = m; a.S = S; a.inv_k = inv_k; a.cov = nullptr;
+    a.N = N; a.Np = Np; a.D = D; a.n_out = n_out; a.npairs = n_out * (n_out + 1) / 2; a.nit = mm_nit(N);
+    a.T = Tq; a.q0 = 0; a.Tq = Tq;
+    a.ws = ws;
+    a.mu = ws + Tq * mmg_fwd_recs(D, n_out);
+    a.V = a.mu + Tq * n_out;
+    g.contrib = a.V + Tq * n_out * D;
+    g.part = g.contrib + Tq * (n_out + a.npairs) * mmg_crec(D);
+    g.mu_bar = g.cov_bar = g.V_bar = nullptr; g.m_bar = g.S_bar = nullptr;
+    return g;
+}
+static void mmg_slice(sr_mmg_args& g, long q0, long T) {
+    sr_mm_args& a = g.f;
+    const long n = a.n_out, D = a.D;
+    a.q0 = q0; a.T = T;
+    a.m += q0 * D;
+    if (a.S) a.S += q0 * D * D;
+    a.mu += q0 * n;
+    a.V += q0 * n * D;
+    g.contrib += q0 * (n + a.npairs) * mmg_crec(a.D);
+    g.part += q0 * n * n * a.nit * mmg_nstat(a.D);
+}
+static int mmg_check_grid(const char* who, int N, int n_out, long T) {
+    SR_CHECK(n_out * n_out < 65536 && mm_nit(N) < 65536 && T <= sr_mmg_max_queries(N, n_out), SR_EUNSUPPORTED,
+             "%s: n_out=%d N=%d T=%ld outside the launch grid", who, n_out, N, T);
     return SR_OK;
 }
 
@@ -781,18 +827,32 @@ int sr_launch_moment_match_vjp(const double* Z, const double* alpha, const doubl
                                int D, int n_out, const double* m, const double* S, long T, const double* inv_k,
                                const double* mu_bar, const double* cov_bar, const double* V_bar, double* m_bar,
                                double* S_bar, double* ws, hipStream_t s) {
-    sr_mmg_args g;
-    sr_mm_args& a = g.f;
-    a.Z = Z; a.alpha = alpha; a.ls = ls; a.sf2 = sf2; a.m = m; a.S = S; a.inv_k = inv_k; a.cov = nullptr;
-    a.N = N; a.Np = Np; a.D = D; a.n_out = n_out; a.npairs = n_out * (n_out + 1) / 2; a.nit = mm_nit(N);
-    a.T = T;
-    a.ws = ws;
-    a.mu = ws + T * mmg_fwd_recs(D, n_out);
-    a.V = a.mu + T * n_out;
-    g.contrib = a.V + T * n_out * D;
-    g.part = g.contrib + T * (n_out + a.npairs) * mmg_crec(D);
+    sr_mmg_args g = mmg_block(Z, alpha, ls, sf2, N, Np, D, n_out, m, S, T, inv_k, ws);
     g.mu_bar = mu_bar; g.cov_bar = cov_bar; g.V_bar = V_bar; g.m_bar = m_bar; g.S_bar = S_bar;
-    SR_CHECK(n_out * n_out < 65536 && a.nit < 65536 && T <= sr_mmg_max_queries(N, n_out), SR_EUNSUPPORTED,
-             "moment_match_vjp: n_out=%d N=%d T=%ld outside the launch grid", n_out, N, T);
-    return sr_pick_le<4, 8, 12>("moment_match_vjp", D, [&](auto dt) { return mmg_launch<decltype(dt)::value>(g, s); });
+    SR_TRY(mmg_check_grid("moment_match_vjp", N, n_out, T));
+    const int rc = sr_pick_le<4, 8, 12>("moment_match_vjp", D, [&](auto dt) { return mmg_launch_records<decltype(dt)::value>(g, s); });
+    if (rc != SR_OK) return rc;
+    return sr_pick_le<4, 8, 12>("moment_match_vjp", D, [&](auto dt) { return mmg_launch_seeded<decltype(dt)::value>(g, s); });
 }
+
+// The two halves on their own (sr_moment_match_rollout_vjp.hip): the records, mu, V and part of Tq queries once, ...
+int sr_launch_moment_match_vjp_records(const double* Z, const double* alpha, const double* ls, const double* sf2, int N,
+                                       int Np, int D, int n_out, const double* m, const double* S, long Tq,
+                                       const double* inv_k, double* ws, hipStream_t s) {
+    sr_mmg_args g = mmg_block(Z, alpha, ls, sf2, N, Np, D, n_out, m, S, Tq, inv_k, ws);
+    SR_TRY(mmg_check_grid("moment_match_vjp", N, n_out, Tq));
+    return sr_pick_le<4, 8, 12>("moment_match_vjp", D, [&](auto dt) { return mmg_launch_records<decltype(dt)::value>(g, s); });
+}
+// ... then, as often as wanted, the seeds of the queries q0 .. q0 + T (seeds and results are the slice's own arrays, T rows)
+int sr_launch_moment_match_vjp_seeded(const double* Z, const double* alpha, const double* ls, const double* sf2, int N,
+                                      int Np, int D, int n_out, const double* m, long q0, long T, long Tq,
+                                      const double* mu_bar, const double* cov_bar, const double* V_bar, double* m_bar,
+                                      double* S_bar, double* ws, hipStream_t s) {
+    sr_mmg_args g = mmg_block(Z, alpha, ls, sf2, N, Np, D, n_out, m, nullptr, Tq, nullptr, ws);
+    mmg_slice(g, q0, T);
+    g.mu_bar = mu_bar; g.cov_bar = cov_bar; g.V_bar = V_bar; g.m_bar = m_bar; g.S_bar = S_bar;
+    return sr_pick_le<4, 8, 12>("moment_match_vjp", D, [&](auto dt) { return mmg_launch_seeded<decltype(dt)::value>(g, s); });
+}
+// where mu (Tq x n_out) and V (Tq x n_out x D) of the records half lie in ws
+double* sr_mmg_ws_mu(double* ws, long Tq, int D, int n_out) { return ws + Tq * mmg_fwd_recs(D, n_out); }
+double* sr_mmg_ws_v(double* ws, long Tq, int D, int n_out) { return sr_mmg_ws_mu(ws, Tq, D, n_out) + Tq * n_out; }

@@ -1026,6 +1026,62 @@ class SimpleGPModel(StateSpaceModel):
                                              B.ptr(cov_all), B.stream_ptr(dev)))
         return mu_all, sigma_all, cov_all
 
+    def moment_match_rollout_vjp_device(self, mu0, k_ff, k_fb, a, b, mu_all, sigma_all, mu_all_bar=None, sigma_all_bar=None,
+                                        cov_all_bar=None, sigma0=None, a_gp_inp_x=None):
+        """Reverse pass of the moment-matching roll-out in one call (``sr_gp_moment_match_rollout_vjp``): the gradient of
+        sum(mu_all_bar * mu_all) + sum(sigma_all_bar * sigma_all) + sum(cov_all_bar * cov_all) in mu0, sigma0, k_ff and k_fb.
+        The forward arguments are those of ``moment_match_rollout_device``; mu_all (T, H, n_s) and sigma_all (T, H, n_s, n_s) are
+        what a forward returned (the fused call or ``moment_matching_batch``); the seeds are shaped like the three forward
+        outputs, None = zero, not all three.  Returns (mu0_bar (T, n_s), sigma0_bar (T, n_s, n_s) exactly symmetric | None
+        without sigma0, kff_bar, kfb_bar | None when H == 1), the gain gradients shaped like k_ff and k_fb: per trajectory, or
+        summed over T for a shared policy (2-D k_ff).  The domain of ``moment_match_vjp_device``: ARD-RBF models, exact or
+        sparse, of ANY size (not only those of the fused forward), D <= 12, n_s <= 12; NotImplementedError for any other kernel
+        before anything is prepared on the device.  The same bits on every call and for any chunk size.  Asynchronous."""
+        self._need_trained()
+        if any(kt != "rbf" for kt in self.kern_types):
+            raise NotImplementedError("moment matching: the reverse pass is for ARD-RBF models only")
+        hd = self._handle
+        n_s, dev = hd.n_out, hd.device
+        tz = None if a_gp_inp_x is None else B.as_dev(a_gp_inp_x, dev)
+        if tz is not None and (tz.dim() != 2 or tz.shape[1] != n_s or not 1 <= tz.shape[0] <= hd.D - 1):
+            raise ValueError("a_gp_inp_x must be (n_x_in, {}) with 1 <= n_x_in <= {}".format(n_s, hd.D - 1))
+        n_x_in = n_s if tz is None else tz.shape[0]
+        n_u = hd.D - n_x_in
+        if n_u < 1:
+            raise ValueError("the closed loop needs D = n_x_in + n_u with n_u >= 1")
+        mu = B.as_dev(mu0, dev)
+        if mu.dim() != 2 or mu.shape[1] != n_s:
+            raise ValueError("mu0 must be (T, {})".format(n_s))
+        T = mu.shape[0]
+        kff = B.as_dev(k_ff, dev)
+        if kff.dim() not in (2, 3) or kff.shape[-1] != n_u or (kff.dim() == 3 and kff.shape[0] != T):
+            raise ValueError("k_ff must be (H, {0}) or (T, H, {0})".format(n_u))
+        per_traj = int(kff.dim() == 3)
+        H = kff.shape[-2]
+        if H < 1:
+            raise ValueError("k_ff needs H >= 1 steps")
+        kfb = B.as_dev(k_fb, dev, ((T,) if per_traj else ()) + (H - 1, n_u, n_s)) if H > 1 else None
+        sig = B.as_dev(sigma0, dev, (T, n_s, n_s)) if sigma0 is not None else None
+        ta, tb = B.as_dev(a, dev, (n_s, n_s)), B.as_dev(b, dev, (n_s, n_u))
+        tmu, tsig = B.as_dev(mu_all, dev, (T, H, n_s)), B.as_dev(sigma_all, dev, (T, H, n_s, n_s))
+        seeds = [None if x is None else B.as_dev(x, dev, shp)
+                 for x, shp in ((mu_all_bar, (T, H, n_s)), (sigma_all_bar, (T, H, n_s, n_s)), (cov_all_bar, (T, H, n_s, n_s)))]
+        if all(x is None for x in seeds):
+            raise ValueError("at least one of mu_all_bar, sigma_all_bar, cov_all_bar is required")
+        kinv = self.inv_K_device()
+        mu0_bar = B.empty((T, n_s), dev)
+        sigma0_bar = B.empty((T, n_s, n_s), dev) if sig is not None else None
+        kff_bar = B.empty((T, H, n_u), dev)
+        kfb_bar = B.empty((T, H - 1, n_u, n_s), dev) if H > 1 else None
+        check(lib.sr_gp_moment_match_rollout_vjp(hd.h, T, H, n_x_in, per_traj, B.ptr(mu), B.ptr(sig), B.ptr(kff), B.ptr(kfb),
+                                                 B.ptr(ta), B.ptr(tb), B.ptr(tz), B.ptr(kinv), B.ptr(tmu), B.ptr(tsig),
+                                                 B.ptr(seeds[0]), B.ptr(seeds[1]), B.ptr(seeds[2]), B.ptr(mu0_bar),
+                                                 B.ptr(sigma0_bar), B.ptr(kff_bar), B.ptr(kfb_bar), B.stream_ptr(dev)))
+        if not per_traj:                               # one policy for all: its gradient is the sum over the trajectories
+            kff_bar = kff_bar.sum(dim=0)
+            kfb_bar = None if kfb_bar is None else kfb_bar.sum(dim=0)
+        return mu0_bar, sigma0_bar, kff_bar, kfb_bar
+
     def moment_match_vjp_device(self, m, S, mu_bar=None, cov_bar=None, V_bar=None):
         """Reverse pass of ``moment_match_device`` (``sr_gp_moment_match_vjp``): for seeds mu_bar (T, n), cov_bar (T, n, n),
         V_bar (T, n, D) (None = zero) the derivatives m_bar (T, D) and S_bar (T, D, D) of

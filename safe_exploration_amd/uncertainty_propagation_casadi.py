@@ -10,7 +10,8 @@ The input transform ``a_gp_inp_x`` of the reference (the GP sees ``a_gp_inp_x @ 
 the state Jacobian is chain-ruled through the constant matrix.
 
 Beyond the reference: EXACT moment matching (``MOMENT_MATCHING``; ``one_step_moment_matching``,
-``multi_step_moment_matching``, ``moment_matching_batch``; ``moment_matching_rollout_batch``: the whole horizon in one launch),
+``multi_step_moment_matching``, ``moment_matching_batch``; ``moment_matching_rollout_batch``: the whole horizon in one launch;
+``moment_matching_rollout_vjp_batch`` / ``moment_matching_rollout_diff_batch``: its reverse pass in one call, one autograd node),
 the scheme the two above approximate.  The GP is evaluated at
 the Gaussian input z = G x + g0, G = [a_gp_inp_x; K], g0 = [0; k_ff] (``SimpleGPModel.moment_match_device``: mean, full
 covariance across outputs and expected Jacobian V in closed form), and with A = a + b K
@@ -463,6 +464,68 @@ def moment_matching_rollout_batch(mu_0, ssm, k_ff, k_fb, a=None, b=None, sigma_0
     kfb = B.as_dev(k_fb, dev, (T, H - 1, n_u, n_s)) if H > 1 else None
     outs = ssm.moment_match_rollout_device(mu, kff, kfb, ta, tb, sigma_0, None if a_gp_inp_x is None else tz)
     return outs if as_t else tuple(B.to_numpy(o) for o in outs)
+
+
+def moment_matching_rollout_vjp_batch(mu_0, ssm, k_ff, k_fb, mu_all, sigma_all, mu_all_bar=None, sigma_all_bar=None,
+                                      cov_all_bar=None, a=None, b=None, sigma_0=None, a_gp_inp_x=None):
+    """The reverse pass of ``moment_matching_batch`` / ``moment_matching_rollout_batch`` in ONE call
+    (``sr_gp_moment_match_rollout_vjp``, ``SimpleGPModel.moment_match_rollout_vjp_device``): the gradient of
+    sum(mu_all_bar * mu_all) + sum(sigma_all_bar * sigma_all) + sum(cov_all_bar * gp_cov_all) in mu_0, sigma_0, k_ff and k_fb at
+    the mu_all, sigma_all either forward returned.  Seeds shaped like the forward's results, None = zero (not all three).
+    Returns (mu_0_bar, sigma_0_bar | None without sigma_0, k_ff_bar, k_fb_bar | None when H == 1), the gain gradients shaped
+    like k_ff / k_fb (summed over T for a shared, 2-D policy).  NumPy in -> NumPy out; device tensors in -> device tensors
+    out.  ARD-RBF models of any size (NotImplementedError otherwise)."""
+    dev, n_s, n_u, ta, tb, tz = _mm_setup(ssm, a, b, a_gp_inp_x)
+    as_t = B.is_tensor(mu_0)
+    outs = ssm.moment_match_rollout_vjp_device(mu_0, k_ff, k_fb, ta, tb, mu_all, sigma_all, mu_all_bar, sigma_all_bar,
+                                               cov_all_bar, sigma_0, None if a_gp_inp_x is None else tz)
+    return outs if as_t else tuple(None if o is None else B.to_numpy(o) for o in outs)
+
+
+class _MomentMatchRolloutFn(torch.autograd.Function):
+    """``moment_matching_rollout_diff_batch``: the forward is ``moment_matching_rollout_batch``, the backward ONE call of
+    ``moment_match_rollout_vjp_device`` at the saved results.  Seeds of results nobody used arrive as None (= zero)."""
+
+    @staticmethod
+    def forward(ctx, ssm, a, b, a_gp_inp_x, mu_0, sigma_0, k_ff, k_fb):
+        outs = moment_matching_rollout_batch(mu_0.detach(), ssm, k_ff.detach(), None if k_fb is None else k_fb.detach(), a, b,
+                                             None if sigma_0 is None else sigma_0.detach(), a_gp_inp_x)
+        ctx.ssm, ctx.lin = ssm, (a, b, a_gp_inp_x)
+        ctx.opt = (sigma_0 is not None, k_fb is not None)
+        ctx.save_for_backward(mu_0, k_ff, outs[0], outs[1], *[x for x in (sigma_0, k_fb) if x is not None])
+        ctx.set_materialize_grads(False)
+        return outs
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, mu_all_bar, sigma_all_bar, cov_all_bar):
+        mu_0, k_ff, mu_all, sigma_all, *rest = ctx.saved_tensors
+        rest = list(rest)
+        sigma_0 = rest.pop(0) if ctx.opt[0] else None
+        k_fb = rest.pop(0) if ctx.opt[1] else None
+        a, b, a_gp_inp_x = ctx.lin
+        if mu_all_bar is None and sigma_all_bar is None and cov_all_bar is None:
+            return (None,) * 8
+        dev, n_s, n_u, ta, tb, tz = _mm_setup(ctx.ssm, a, b, a_gp_inp_x)
+        g = ctx.ssm.moment_match_rollout_vjp_device(mu_0, k_ff, k_fb, ta, tb, mu_all, sigma_all, mu_all_bar, sigma_all_bar,
+                                                    cov_all_bar, sigma_0, None if a_gp_inp_x is None else tz)
+        return None, None, None, None, g[0], g[1], g[2], g[3]
+
+
+def moment_matching_rollout_diff_batch(mu_0, ssm, k_ff, k_fb, a=None, b=None, sigma_0=None, a_gp_inp_x=None):
+    """``moment_matching_rollout_batch`` as ONE ``torch.autograd.Function`` for the whole roll-out: the same arguments
+    (mu_0 (T,n_s); k_ff (T,H,n_u); k_fb (T,H-1,n_u,n_s) or None when H == 1; sigma_0 (T,n_s,n_s) or None), the same three
+    results with the same bits -- the fused kernel inside its domain, the per-step route outside --, and a backward that is
+    one call of ``sr_gp_moment_match_rollout_vjp`` (once differentiable; gradients to mu_0, sigma_0, k_ff and k_fb, not to a, b
+    or the model).  ARD-RBF models only (NotImplementedError otherwise, before any launch).  Device tensors come back as
+    device tensors that carry the graph; NumPy inputs give NumPy results (the plain forward: nothing to differentiate)."""
+    dev, n_s, n_u, ta, tb, tz = _mm_setup(ssm, a, b, a_gp_inp_x)
+    if any(kt != "rbf" for kt in ssm.kern_types):
+        raise NotImplementedError("moment matching: the reverse pass is for ARD-RBF models only")
+    as_t = B.is_tensor(mu_0)
+    leaves = [None if x is None else B.as_dev(x, dev) for x in (mu_0, sigma_0, k_ff, k_fb)]
+    outs = _MomentMatchRolloutFn.apply(ssm, a, b, a_gp_inp_x, *leaves)
+    return outs if as_t else tuple(B.to_numpy(o.detach()) for o in outs)
 
 
 def one_step_moment_matching(mu_x, ssm, k_ff, sigma_x=None, k_fb=None, a=None, b=None, a_gp_inp_x=None):
