@@ -22,7 +22,7 @@
 //        the 16 rollouts (sr_ellipsoid_one, one lane each, state (p, Q) in LDS), writes p_all / q_all.
 // The centres do not depend on the shape matrices, so the posterior workgroups never wait for an ellipsoid step (n_s = 4:
 // 8 us of Jacobi rotations): the Q chain trails the chain of centres.
-// Exchange: every element is 16 bytes (value, bits(value) ^ mix(tag)), tag = the group's epoch + step + 1, written by ONE
+// Exchange: every element is 16 bytes (value, bits(value) ^ mix(tag)), tag = (the group's epoch + step + 1, H, parts: sr_chain_tag), written by ONE
 // agent-scope store and read by one agent-scope load; a reader polls until value and check word agree for this step's
 // tag.  No ticket, no fence, no wait for the stores to be acknowledged; every (step, output) has its own slot, so
 // nothing is overwritten inside a launch; the epoch lives on the device (a captured launch can be replayed).
@@ -182,6 +182,20 @@ __device__ __forceinline__ bool sr_xel_poll(const sr_xel* p, long stride, unsign
     }
 }
 
+// The tag of step i of a launch whose group stands at epoch `base`: the step count epoch + i + 1 above the launch's layout.
+// Where an element lies in the buffer depends on H (slot g H + i of group g) and on the parts per output (SR_CHAIN_BS), and a
+// handle's launches may differ in both (another H; a model that grew to another padded size).  The epochs count per group, so
+// with the step count alone group g can meet, in a slot that another group wrote under another layout, exactly the count it
+// waits for, and take that old element for its own step's: H = 12 with 5 roll-outs leaves count s + 1 in slot s; two launches of
+// H = 2 with 32 roll-outs move group 1 to epoch 4; group 1 of an H = 4 launch then reads slots 4 .. 7 for the counts 5 .. 8.
+// With the layout in the tag, two elements carry the same tag only under the same layout, where slot (g, i) is only ever
+// written by group g at step i and its counts grow from launch to launch.
+template <int P>
+__device__ __forceinline__ unsigned long long sr_chain_tag(unsigned long long base, int i, int H) {
+    static_assert(P >= 1 && P <= 4, "two bits for the parts");
+    return (base + (unsigned long long)i + 1ull) << 9 | (unsigned long long)(P - 1) << 7 | (unsigned long long)H;   // H < 128 (sr_launch_chain)
+}
+
 // centre of the next step: p1 = a p + b u + mu (gp_reachability.py:82-83 / :115) -- the operation order of
 // sr_ellipsoid_one, so the workgroups that only follow the centres and the one that runs the full step agree bit for bit
 template <int NS, int NU>
@@ -301,7 +315,7 @@ __global__ __launch_bounds__(64 * SR_CHAIN_NW) void sr_chain_kernel(sr_chain_arg
         __syncthreads();
         if (tid == 0) __hip_atomic_store(c.alive + g, base_s + 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         for (int i = 0; i < c.H; ++i) {
-            const unsigned long long tag = base_s + (unsigned long long)i + 1ull;
+            const unsigned long long tag = sr_chain_tag<P>(base_s, i, c.H);
             const sr_xel* xi = c.xch + ((long)g * c.H + i) * n_out * BS;
             if (tid < n_out * SR_FQ * (D + 2)) {
                 const int o = tid / (SR_FQ * (D + 2)), r = tid % (SR_FQ * (D + 2));
@@ -342,9 +356,9 @@ __global__ __launch_bounds__(64 * SR_CHAIN_NW) void sr_chain_kernel(sr_chain_arg
             sr_small_phase_a<NP, DT, false, KEEP, NW>(c.k, d, xa, NS, xb, (long)c.H * NU, nq, L, &rows);
             __syncthreads();                                   // R complete: the partial-R buffer becomes the partial-V buffer
             // Every 16-byte element of the exchange buffer is (value, tag) written by ONE store, tag = the group's epoch
-            // + step + 1: a reader polls the elements it needs until they carry this step's tag -- no ticket, no wait for
+            // + step + 1 above the launch's layout (sr_chain_tag): a reader polls the elements it needs until they carry this step's tag -- no ticket, no wait for
             // the stores to be acknowledged.  (mu, d mu/dx)[d] leave before the contraction with U^-1 starts.
-            const unsigned long long tag = base_s + (unsigned long long)i + 1ull;
+            const unsigned long long tag = sr_chain_tag<P>(base_s, i, c.H);
             sr_xel* xo = c.xch + (((long)g * c.H + i) * n_out + d) * BS;
             if (TAIL && part == 0 && tid < SR_FQ * (D + 1)) {
                 const int j = tid >> 4, t = tid & 15;
@@ -479,6 +493,7 @@ bool sr_chain_supported(int Np, int D, int n_s, int n_u, int H) {
 
 int sr_launch_chain(const sr_chain_args& a, hipStream_t s) {
     const int n_s = a.k.n_out, n_u = a.k.D - a.k.n_out;
+    SR_CHECK(a.H >= 1 && a.H < 128, SR_EINVAL, "chain: H=%d (the tags hold seven bits of it)", a.H);
     SR_CHECK((a.T + SR_FQ - 1) / SR_FQ * sr_chain_wgs_per_group(a.k.Np, n_s) <= SR_CHAIN_GROUPS, SR_EINVAL,
              "chain: %ld rollouts x %d outputs x %d parts do not fit one launch", a.T, n_s, a.k.Np / 128);
     SR_CHECK((a.T + SR_FQ - 1) / SR_FQ * sr_chain_xels_per_group(a.k.Np, n_s, n_u, a.H) <= (long)SR_CHAIN_XELS, SR_EINVAL,

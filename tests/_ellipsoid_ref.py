@@ -30,14 +30,14 @@ KFB_SCALES = (0.0, 0.3, 1e3)       # thirds of every family; 1e3 makes I + K^T K
 Q_FAMILIES = ("random", "diag", "identity", "rank1", "twin_top", "all_equal", "graded", "tiny", "huge", "rounded")
 
 
-def _ld(x):
-    return None if x is None else np.asarray(x, dtype=LD)
+def _ld(x, dtype=LD):
+    return None if x is None else np.asarray(x, dtype=dtype)
 
 
 def _cholesky(b):
-    """lower Cholesky factor, long double, plain column loop"""
+    """lower Cholesky factor in the dtype of b (long double unless the caller chose another), plain column loop"""
     n = b.shape[0]
-    l = np.zeros((n, n), dtype=LD)
+    l = np.zeros((n, n), dtype=b.dtype)
     for j in range(n):
         s = b[j, j] - np.dot(l[j, :j], l[j, :j])
         l[j, j] = np.sqrt(s)
@@ -46,37 +46,39 @@ def _cholesky(b):
     return l
 
 
-def similarity(q, k_fb):
-    """M = L^T Q L with B = I + K^T K = L L^T, all in long double: eig(M) == eig(Q B)."""
-    q = _ld(q)
+def similarity(q, k_fb, dtype=LD):
+    """M = L^T Q L with B = I + K^T K = L L^T, all in `dtype` (long double): eig(M) == eig(Q B)."""
+    q = _ld(q, dtype)
     q = (q + q.T) / 2
-    k = _ld(k_fb)
-    l = _cholesky(np.eye(q.shape[0], dtype=LD) + k.T.dot(k))
+    k = _ld(k_fb, dtype)
+    l = _cholesky(np.eye(q.shape[0], dtype=dtype) + k.T.dot(k))
     return l.T.dot(q).dot(l)
 
 
-def lambda_max_qb(q, k_fb):
-    """largest eigenvalue of Q (I + K^T K), Q symmetric positive semi-definite; long double scalar"""
-    m = similarity(q, k_fb)
+def lambda_max_qb(q, k_fb, dtype=LD):
+    """largest eigenvalue of Q (I + K^T K), Q symmetric positive semi-definite; a scalar of `dtype` (long double)"""
+    m = similarity(q, k_fb, dtype)
     m = (m + m.T) / 2
     _, vec = np.linalg.eigh(m.astype(np.float64))
-    v = _ld(vec[:, -1])
+    v = _ld(vec[:, -1], dtype)
     return v.dot(m).dot(v) / v.dot(v)
 
 
-def _lin(a, b, n_s, n_u):
+def _lin(a, b, n_s, n_u, dtype=LD):
     if a is None:                                  # gp_reachability.py:61-63
-        return np.eye(n_s, dtype=LD), np.zeros((n_s, n_u), dtype=LD)
-    return _ld(a), _ld(b)
+        return np.eye(n_s, dtype=dtype), np.zeros((n_s, n_u), dtype=dtype)
+    return _ld(a, dtype), _ld(b, dtype)
 
 
-def step(p, q, k_ff, k_fb, mu, var, jac, l_mu, l_sigma, c, a, b, mode=0):
+def step(p, q, k_ff, k_fb, mu, var, jac, l_mu, l_sigma, c, a, b, mode=0, dtype=LD):
     """One query.  p (n_s,), q (n_s,n_s) or None, k_ff (n_u,), k_fb (n_u,n_s), mu, var (n_s,), jac (n_s,n_s+n_u),
     mode 0: reachability step; 1: Taylor moments; 2: mean-equivalent moments (jac is not read).
-    Returns dict(p1, q1, bad, p1_abs, q1_abs), long double."""
-    p, u, mu, var = _ld(p), _ld(k_ff), _ld(mu), _ld(var)
+    Returns dict(p1, q1, bad, p1_abs, q1_abs), long double; dtype=np.float64 runs the same lines in fp64 (the rounding floor of
+    a correct fp64 implementation; tests/_chain_ref.py)."""
+    ld = lambda x: _ld(x, dtype)
+    p, u, mu, var = ld(p), ld(k_ff), ld(mu), ld(var)
     n_s, n_u = p.shape[0], u.shape[0]
-    a, b = _lin(a, b, n_s, n_u)
+    a, b = _lin(a, b, n_s, n_u, dtype)
     p1 = a.dot(p) + b.dot(u) + mu                                     # :82-83 / :115
     p1_abs = np.abs(a).dot(np.abs(p)) + np.abs(b).dot(np.abs(u)) + np.abs(mu)
     if q is None:
@@ -87,12 +89,12 @@ def step(p, q, k_ff, k_fb, mu, var, jac, l_mu, l_sigma, c, a, b, mode=0):
         else:                                                         # uncertainty_propagation_casadi.py:50-55
             q1, bad = np.diag(var), False
         return dict(p1=p1, q1=q1, bad=bad, p1_abs=p1_abs, q1_abs=np.abs(q1))
-    q, k = _ld(q), _ld(k_fb)
+    q, k = ld(q), ld(k_fb)
     if mode == 2:
         h = a + b.dot(k)
         h_abs = np.abs(a) + np.abs(b).dot(np.abs(k))
     else:
-        jac = _ld(jac)
+        jac = ld(jac)
         a_mu, b_mu = jac[:, :n_s], jac[:, n_s:]                       # :110-111
         h = a + a_mu + (b_mu + b).dot(k)                              # :114
         h_abs = np.abs(a) + np.abs(a_mu) + (np.abs(b_mu) + np.abs(b)).dot(np.abs(k))
@@ -100,9 +102,9 @@ def step(p, q, k_ff, k_fb, mu, var, jac, l_mu, l_sigma, c, a, b, mode=0):
     q0_abs = h_abs.dot(np.abs(q)).dot(h_abs.T)
     if mode != 0:                                                     # [a b I] Sigma_all [a b I]^T = H Sigma H^T + diag(var)
         return dict(p1=p1, q1=q0 + np.diag(var), bad=False, p1_abs=p1_abs, q1_abs=q0_abs + np.diag(var))
-    r2 = lambda_max_qb(q, k)                                          # utils.py:129-142
-    ub_mu = _ld(l_mu) * r2
-    ub_sg = c * (np.sqrt(var) + _ld(l_sigma) * np.sqrt(r2))           # :127
+    r2 = lambda_max_qb(q, k, dtype)                                        # utils.py:129-142
+    ub_mu = ld(l_mu) * r2
+    ub_sg = c * (np.sqrt(var) + ld(l_sigma) * np.sqrt(r2))           # :127
     bad = not bool(np.all(ub_mu > 0) and np.all(ub_sg > 0))
     d_s, d_m = n_s * ub_sg * ub_sg, n_s * ub_mu * ub_mu               # utils_ellipsoid.py:197-233
     c1 = np.sqrt(d_s.sum() / d_m.sum())                               # utils_ellipsoid.py:88-92

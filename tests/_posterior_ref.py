@@ -149,10 +149,12 @@ class Problem(object):
 
 
 # ------------------------------------------------------------------------------------------------ long-double algebra
-def cholesky_ld(a):
-    """lower Cholesky factor of a (long double), one vector operation per column"""
+def cholesky_ld(a, dtype=LD):
+    """lower Cholesky factor of a (long double), one vector operation per column.  dtype (here and below): np.float64 runs
+    the same lines in fp64, the rounding floor of a correct fp64 implementation (tests/_chain_ref.py)"""
     n = a.shape[0]
-    l = np.zeros((n, n), dtype=LD)
+    a = np.asarray(a, dtype=dtype)
+    l = np.zeros((n, n), dtype=dtype)
     for j in range(n):
         s = a[j, j] - np.dot(l[j, :j], l[j, :j])
         assert s > 0
@@ -162,9 +164,9 @@ def cholesky_ld(a):
     return l
 
 
-def solve_lower_ld(l, rhs):
+def solve_lower_ld(l, rhs, dtype=LD):
     """l^-1 rhs by forward substitution, rhs (n, m)"""
-    x = np.array(rhs, dtype=LD)
+    x = np.array(rhs, dtype=dtype)
     for i in range(l.shape[0]):
         if i:
             x[i] -= l[i, :i].dot(x[:i])
@@ -172,9 +174,9 @@ def solve_lower_ld(l, rhs):
     return x
 
 
-def solve_upper_ld(l, rhs):
+def solve_upper_ld(l, rhs, dtype=LD):
     """l^-T rhs by back substitution (l lower), rhs (n, m)"""
-    x = np.array(rhs, dtype=LD)
+    x = np.array(rhs, dtype=dtype)
     for i in range(l.shape[0] - 1, -1, -1):
         if i + 1 < l.shape[0]:
             x[i] -= l[i + 1:, i].dot(x[i + 1:])
@@ -182,8 +184,9 @@ def solve_upper_ld(l, rhs):
     return x
 
 
-def kernel_ld(kern, x, z, ls, sf2):
+def kernel_ld(kern, x, z, ls, sf2, dtype=LD):
     """k (T, n) and g = kappa'(r) / r (T, n) of x (T, D) against z (n, D), long double"""
+    LD = dtype
     x, z, ls = np.asarray(x, dtype=LD), np.asarray(z, dtype=LD), np.asarray(ls, dtype=LD)
     diff = (x[:, None, :] - z[None, :, :]) / ls[None, None, :]
     r2 = np.sum(diff * diff, axis=2)
