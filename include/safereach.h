@@ -411,6 +411,35 @@ int sr_onestep_moments_vjp(sr_gp_t h, long T, int mode, const double* mu_x, cons
                            const double* k_fb, const double* a, const double* b, const double* mu1_bar,
                            const double* sigma1_bar, const double* gpvar_bar, double* mux_bar, double* sigma_bar,
                            double* kff_bar, double* kfb_bar, void* stream);
+/* sr_multistep_moments_vjp: the reverse pass of a whole Taylor (mode 1) / mean-equivalent (mode 2) roll-out, GP included.  The
+ * forward arguments are those of sr_multistep_moments with an optional sigma0 T x n_s x n_s: sigma0 == NULL, step 0 starts from a
+ * point (what sr_multistep_moments computes); sigma0 given, the roll-out starts from N(mu0, sigma0) and step 0 has a zero gain (H
+ * rounds of sr_onestep_moments, the first with k_fb = 0).  Step i >= 1 uses k_fb[i-1]; k_fb and kfb_bar may be NULL when H == 1.
+ * mu_all T x H x n_s and sigma_all T x H x n_s x n_s are what either forward returned (the two agree to rounding): step i is
+ * differentiated at the stored (mu_{i-1}, Sigma_{i-1}), step 0 at (mu0, sigma0) or in the point branch.
+ * Seeds mu_all_bar, sigma_all_bar, gpvar_all_bar (T x H x n_s) shaped like the three forward outputs (any NULL = zero, the same
+ * bits; not all three).  With L = sum mu_all_bar . mu_all + sum sigma_all_bar . sigma_all + sum gpvar_all_bar . gp_var_all the
+ * outputs are dL/dmu0 (T x n_s), dL/dsigma0 (T x n_s x n_s, exactly symmetric; required iff sigma0 is given, not read otherwise),
+ * dL/dk_ff (T x H x n_u) and dL/dk_fb (T x (H-1) x n_u x n_s).  a, b and the model get no derivative.
+ * Per trajectory, for i = H-1 .. 0: the seed of step i is the caller's seed on step i plus the (mu_bar, sigma_bar) step i+1
+ * produced; the step is differentiated by the formulas of sr_onestep_moments_vjp -- the same device functions --; the GP link adds
+ * Tz^T z_bar[:n_x_in] to mu_bar and z_bar[n_x_in:] to kff_bar[i].  The conventions are those of sr_onestep_moments_vjp: only the
+ * symmetric part of a sigma seed counts (the seed is symmetrised before the carried sigma_bar is added: a seed and its symmetric
+ * part give the same bits), the clip of the GP variance at 1e-15 is ignored, there is no square root: nothing is NaN that was not.
+ * Structure: trajectories in groups of max(1, chunk / H) (sr_gp_set_chunk), at most 2^28 doubles of scratch.  Per group ONE launch
+ * forms z_n = [Tz mu_in; k_ff[t][i]], n = t H + i, of every (trajectory, step) pair with the step's (Sigma_in, K_in) dense in n
+ * (the launch of sr_multistep_reach_vjp); the GP derivatives of all pairs go into the grow-only scratch of sr_onestep_reach_vjp, in
+ * passes of at most min(chunk, 256 k) queries exactly as there (the split counts depend on the model alone): sr_gp_linearize_batch
+ * in mode 1 (the Hessian of the mean is read at steps with a Gaussian input only), sr_gp_predict_grad in mode 2 and for H == 1 from
+ * a point; then ONE launch sweeps, one thread per trajectory in workgroups of one wavefront.  No atomics, no waiting between
+ * workgroups, sums in a fixed order: the same bits on every call, for ANY chunk size and whatever other trajectories are in the batch.
+ * Every kernel identifier, exact and sparse handles and the input transform are accepted.  Before any launch: SR_EINVAL NULL where
+ * required, sigma0 without sigma0_bar, every seed NULL, mode outside {1, 2}, H < 1, T < 0; SR_ESTATE not factorized;
+ * SR_EUNSUPPORTED D > 8, n_s > 8, n_u > 4; T == 0 is a no-op.  Asynchronous on `stream`. */
+int sr_multistep_moments_vjp(sr_gp_t h, long T, int H, int mode, const double* mu0, const double* sigma0, const double* k_ff,
+                             const double* k_fb, const double* a, const double* b, const double* mu_all, const double* sigma_all,
+                             const double* mu_all_bar, const double* sigma_all_bar, const double* gpvar_all_bar, double* mu0_bar,
+                             double* sigma0_bar, double* kff_bar, double* kfb_bar, void* stream);
 
 /* ---- exact moment matching: the GP at Gaussian inputs (beyond the reference, which has the two approximations above) ----
  * For T inputs z ~ N(m[t], S[t]) (m T x D; S T x D x D symmetric PSD, may be singular; NULL = all zero) the exact mean,

@@ -84,6 +84,7 @@ SIGNATURES = {
     "sr_moment_step_vjp": (_I, [_I, _L, _I, _I, _I] + [_P] * 19),
     "sr_onestep_moments": (_I, [_H, _L, _I] + [_P] * 10),
     "sr_onestep_moments_vjp": (_I, [_H, _L, _I] + [_P] * 14),
+    "sr_multistep_moments_vjp": (_I, [_H, _L, _I, _I] + [_P] * 16),
     "sr_remainder_overapprox": (_I, [_I, _L, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
     "sr_safety_distance": (_I, [_I, _L, _I, _I, _P, _P, _P, _P, _D, _P, _P]),
     "sr_distance_to_center": (_I, [_I, _L, _I, _I, _P, _I, _P, _P, _P, _P]),

@@ -1,6 +1,6 @@
 // sr_capi_reach.hip -- reachability entry points: one-step and multi-step ellipsoid propagation (mode 0) and Gaussian moment
 // propagation (modes 1 / 2) through one forward step (ell_args, reach_step) and one driver each (onestep_impl, multistep_impl);
-// the reverse pass of one step of either through one driver (onestep_vjp_impl) and of a whole mode-0 roll-out (sr_multistep_reach_vjp); exact moment matching, its reverse pass and
+// the reverse pass of one step of either through one driver (onestep_vjp_impl) and of a whole roll-out (sr_multistep_reach_vjp, mode 0; sr_multistep_moments_vjp, modes 1 / 2); exact moment matching, its reverse pass and
 // its roll-out in one launch; the stateless per-query steps (ellipsoid, moments, their reverse passes, remainder, safety distance, distance to centre, sampling);
 // and the dispatch of the persistent chain kernel (sr_chain.hip K0c) with its process-wide launch gate.
 #include "sr_handle.h"
@@ -748,6 +748,96 @@ extern "C" int sr_multistep_reach_vjp(sr_gp_t h, long T, int H, const double* p0
         }
         sr_prof_scope ps(&h->prof, SR_K_REACH_VJP, s);
         SR_TRY(sr_launch_reach_rollout_vjp(r, s));
+    }
+    return SR_OK;
+}
+
+// doubles of reach_ws per (trajectory, step) pair of sr_multistep_moments_vjp: z | mu, var | jac_mu, jac_var | hess_mu (where it is
+// read) | mu_bar, var_bar | jac_bar, jac_s, jz (mode 1) | q_in, kfb_in | p_seed, q_seed | p_bar, q_bar, kff_bar, kfb_bar
+static long sr_moments_rollout_vjp_ws_per_query(int n_s, int n_u, int D, int mode, bool second) {
+    return D + 4L * n_s + 2L * n_s * D + (second ? (long)n_s * D * D : 0) + (mode == 1 ? 2L * n_s * (n_s + n_u) + (long)n_s * D : 0) +
+           2L * n_s + 3L * n_s * n_s + 2L * n_u * n_s + n_u;
+}
+
+// The reverse pass of sr_multistep_moments, and of H rounds of sr_onestep_moments from N(mu0, sigma0) (sr_moments_rollout_vjp.hip).
+// Per group of max(1, chunk / H) trajectories: the inputs of all their steps (the launch of sr_multistep_reach_vjp), the GP derivatives
+// at them in passes bounded as onestep_vjp_impl bounds them -- sr_gp_linearize_batch in mode 1, where a step from a Gaussian reads
+// the Hessian of the mean, sr_gp_predict_grad in mode 2 and for one step from a point --, then the sweep, one thread per trajectory.
+// A thread owns its trajectory: the grouping decides nothing but the size of the scratch.
+extern "C" int sr_multistep_moments_vjp(sr_gp_t h, long T, int H, int mode, const double* mu0, const double* sigma0,
+                                        const double* k_ff, const double* k_fb, const double* a, const double* b,
+                                        const double* mu_all, const double* sigma_all, const double* mu_all_bar,
+                                        const double* sigma_all_bar, const double* gpvar_all_bar, double* mu0_bar,
+                                        double* sigma0_bar, double* kff_bar, double* kfb_bar, void* stream) {
+    const char* who = "sr_multistep_moments_vjp";
+    SR_CHECK(h != nullptr, SR_EINVAL, "%s: NULL handle", who);
+    SR_CHECK(h->factorized, SR_ESTATE, "%s: model not factorized", who);
+    SR_CHECK(T >= 0 && H >= 1 && (mode == 1 || mode == 2), SR_EINVAL, "%s: T=%ld H=%d mode=%d", who, T, H, mode);
+    int n_s, n_u;
+    SR_TRY(check_reach_dims(h, &n_s, &n_u));
+    if (h->D > 8) {                                   // the widths sr_gp_linearize_batch is compiled for
+        sr_set_error("%s: D=%d > 8 (the batched linearisation behind it)", who, h->D);
+        return SR_EUNSUPPORTED;
+    }
+    if (T == 0) return SR_OK;
+    SR_CHECK(mu0 && k_ff && a && b && mu_all && sigma_all && mu0_bar && kff_bar, SR_EINVAL, "%s: NULL argument", who);
+    SR_CHECK(H == 1 || (k_fb && kfb_bar), SR_EINVAL, "%s: k_fb and kfb_bar required for H > 1", who);
+    SR_CHECK(sigma0 == nullptr || sigma0_bar != nullptr, SR_EINVAL, "%s: sigma0 without sigma0_bar", who);
+    SR_CHECK(mu_all_bar || sigma_all_bar || gpvar_all_bar, SR_EINVAL, "%s: every seed NULL", who);
+    hipStream_t s = (hipStream_t)stream;
+    SR_DEVICE(h->device);
+    const int D = h->D, n_xin = h->n_xin ? h->n_xin : n_s;
+    const bool second = mode == 1 && (H > 1 || sigma0 != nullptr);
+    const long per = sr_moments_rollout_vjp_ws_per_query(n_s, n_u, D, mode, second);
+    const long nss = (long)n_s * n_s, nus = (long)n_u * n_s, nd = (long)n_s * D, nds = (long)n_s * (n_s + n_u);
+    // a group: chunk / H trajectories and at most 2^28 doubles (2 GB) of scratch; a pass of GP derivatives: as in onestep_vjp_impl
+    const long group = std::max(1L, std::min(h->chunk / H, ((long)1 << 28) / (per * H)));
+    const long pass = std::max(1L, std::min(h->chunk, sr_stable_pass_max(h->N, h->Np, h->n_out)));
+    const long Qw = std::min(group, T) * H;
+    SR_TRY(h->reach_ws.grow((size_t)(Qw * per), wait::stream(s)));
+    double* w = h->reach_ws.get();
+    auto take = [&](long each) { double* x = w; w += Qw * each; return x; };
+    sr_mrv_args m{};
+    sr_rrv_args& r = m.r;
+    sr_ellvjp_args& ea = r.e;
+    r.z = take(D);
+    double* mu = take(n_s);
+    double* var = take(n_s);
+    double* jm = take(nd);
+    double* jv = take(nd);
+    double* hm = second ? take(nd * D) : nullptr;
+    ea.mu_bar = take(n_s); ea.var_bar = take(n_s);
+    if (mode == 1) { ea.jac_bar = take(nds); ea.jac_s = take(nds); ea.jz = take(nd); }
+    r.q_in = take(nss); r.kfb_in = take(nus); r.p_seed = take(n_s); r.q_seed = take(nss);
+    ea.p_bar = take(n_s); ea.q_bar = take(nss); ea.kff_bar = take(n_u); ea.kfb_bar = take(nus);
+    ea.q = r.q_in; ea.k_fb = r.kfb_in; ea.var = var; ea.jac = jm;
+    ea.a = a; ea.b = b; ea.c_safety = 1.0;
+    ea.p1_bar = r.p_seed; ea.q1_bar = r.q_seed;
+    ea.jac_mu = jm; ea.jac_var = jv; ea.hess_mu = hm; ea.Tz = h->n_xin ? h->Tz : nullptr; ea.D = D; ea.n_xin = n_xin;
+    r.H = H; r.n_s = n_s; r.n_u = n_u;
+    m.mode = mode;
+    for (long t0 = 0; t0 < T; t0 += group) {
+        const long Tg = std::min(group, T - t0), Q = Tg * H;
+        ea.T = Tg;
+        r.p0 = mu0 + t0 * n_s; r.q0 = sigma0 ? sigma0 + t0 * nss : nullptr;
+        r.k_ff = k_ff + t0 * H * n_u; r.k_fb = k_fb ? k_fb + t0 * (H - 1) * nus : nullptr;
+        r.p_all = mu_all + t0 * H * n_s; r.q_all = sigma_all + t0 * H * nss;
+        r.p_all_bar = mu_all_bar ? mu_all_bar + t0 * H * n_s : nullptr;
+        r.q_all_bar = sigma_all_bar ? sigma_all_bar + t0 * H * nss : nullptr;
+        m.gpvar_all_bar = gpvar_all_bar ? gpvar_all_bar + t0 * H * n_s : nullptr;
+        r.p0_bar = mu0_bar + t0 * n_s; r.q0_bar = sigma0 ? sigma0_bar + t0 * nss : nullptr;
+        r.kff_bar = kff_bar + t0 * H * n_u; r.kfb_bar = H > 1 ? kfb_bar + t0 * (H - 1) * nus : nullptr;
+        SR_TRY(sr_launch_reach_rollout_prep(r, s));
+        for (long q1 = 0; q1 < Q; q1 += pass) {
+            const long Qc = std::min(pass, Q - q1);
+            if (second)
+                SR_TRY(sr_gp_linearize_batch(h, r.z + q1 * D, Qc, mu + q1 * n_s, var + q1 * n_s, jm + q1 * nd, jv + q1 * nd,
+                                             hm + q1 * nd * D, stream));
+            else
+                SR_TRY(sr_gp_predict_grad(h, r.z + q1 * D, Qc, mu + q1 * n_s, var + q1 * n_s, jm + q1 * nd, jv + q1 * nd, stream));
+        }
+        sr_prof_scope ps(&h->prof, SR_K_REACH_VJP, s);
+        SR_TRY(sr_launch_moments_rollout_vjp(m, s));
     }
     return SR_OK;
 }

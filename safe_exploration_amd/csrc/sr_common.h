@@ -758,6 +758,17 @@ struct sr_rrv_args {
 int sr_launch_reach_rollout_prep(const sr_rrv_args& r, hipStream_t s);
 int sr_launch_reach_rollout_eig(const sr_rrv_args& r, hipStream_t s);
 int sr_launch_reach_rollout_vjp(const sr_rrv_args& r, hipStream_t s);
+// reverse pass of a roll-out of H steps in mode 1 / 2 (sr_moments_rollout_vjp.hip): the fields of sr_rrv_args under the names of the
+// moment roll-out -- p0 = mu0, q0 = sigma0 (NULL: point start), k_fb0 NULL (step 0 has a zero gain), p_all / q_all = mu_all / sigma_all
+// and their seeds, p0_bar / q0_bar = mu0_bar / sigma0_bar, kfb0_bar and eig unread; r.e as sr_momvjp_args names it: jac_bar NULL in
+// mode 2, hess_mu set in mode 1 only (the sweep drops it at step 0 of a point start).  sr_launch_reach_rollout_prep(m.r) fills z, q_in
+// and kfb_in.
+struct sr_mrv_args {
+    sr_rrv_args r;
+    const double* gpvar_all_bar;      // seed on the GP variances (T x H x n_s) or NULL
+    int mode;                         // 1 Taylor, 2 mean-equivalent
+};
+int sr_launch_moments_rollout_vjp(const sr_mrv_args& m, hipStream_t s);
 int sr_launch_remainder(long T, int n_s, int n_u, const double* q, const double* k_fb,
                         const double* l_mu, const double* l_sigma, double* u_mu, double* u_sigma,
                         hipStream_t s);

@@ -9,7 +9,7 @@
 // jac_mu == NULL, no link (sr_moment_step_vjp); hess_mu == NULL, no second-order term.  The host sets hess_mu only where jac_bar is
 // not zero: mode 1 from a Gaussian start.  The formulas and the conventions: sr_moments_vjp_dev.h.  Chains of steps are
 // differentiated by torch autograd over this one step (uncertainty_propagation_casadi.multistep_moments_batch(differentiable=
-// True)); there is no persistent reverse chain.
+// True)), or in one call by the sweep of sr_moments_rollout_vjp.hip over the same device functions.
 #include "sr_common.h"
 #include "sr_moments_vjp_dev.h"
 

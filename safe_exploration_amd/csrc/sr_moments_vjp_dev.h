@@ -32,45 +32,49 @@
 
 // (sr_momvjp_args: sr_common.h)
 
-// the reverse of sr_ellipsoid_one in mode MODE (1 or 2) for query t; writes every output of the query that is not NULL
+// the reverse of sr_ellipsoid_one in mode MODE (1 or 2) for query t; writes every output of the query that is not NULL.
+// ts (default: t), as in sr_ellipsoid_vjp_one: the index of the query in the arrays the stages hand to each other and to the next
+// step -- the two seeds, every output, jac where it is jac_s --, which the roll-out sweep (sr_moments_rollout_vjp.hip) keeps one
+// slot per thread; t indexes the query's inputs (q, k_fb, jac where it is not jac_s, gpvar_bar).
 template <int NS, int NU, int MODE>
-__device__ __forceinline__ void sr_moments_vjp_one(const sr_momvjp_args& m, long t, double* lds, int lds_stride) {
+__device__ __forceinline__ void sr_moments_vjp_one(const sr_momvjp_args& m, long t, double* lds, int lds_stride, long ts_ = -1) {
     static_assert(MODE == 1 || MODE == 2, "the moment modes");
+    const long ts = ts_ < 0 ? t : ts_;
     const sr_ellvjp_args& a = m.e;
     constexpr int D = NS + NU;
-    const double* G = a.q1_bar ? a.q1_bar + t * NS * NS : nullptr;
+    const double* G = a.q1_bar ? a.q1_bar + ts * NS * NS : nullptr;
     auto g = [&](int i, int j) { return G ? 0.5 * (G[i * NS + j] + G[j * NS + i]) : 0.0; };
     {
         double pb[NS];
 #pragma unroll
-        for (int i = 0; i < NS; ++i) pb[i] = a.p1_bar ? a.p1_bar[t * NS + i] : 0.0;
+        for (int i = 0; i < NS; ++i) pb[i] = a.p1_bar ? a.p1_bar[ts * NS + i] : 0.0;
 #pragma unroll
         for (int i = 0; i < NS; ++i) {
-            a.mu_bar[t * NS + i] = pb[i];
-            a.var_bar[t * NS + i] = g(i, i) + (m.gpvar_bar ? m.gpvar_bar[t * NS + i] : 0.0);
+            a.mu_bar[ts * NS + i] = pb[i];
+            a.var_bar[ts * NS + i] = g(i, i) + (m.gpvar_bar ? m.gpvar_bar[t * NS + i] : 0.0);
             double s = 0.0;
 #pragma unroll
             for (int k = 0; k < NS; ++k) s = fma(a.a[k * NS + i], pb[k], s);
-            a.p_bar[t * NS + i] = s;
+            a.p_bar[ts * NS + i] = s;
         }
 #pragma unroll
         for (int u = 0; u < NU; ++u) {
             double s = 0.0;
 #pragma unroll
             for (int k = 0; k < NS; ++k) s = fma(a.b[k * NU + u], pb[k], s);
-            a.kff_bar[t * NU + u] = s;
+            a.kff_bar[ts * NU + u] = s;
         }
     }
     if (a.q == nullptr) {
         if (a.jac_bar)
 #pragma unroll
-            for (int e = 0; e < NS * D; ++e) a.jac_bar[t * NS * D + e] = 0.0;
+            for (int e = 0; e < NS * D; ++e) a.jac_bar[ts * NS * D + e] = 0.0;
         if (a.q_bar)
 #pragma unroll
-            for (int e = 0; e < NS * NS; ++e) a.q_bar[t * NS * NS + e] = 0.0;
+            for (int e = 0; e < NS * NS; ++e) a.q_bar[ts * NS * NS + e] = 0.0;
         if (a.kfb_bar)
 #pragma unroll
-            for (int e = 0; e < NU * NS; ++e) a.kfb_bar[t * NU * NS + e] = 0.0;
+            for (int e = 0; e < NU * NS; ++e) a.kfb_bar[ts * NU * NS + e] = 0.0;
         return;
     }
 
@@ -89,7 +93,7 @@ __device__ __forceinline__ void sr_moments_vjp_one(const sr_momvjp_args& m, long
         for (int j = 0; j < NS; ++j)
             if (j >= i) qs[i][j] = 0.5 * (qg[i * NS + j] + qg[j * NS + i]);
 #define SR_QS(i, j) qs[(i) < (j) ? (i) : (j)][(i) < (j) ? (j) : (i)]
-    const double* jac = (MODE == 1) ? a.jac + t * NS * D : nullptr;
+    const double* jac = (MODE == 1) ? a.jac + (a.jac == a.jac_s ? ts : t) * NS * D : nullptr;
     sr_tmat<NS, sr_vjp_in_lds<NS>()> H(lds, lds_stride);
     constexpr int ROW_UNROLL = sr_vjp_in_lds<NS>() ? 1 : NS;
 #pragma unroll ROW_UNROLL
@@ -137,7 +141,7 @@ __device__ __forceinline__ void sr_moments_vjp_one(const sr_momvjp_args& m, long
 #pragma unroll
             for (int k = 0; k < NS; ++k) s = fma(t2[k], SR_QS(k, j), s);
             hb[j] = 2.0 * s;
-            if (a.jac_bar) a.jac_bar[(t * NS + i) * D + j] = (MODE == 1) ? hb[j] : 0.0;
+            if (a.jac_bar) a.jac_bar[(ts * NS + i) * D + j] = (MODE == 1) ? hb[j] : 0.0;
 #pragma unroll
             for (int l = 0; l < NS; ++l)
                 if (l >= j) qacc[j][l] = fma(H.get(i, j), t2[l], qacc[j][l]);
@@ -148,9 +152,9 @@ __device__ __forceinline__ void sr_moments_vjp_one(const sr_momvjp_args& m, long
                 double s = 0.0;
 #pragma unroll
                 for (int j = 0; j < NS; ++j) s = fma(hb[j], sr_vjp_in_lds<NS>() ? kq[u * NS + j] : K[u][j], s);
-                if (a.jac_bar) a.jac_bar[(t * NS + i) * D + NS + u] = s;
+                if (a.jac_bar) a.jac_bar[(ts * NS + i) * D + NS + u] = s;
             } else if (a.jac_bar) {
-                a.jac_bar[(t * NS + i) * D + NS + u] = 0.0;
+                a.jac_bar[(ts * NS + i) * D + NS + u] = 0.0;
             }
             const double bm = (MODE == 1 ? jac[i * D + NS + u] : 0.0) + a.b[i * NU + u];
 #pragma unroll
@@ -163,11 +167,11 @@ __device__ __forceinline__ void sr_moments_vjp_one(const sr_momvjp_args& m, long
 #pragma unroll
         for (int j = 0; j < NS; ++j)
             if (j >= i) {
-                a.q_bar[(t * NS + i) * NS + j] = qacc[i][j];
-                a.q_bar[(t * NS + j) * NS + i] = qacc[i][j];
+                a.q_bar[(ts * NS + i) * NS + j] = qacc[i][j];
+                a.q_bar[(ts * NS + j) * NS + i] = qacc[i][j];
             }
 #pragma unroll
     for (int u = 0; u < NU; ++u)
 #pragma unroll
-        for (int j = 0; j < NS; ++j) a.kfb_bar[(t * NU + u) * NS + j] = kacc[u][j];
+        for (int j = 0; j < NS; ++j) a.kfb_bar[(ts * NU + u) * NS + j] = kacc[u][j];
 }

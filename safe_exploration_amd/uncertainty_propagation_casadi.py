@@ -24,7 +24,11 @@ Beyond the reference as well: the reverse pass of ONE Taylor / mean-equivalent s
 the GP inside (``onestep_moments_batch`` / ``sr_onestep_moments``) and, on top of them, ``differentiable=True`` on
 ``moment_step_batch``, ``onestep_moments_batch`` and ``multistep_moments_batch``: the forward stays the plain call (the same
 bits), the backward is the device reverse pass, steps are chained by torch autograd.  Gradients reach the means, covariances and
-controls (and mu_g, var_g, jac_g of ``moment_step_batch``), not the model.  D <= 8; no persistent reverse chain.
+controls (and mu_g, var_g, jac_g of ``moment_step_batch``), not the model.  D <= 8.
+The reverse pass of a WHOLE Taylor / mean-equivalent roll-out in one call: ``multistep_moments_vjp_batch`` /
+``sr_multistep_moments_vjp`` (one pass of GP derivatives over all T*H steps, then a sweep, one thread per trajectory);
+``multistep_moments_diff_batch`` is the autograd surface over it, one node for the roll-out, its forward the plain one-launch
+``multistep_moments_batch`` (from sigma_0: H plain one-step calls).
 """
 import numpy as np
 import torch
@@ -300,6 +304,112 @@ class _OnestepMomentsFn(torch.autograd.Function):
             return (None,) * 6
         g = onestep_moments_vjp_batch(mu_x, ctx.ssm, k_ff, mu1_bar, sigma1_bar, gpvar_bar, sigma_x, k_fb, a, b, mode, a_gp_inp_x)
         return None, None, g[0], g[1], g[2].reshape(k_ff.shape), g[3]
+
+
+def multistep_moments_vjp_batch(mu_0, ssm, k_ff, k_fb, mu_all, sigma_all, mu_all_bar=None, sigma_all_bar=None, gpvar_all_bar=None,
+                                a=None, b=None, mode=TAYLOR, a_gp_inp_x=None, sigma_0=None):
+    """Reverse pass of a whole Taylor / mean-equivalent roll-out in one call (``sr_multistep_moments_vjp``): one pass of GP
+    derivatives at the inputs of all T*H steps -- the means mu_all are known --, then a sweep over the steps, one thread per
+    trajectory.
+
+    The forward arguments as ``multistep_moments_batch`` takes them (k_fb may be None when H == 1); sigma_0 (T,n_s,n_s): the
+    roll-out started from N(mu_0, sigma_0), step 0 with a zero gain, as ``multistep_moments_batch(sigma_0=..., differentiable=True)``
+    runs it.  mu_all (T,H,n_s), sigma_all (T,H,n_s,n_s) are what the forward returned; seeds mu_all_bar, sigma_all_bar,
+    gpvar_all_bar (T,H,n_s) shaped like its three results (None = zero, not all three).  Returns the gradients of
+    sum(mu_all_bar * mu_all) + sum(sigma_all_bar * sigma_all) + sum(gpvar_all_bar * gp_var_all): (mu0_bar, sigma0_bar, kff_bar,
+    kfb_bar), shaped like mu_0, sigma_0, k_ff and k_fb ((T,H-1,n_u,n_s)); sigma0_bar is None without sigma_0.  Only the symmetric
+    part of sigma_all_bar counts, sigma0_bar is exactly symmetric.  The same bits on every call and for any ``set_chunk``.
+    Models as ``linearize_device_batch`` takes them (D <= 8: NotImplementedError beyond).  numpy in -> numpy out, tensors in ->
+    tensors out."""
+    from .gp_reachability import _input_transform, _reach_dims
+    if not isinstance(ssm, SimpleGPModel):
+        raise TypeError("multistep_moments_vjp_batch needs the HIP SimpleGPModel")
+    ssm._need_trained()
+    if int(mode) not in (TAYLOR, MEAN_EQUIVALENT):
+        raise ValueError("mode must be TAYLOR (1) or MEAN_EQUIVALENT (2), got {}".format(mode))
+    as_t = B.is_tensor(mu_0)
+    hd = ssm._handle
+    dev = hd.device
+    n_s, n_u = _reach_dims(hd, a_gp_inp_x)
+    shp, kshp = tuple(np.shape(mu_0)), tuple(np.shape(k_ff))
+    if len(shp) != 2 or shp[1] != n_s:
+        raise ValueError("mu_0 must be (T, {})".format(n_s))
+    T = shp[0]
+    if len(kshp) != 3 or kshp[0] != T or kshp[2] != n_u or kshp[1] < 1:
+        raise ValueError("k_ff must be (T, H, {}) with H >= 1".format(n_u))
+    H = kshp[1]
+    if H > 1 and (k_fb is None or tuple(np.shape(k_fb)) != (T, H - 1, n_u, n_s)):
+        raise ValueError("k_fb must be {}".format((T, H - 1, n_u, n_s)))
+    for x, shape, name in ((sigma_0, (T, n_s, n_s), "sigma_0"), (mu_all, (T, H, n_s), "mu_all"),
+                           (sigma_all, (T, H, n_s, n_s), "sigma_all")):
+        if (x is None and name != "sigma_0") or (x is not None and tuple(np.shape(x)) != shape):
+            raise ValueError("{} must be {}".format(name, shape))
+    _check_seeds((mu_all_bar, sigma_all_bar, gpvar_all_bar), ((T, H, n_s), (T, H, n_s, n_s), (T, H, n_s)))
+    m0, kff = B.as_dev(mu_0, dev), B.as_dev(k_ff, dev)
+    kfb = B.as_dev(k_fb, dev) if H > 1 else None
+    s0, ma, sa = B.as_dev(sigma_0, dev), B.as_dev(mu_all, dev), B.as_dev(sigma_all, dev)
+    seeds = [B.as_dev(x, dev) for x in (mu_all_bar, sigma_all_bar, gpvar_all_bar)]
+    a, b = _lin_model(a, b, n_s, n_u)
+    ta, tb = B.const_dev(a, dev, (n_s, n_s)), B.const_dev(b, dev, (n_s, n_u))
+    outs = [B.empty((T, n_s), dev), B.empty((T, n_s, n_s), dev) if s0 is not None else None, B.empty((T, H, n_u), dev),
+            B.empty((T, H - 1, n_u, n_s), dev)]
+    with _input_transform(ssm, a_gp_inp_x):
+        check(lib.sr_multistep_moments_vjp(hd.h, T, H, int(mode), B.ptr(m0), B.ptr(s0), B.ptr(kff), B.ptr(kfb), B.ptr(ta), B.ptr(tb),
+                                           B.ptr(ma), B.ptr(sa), *[B.ptr(x) for x in seeds],
+                                           *[B.ptr(o) if o is not None and o.numel() else None for o in outs], B.stream_ptr(dev)))
+    return tuple(outs) if as_t else tuple(None if o is None else B.to_numpy(o) for o in outs)
+
+
+class _MultistepMomentsFn(torch.autograd.Function):
+    """``multistep_moments_diff_batch``: the forward is the plain one-launch ``multistep_moments_batch`` from a point, H plain
+    ``onestep_moments_batch`` calls from N(mu_0, sigma_0); the backward ONE ``multistep_moments_vjp_batch`` call at the saved
+    mu_all, sigma_all.  Seeds of results nobody used arrive as None (= zero, the same bits)."""
+
+    @staticmethod
+    def forward(ctx, ssm, cfg, mu_0, sigma_0, k_ff, k_fb):
+        a, b, mode, a_gp_inp_x = cfg
+        if sigma_0 is None:
+            outs = multistep_moments_batch(mu_0, ssm, k_ff, k_fb, a, b, mode, a_gp_inp_x)
+        else:
+            mu, sigma, steps = mu_0, sigma_0, []
+            for i in range(k_ff.shape[1]):
+                kfb_i = sigma_0.new_zeros((mu_0.shape[0], k_ff.shape[2], mu_0.shape[1])) if i == 0 else k_fb[:, i - 1]
+                mu, sigma, var = onestep_moments_batch(mu, ssm, k_ff[:, i], sigma, kfb_i, a, b, mode, a_gp_inp_x)
+                steps.append((mu, sigma, var))
+            outs = tuple(torch.stack([st[k] for st in steps], dim=1) for k in range(3))
+        ctx.ssm, ctx.cfg = ssm, cfg
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(mu_0, sigma_0, k_ff, k_fb, outs[0], outs[1])
+        return outs
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, mu_all_bar, sigma_all_bar, gpvar_all_bar):
+        mu_0, sigma_0, k_ff, k_fb, mu_all, sigma_all = ctx.saved_tensors
+        a, b, mode, a_gp_inp_x = ctx.cfg
+        if mu_all_bar is None and sigma_all_bar is None and gpvar_all_bar is None:
+            return (None,) * 6
+        g = multistep_moments_vjp_batch(mu_0, ctx.ssm, k_ff, k_fb, mu_all, sigma_all, mu_all_bar, sigma_all_bar, gpvar_all_bar,
+                                        a, b, mode, a_gp_inp_x, sigma_0)
+        return None, None, g[0], g[1], g[2], (g[3].reshape(k_fb.shape) if k_fb is not None else None)
+
+
+def multistep_moments_diff_batch(mu_0, ssm, k_ff, k_fb, a=None, b=None, mode=TAYLOR, a_gp_inp_x=None, sigma_0=None):
+    """``multistep_moments_batch`` (tensors only) as ONE autograd node for the whole roll-out, with gradients to mu_0, sigma_0, k_ff
+    and k_fb.  From a point the forward IS the plain one-launch call (the same bits); from sigma_0 (T,n_s,n_s) it is H plain
+    ``sr_onestep_moments`` calls, step 0 with a zero gain: the bits of ``multistep_moments_batch(sigma_0=..., differentiable=True)``.
+    The backward is ONE ``multistep_moments_vjp_batch`` call at the saved mu_all, sigma_all (once differentiable; no gradient to
+    a, b or the model).  ``multistep_moments_batch(differentiable=True)`` chains H one-step nodes instead and stays as it is."""
+    if not isinstance(ssm, SimpleGPModel):
+        raise TypeError("multistep_moments_diff_batch needs the HIP SimpleGPModel")
+    ssm._need_trained()
+    if not B.is_tensor(mu_0):
+        raise TypeError("multistep_moments_diff_batch needs tensors")
+    if k_ff.dim() != 3:
+        raise ValueError("k_ff must be (T, H, n_u)")
+    if k_ff.shape[1] > 1 and k_fb is None:
+        raise ValueError("k_fb is required for H > 1")
+    return _MultistepMomentsFn.apply(ssm, (a, b, mode, a_gp_inp_x), mu_0, sigma_0, k_ff, k_fb if k_ff.shape[1] > 1 else None)
 
 
 def _one_step(mu_x, ssm, k_ff, sigma_x, k_fb, a, b, a_gp_inp_x, mode):
