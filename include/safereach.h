@@ -533,6 +533,42 @@ int sr_safety_distance(int device, long T, int n_s, int m, const double* p, cons
                        const double* h_mat, const double* h_vec, double c_safety, double* d,
                        void* stream);
 
+/* replaces: utils_casadi.generic_cost with trig_aug as state transformation and loss_sat / loss_quadratic as stage and terminal
+ * cost  utils_casadi.py:178-395 (batched; the objective of the reference's journal experiments)
+ * sr_rollout_cost: the MPC objective over T stored moment trajectories of H states in ONE launch.  mu T x H x n_s, sigma
+ * T x H x n_s x n_s (read as (sigma + sigma^T) / 2; NULL = zero, the same bits as a zero array), u T x H x n_u (row H - 1 unread):
+ * the layouts of mu_all / sigma_all of sr_multistep_moments and sr_gp_moment_match_rollout, and of p_all / q_all of
+ * sr_multistep_reach.  Per state: the augmentation trig_aug(m, v, idx_angle, a_trig, keep_radian) -- [m; a E sin; a E cos] with the
+ * exact covariance, the angle's own row and column deleted unless keep_radian; idx_angle == -1: none -- to width n_c = n_s,
+ * n_s + 1 or n_s + 2, then the loss against the target z (n_c) under W = F F^T (F n_c x n_c, row-major; W symmetric PSD, may be
+ * singular; the caller factors it once):  loss 0, saturating: 1 - exp(-d^T W (I + S W)^-1 d / 2) / sqrt|I + S W|, d = m - z,
+ * computed from the Cholesky factor of I + F^T S F (SPD for any PSD S: nothing inverts S, W or I + S W) and with expm1 / log1p, so
+ * that a cost of 1e-9 at the target keeps its digits;  loss 1, quadratic: d^T W d + tr(W S).
+ *   cost_steps[t][i] = w_stage loss_i + u_i^T R u_i  (i < H - 1) ;  w_term loss_{H-1}  (i = H - 1)       (T x H, may be NULL)
+ *   cost[t] = the sum of cost_steps[t][:] in the order i = 0 .. H - 1                                     (T)
+ * R n_u x n_u (need not be symmetric) or NULL: no control term; u NULL iff R NULL.  The same bits on every call, with and without
+ * cost_steps, and whatever other trajectories are in the batch.  No model handle, no scratch.  Asynchronous on `stream`.
+ * Errors, before any launch: SR_EINVAL NULL where required, T < 0, H < 1, n_s < 1, idx_angle outside -1 .. n_s - 1, loss outside
+ * {0, 1}, R without u or u without R, keep_radian with idx_angle == -1; SR_EUNSUPPORTED n_s > 12 or n_u > 12; T == 0 is a no-op. */
+int sr_rollout_cost(int device, long T, int H, int n_s, int n_u, int idx_angle /* -1: none */, double a_trig,
+                    int keep_radian, int loss /* 0 sat, 1 quadratic */, const double* z, const double* F,
+                    double w_stage, double w_term, const double* R /* n_u x n_u | NULL */,
+                    const double* mu, const double* sigma /* | NULL */, const double* u /* | NULL iff R NULL */,
+                    double* cost, double* cost_steps /* | NULL */, void* stream);
+/* Its reverse pass in ONE launch: for the seed cost_bar (T; NULL = ones, the same bits as an array of ones) the gradient of
+ * sum_t cost_bar[t] cost[t] in the inputs:  mu_bar T x H x n_s ; sigma_bar T x H x n_s x n_s, exactly symmetric, also when sigma
+ * is NULL (the gradient of the function extended to unsymmetric arguments by sigma -> (sigma + sigma^T) / 2) ; u_bar T x H x n_u
+ * (row H - 1 exactly zero; all zero without R).  Each of the three may be NULL, not all three.  They are shaped like, and are, the
+ * seeds mu_all_bar / sigma_all_bar of sr_multistep_moments_vjp and sr_gp_moment_match_rollout_vjp and p_all_bar / q_all_bar of
+ * sr_multistep_reach_vjp: the gradient of the objective in k_ff, k_fb is a roll-out, this call and the roll-out's reverse pass.
+ * Closed form, no differences: with A = F B^-1 F^T, B = I + F^T S F, g = A d, q = 1 - loss the saturating loss has
+ * d loss / d m = q g and d loss / d S = q (A - g g^T) / 2; the quadratic 2 W d and W; then back through the augmentation.
+ * Inputs, determinism and refusals as sr_rollout_cost; SR_EINVAL also when every output is NULL.  Asynchronous on `stream`. */
+int sr_rollout_cost_vjp(int device, long T, int H, int n_s, int n_u, int idx_angle, double a_trig, int keep_radian, int loss,
+                        const double* z, const double* F, double w_stage, double w_term, const double* R,
+                        const double* mu, const double* sigma, const double* u, const double* cost_bar,
+                        double* mu_bar, double* sigma_bar, double* u_bar, void* stream);
+
 /* replaces: utils_ellipsoid.distance_to_center / sample_inside_ellipsoid  utils_ellipsoid.py:16-60 (batched;
  * the Monte-Carlo verification of sampling_models.py / gp_reachability.py:323-356 evaluates it per step)
  * T ellipsoids (p T x n_s, q T x n_s x n_s) against K samples: samples K x n_s shared by all ellipsoids

@@ -10,7 +10,7 @@ call fails loudly when no ROCm GPU is visible -- there is no CPU fallback.
 from . import _lib  # noqa: F401  (ImportError here == library not built)
 from .state_space_models import StateSpaceModel  # noqa: F401
 from .ssm_hip.gaussian_process import SimpleGPModel  # noqa: F401
-from . import gp_reachability, utils, utils_ellipsoid  # noqa: F401
+from . import gp_reachability, utils, utils_casadi, utils_ellipsoid  # noqa: F401
 
 
 
@@ -19,4 +19,4 @@ def release_cached_memory():
     _lib.check(_lib.lib.sr_release_cached_memory())
 
 
-__all__ = ["SimpleGPModel", "StateSpaceModel", "gp_reachability", "utils", "utils_ellipsoid", "release_cached_memory"]
+__all__ = ["SimpleGPModel", "StateSpaceModel", "gp_reachability", "utils", "utils_casadi", "utils_ellipsoid", "release_cached_memory"]

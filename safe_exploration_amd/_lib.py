@@ -87,6 +87,8 @@ SIGNATURES = {
     "sr_multistep_moments_vjp": (_I, [_H, _L, _I, _I] + [_P] * 16),
     "sr_remainder_overapprox": (_I, [_I, _L, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
     "sr_safety_distance": (_I, [_I, _L, _I, _I, _P, _P, _P, _P, _D, _P, _P]),
+    "sr_rollout_cost": (_I, [_I, _L, _I, _I, _I, _I, _D, _I, _I, _P, _P, _D, _D] + [_P] * 7),
+    "sr_rollout_cost_vjp": (_I, [_I, _L, _I, _I, _I, _I, _D, _I, _I, _P, _P, _D, _D] + [_P] * 9),
     "sr_distance_to_center": (_I, [_I, _L, _I, _I, _P, _I, _P, _P, _P, _P]),
     "sr_gp_mll": (_I, [_H, _P, _P, _P]),
     "sr_gp_logdet": (_I, [_H, _P, _P]),

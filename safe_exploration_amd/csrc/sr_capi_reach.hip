@@ -1,7 +1,7 @@
 // sr_capi_reach.hip -- reachability entry points: one-step and multi-step ellipsoid propagation (mode 0) and Gaussian moment
 // propagation (modes 1 / 2) through one forward step (ell_args, reach_step) and one driver each (onestep_impl, multistep_impl);
 // the reverse pass of one step of either through one driver (onestep_vjp_impl) and of a whole roll-out (sr_multistep_reach_vjp, mode 0; sr_multistep_moments_vjp, modes 1 / 2); exact moment matching, its reverse pass and
-// its roll-out in one launch; the stateless per-query steps (ellipsoid, moments, their reverse passes, remainder, safety distance, distance to centre, sampling);
+// its roll-out in one launch; the stateless per-query steps (ellipsoid, moments, their reverse passes, remainder, safety distance, the roll-out cost and its reverse pass, distance to centre, sampling);
 // and the dispatch of the persistent chain kernel (sr_chain.hip K0c) with its process-wide launch gate.
 #include "sr_handle.h"
 using namespace srh;
@@ -900,6 +900,53 @@ extern "C" int sr_safety_distance(int device, long T, int n_s, int m, const doub
     SR_CHECK(p && q && h_mat && h_vec && d, SR_EINVAL, "sr_safety_distance: NULL argument");
     SR_DEVICE(device);
     return sr_launch_safety(T, n_s, m, p, q, h_mat, h_vec, c_safety, d, (hipStream_t)stream);
+}
+
+// the arguments sr_rollout_cost and sr_rollout_cost_vjp share: checked, then packed; before any launch
+static int rollout_cost_args(const char* who, long T, int H, int n_s, int n_u, int idx_angle, double a_trig, int keep_radian, int loss,
+                             const double* z, const double* F, double w_stage, double w_term, const double* R, const double* mu,
+                             const double* sigma, const double* u, sr_cost_args& c) {
+    SR_CHECK(T >= 0 && H >= 1 && n_s >= 1 && n_u >= 0, SR_EINVAL, "%s: T=%ld H=%d n_s=%d n_u=%d", who, T, H, n_s, n_u);
+    SR_CHECK(idx_angle >= -1 && idx_angle < n_s, SR_EINVAL, "%s: idx_angle=%d outside -1 .. %d", who, idx_angle, n_s - 1);
+    SR_CHECK(loss == 0 || loss == 1, SR_EINVAL, "%s: loss=%d (0 saturating, 1 quadratic)", who, loss);
+    SR_CHECK(!(keep_radian && idx_angle < 0), SR_EINVAL, "%s: keep_radian without an angle", who);
+    SR_CHECK(z && F && mu, SR_EINVAL, "%s: NULL argument", who);
+    SR_CHECK(!R || (u && n_u >= 1), SR_EINVAL, "%s: R without u", who);
+    SR_CHECK(R || !u, SR_EINVAL, "%s: u without R", who);
+    SR_CHECK(n_s <= 12 && n_u <= 12, SR_EUNSUPPORTED, "%s: n_s=%d n_u=%d beyond 12", who, n_s, n_u);
+    c = sr_cost_args{};
+    c.T = T; c.H = H; c.n_s = n_s; c.n_u = n_u; c.idx = idx_angle; c.keep = keep_radian != 0; c.loss = loss;
+    c.n_c = idx_angle < 0 ? n_s : (keep_radian ? n_s + 2 : n_s + 1);
+    c.a_trig = a_trig; c.w_stage = w_stage; c.w_term = w_term;
+    c.z = z; c.F = F; c.R = R; c.mu = mu; c.sigma = sigma; c.u = u;
+    return SR_OK;
+}
+
+extern "C" int sr_rollout_cost(int device, long T, int H, int n_s, int n_u, int idx_angle, double a_trig, int keep_radian, int loss,
+                               const double* z, const double* F, double w_stage, double w_term, const double* R, const double* mu,
+                               const double* sigma, const double* u, double* cost, double* cost_steps, void* stream) {
+    sr_cost_args c;
+    SR_TRY(rollout_cost_args("sr_rollout_cost", T, H, n_s, n_u, idx_angle, a_trig, keep_radian, loss, z, F, w_stage, w_term, R, mu,
+                             sigma, u, c));
+    SR_CHECK(cost != nullptr, SR_EINVAL, "sr_rollout_cost: NULL argument");
+    if (T == 0) return SR_OK;
+    SR_DEVICE(device);
+    c.cost = cost; c.cost_steps = cost_steps;
+    return sr_launch_rollout_cost(c, false, (hipStream_t)stream);
+}
+
+extern "C" int sr_rollout_cost_vjp(int device, long T, int H, int n_s, int n_u, int idx_angle, double a_trig, int keep_radian, int loss,
+                                   const double* z, const double* F, double w_stage, double w_term, const double* R, const double* mu,
+                                   const double* sigma, const double* u, const double* cost_bar, double* mu_bar, double* sigma_bar,
+                                   double* u_bar, void* stream) {
+    sr_cost_args c;
+    SR_TRY(rollout_cost_args("sr_rollout_cost_vjp", T, H, n_s, n_u, idx_angle, a_trig, keep_radian, loss, z, F, w_stage, w_term, R,
+                             mu, sigma, u, c));
+    SR_CHECK(mu_bar || sigma_bar || u_bar, SR_EINVAL, "sr_rollout_cost_vjp: every output NULL");
+    if (T == 0) return SR_OK;
+    SR_DEVICE(device);
+    c.cost_bar = cost_bar; c.mu_bar = mu_bar; c.sigma_bar = sigma_bar; c.u_bar = u_bar;
+    return sr_launch_rollout_cost(c, true, (hipStream_t)stream);
 }
 
 extern "C" int sr_distance_to_center(int device, long T, int K, int n_s, const double* samples, int per_t,

@@ -779,6 +779,16 @@ int sr_launch_distance(long T, int K, int n_s, const double* samples, int per_t,
                        const double* q, double* d, hipStream_t s);
 int sr_launch_safety(long T, int n_s, int m, const double* p, const double* q, const double* h_mat,
                      const double* h_vec, double c, double* d, hipStream_t s);
+// the MPC objective over a stored moment trajectory and its reverse pass (sr_rollout_cost.hip): the arguments of sr_rollout_cost /
+// sr_rollout_cost_vjp; n_c the width of the augmented state (n_s, n_s + 1 or n_s + 2), G the trajectories per workgroup (set by the
+// launch)
+struct sr_cost_args {
+    long T; int H, n_s, n_u, idx, keep, loss, n_c, G;
+    double a_trig, w_stage, w_term;
+    const double *z, *F, *R, *mu, *sigma, *u, *cost_bar;
+    double *cost, *cost_steps, *mu_bar, *sigma_bar, *u_bar;
+};
+int sr_launch_rollout_cost(sr_cost_args a, bool reverse, hipStream_t s);
 
 // ---- fused small-batch posterior (sr_stream.hip) ------------------------------------------------------
 struct sr_lin_args;
