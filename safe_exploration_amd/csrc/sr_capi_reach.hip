@@ -1,9 +1,13 @@
-// sr_capi_reach.hip -- reachability entry points: one-step and multi-step ellipsoid propagation (mode 0) and Gaussian moment
-// propagation (modes 1 / 2) through one forward step (ell_args, reach_step) and one driver each (onestep_impl, multistep_impl);
-// the reverse pass of one step of either through one driver (onestep_vjp_impl) and of a whole roll-out (sr_multistep_reach_vjp, mode 0; sr_multistep_moments_vjp, modes 1 / 2); exact moment matching, its reverse pass and
-// its roll-out in one launch; the stateless per-query steps (ellipsoid, moments, their reverse passes, remainder, safety distance, the roll-out cost and its reverse pass, distance to centre, sampling);
-// and the dispatch of the persistent chain kernel (sr_chain.hip K0c) with its process-wide launch gate.
+// sr_capi_reach.hip -- the reachability and moment-propagation entry points.
+// Forward, with the GP inside: one step and H steps of ellipsoid propagation (mode 0) and of Gaussian moment propagation
+// (modes 1 / 2).  Both go through one step function (ell_args, reach_step) and one driver each (onestep_impl, multistep_impl);
+// a multi-step call tries the persistent chain kernel first (try_chain, sr_capi_chain.hip).
+// Reverse, with the GP inside: one step through onestep_vjp_impl, a whole roll-out through rollout_vjp_impl, in all three
+// modes.  Their scratch is the handle's reach_ws, laid out by sr_reach_ws.h.
+// Stateless, per query: the ellipsoid and moment steps and their reverse passes, the remainder, the safety distance, the
+// roll-out cost and its reverse pass, the distance to the centre, and sampling.
 #include "sr_handle.h"
+#include "sr_reach_ws.h"
 using namespace srh;
 
 static int check_reach_dims(const sr_gp* h, int* n_s, int* n_u) {
@@ -16,14 +20,15 @@ static int check_reach_dims(const sr_gp* h, int* n_s, int* n_u) {
     return SR_OK;
 }
 
-static int try_chain(sr_gp* h, long T, int H, int mode, const double* p0, const double* q0, const double* k_fb0,
-                     const double* k_ff, const double* k_fb, const double* a, const double* b, const double* l_mu,
-                     const double* l_sigma, double c_safety, double* p_all, double* q_all, double* gp_var_all,
-                     int* n_bad, int n_s, int n_u, hipStream_t s, bool* taken);
+// the reverse passes go through sr_gp_linearize_batch: the widths it is compiled for
+static int check_linearize_width(const sr_gp* h, const char* who) {
+    SR_CHECK(h->D <= 8, SR_EUNSUPPORTED, "%s: D=%d > 8 (the batched linearisation behind it)", who, h->D);
+    return SR_OK;
+}
 
 // The one place that fills sr_ell_args: T rows of the step's inputs and outputs with their row strides, the constants and the mode.
-// The moment modes read neither l_mu, l_sigma nor c_safety: any valid device pointer will do.  mu, var and jac (dense) are the
-// caller's, or reach_step's.
+// The moment modes read neither l_mu, l_sigma nor c_safety and pass NULL: any valid device pointer will do.  mu, var and jac
+// (dense) are the caller's, or reach_step's.
 static sr_ell_args ell_args(long T, int n_s, int n_u, int mode, const double* p, long ldp, const double* q, long ldq,
                             const double* k_ff, long ldkff, const double* k_fb, long ldkfb, const double* a, const double* b,
                             const double* l_mu, const double* l_sigma, double c_safety, double* p_out, long ldpo,
@@ -99,8 +104,7 @@ extern "C" int sr_onestep_reach(sr_gp_t h, long T, const double* p, const double
                                 const double* b, const double* l_mu, const double* l_sigma,
                                 double c_safety, double* p_out, double* q_out, double* var_out,
                                 int* n_bad, void* stream) {
-    SR_CHECK(h != nullptr, SR_EINVAL, "sr_onestep_reach: NULL handle");
-    SR_CHECK(h->factorized, SR_ESTATE, "sr_onestep_reach: model not factorized");
+    SR_TRY(handle_ready(h, "sr_onestep_reach"));
     SR_CHECK(T >= 0, SR_EINVAL, "sr_onestep_reach: T=%ld", T);
     if (T == 0) return SR_OK;
     SR_CHECK(p && k_ff && a && b && l_mu && l_sigma && p_out && q_out, SR_EINVAL,
@@ -115,164 +119,13 @@ extern "C" int sr_onestep_reach(sr_gp_t h, long T, const double* p, const double
 extern "C" int sr_onestep_moments(sr_gp_t h, long T, int mode, const double* mu_x, const double* sigma_x, const double* k_ff,
                                   const double* k_fb, const double* a, const double* b, double* mu_out, double* sigma_out,
                                   double* var_out, void* stream) {
-    SR_CHECK(h != nullptr, SR_EINVAL, "sr_onestep_moments: NULL handle");
-    SR_CHECK(h->factorized, SR_ESTATE, "sr_onestep_moments: model not factorized");
+    SR_TRY(handle_ready(h, "sr_onestep_moments"));
     SR_CHECK(T >= 0 && (mode == 1 || mode == 2), SR_EINVAL, "sr_onestep_moments: T=%ld mode=%d", T, mode);
     if (T == 0) return SR_OK;
     SR_CHECK(mu_x && k_ff && a && b && mu_out && sigma_out, SR_EINVAL, "sr_onestep_moments: NULL argument");
     SR_CHECK(sigma_x == nullptr || k_fb != nullptr, SR_EINVAL, "sr_onestep_moments: k_fb required with sigma_x");
     return onestep_impl(h, T, mode, mu_x, sigma_x, k_ff, k_fb, a, b, nullptr, nullptr, 1.0, mu_out, sigma_out, var_out,
                         nullptr, (hipStream_t)stream);
-}
-
-// Persistent chain launches of one device never overlap, whichever handle or stream they come from: each needs (almost)
-// every CU resident at once, two of them side by side would wait for each other's workgroups until the time-out.  Every
-// launch waits for the event the previous one recorded (per device, process-wide) and records its own.  Not while the
-// caller's stream is being captured into a graph (a cross-stream wait on an uncaptured event is not capturable): a
-// captured chain is ordered by its graph.
-struct sr_chain_gate { std::mutex m; hipEvent_t ev[32] = {}; hipStream_t last[32] = {}; bool any[32] = {}; };
-static sr_chain_gate g_chain_gate;
-struct sr_chain_turn {                 // holds the gate from the wait to the record: host threads take turns too
-    int device; hipStream_t s; bool active = false;
-    sr_chain_turn(int device_, hipStream_t s_) : device(device_), s(s_) {}
-    int enter() {
-        hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-        const hipError_t ce = hipStreamIsCapturing(s, &st);
-        const bool capturing = (ce == hipSuccess && st != hipStreamCaptureStatusNone);
-        if (capturing || device < 0 || device >= 32) return SR_OK;
-        g_chain_gate.m.lock();
-        active = true;
-        // (the previous launch on the SAME stream is ordered by the stream itself)
-        if (g_chain_gate.ev[device] && !(g_chain_gate.any[device] && g_chain_gate.last[device] == s))
-            SR_HIP(hipStreamWaitEvent(s, g_chain_gate.ev[device], 0));
-        return SR_OK;
-    }
-    int leave() {
-        if (!active) return SR_OK;
-        if (!g_chain_gate.ev[device]) SR_HIP(hipEventCreateWithFlags(&g_chain_gate.ev[device], hipEventDisableTiming));
-        SR_HIP(hipEventRecord(g_chain_gate.ev[device], s));
-        g_chain_gate.last[device] = s; g_chain_gate.any[device] = true;
-        return SR_OK;
-    }
-    ~sr_chain_turn() { if (active) g_chain_gate.m.unlock(); }
-};
-
-// The persistent kernel of sr_chain.hip (K0c) for a chain of H >= 1 steps, where it applies; *taken says whether it ran.
-static int try_chain(sr_gp* h, long T, int H, int mode, const double* p0, const double* q0, const double* k_fb0,
-                     const double* k_ff, const double* k_fb, const double* a, const double* b, const double* l_mu,
-                     const double* l_sigma, double c_safety, double* p_all, double* q_all, double* gp_var_all,
-                     int* n_bad, int n_s, int n_u, hipStream_t s, bool* taken) {
-    *taken = false;
-    const long nss = (long)n_s * n_s, nus = (long)n_u * n_s;
-    // small model, few rollouts: the whole chain in one launch (sr_chain.hip K0c).  One launch holds SR_CHAIN_GROUPS
-    // workgroups = gmax groups of 16 rollouts (n_s Np / 128 posterior workgroups + the tail workgroup each): 768 rollouts
-    // of a pendulum model with N <= 256, 416 of a cart-pole model.  Measured at N = 200, H = 15: 256 rollouts 246
-    // (per-step launches) -> 102 us.
-    // every workgroup of a launch must be resident (one per CU): leave 16 CUs of whatever this device (or partition of
-    // a device) has to other work
-    if (h->chain_cap < 0) {
-        int cus = 0;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess) cus = 0;
-        h->chain_cap = std::max(0, std::min(SR_CHAIN_GROUPS, cus - 16));
-    }
-    const int wpg = sr_chain_wgs_per_group(h->Np, n_s);                 // posterior workgroups + the tail workgroup
-    if (h->chain_cap < wpg) return SR_OK;                               // not even one group fits: per-step launches
-    // A chain launch whose hand-off timed out (SR_CHAIN_TIMEOUT_TICKS: its workgroups were not co-resident in time) has
-    // poisoned its outputs with NaN and raised the pinned status word.  The first entry after that reports it -- a
-    // caller that never looked at the outputs must not go on with them -- and the handle takes the per-step launches
-    // from here on (sr_gp_set_chain(h, 1) re-arms the persistent kernel).
-    if (h->chain_status_host && *(volatile int*)h->chain_status_host != 0) {
-        *(volatile int*)h->chain_status_host = 0;
-        h->chain = 0;
-        sr_set_error("a previous persistent multi-step launch timed out (its workgroups did not become co-resident within "
-                     "100 ms); its outputs were filled with NaN.  The handle now uses per-step launches; repeat the call.");
-        return SR_ESTATE;
-    }
-    const long xpg = std::max(1l, sr_chain_xels_per_group(h->Np, n_s, n_u, H));
-    const int gmax = (int)std::max(1l, std::min((long)(h->chain_cap / wpg), (long)SR_CHAIN_XELS / xpg));   // groups of 16 rollouts per launch
-    const long chain_launches = ((T + SR_SMALL_T - 1) / SR_SMALL_T + gmax - 1) / gmax;
-    // Several launches in a row still beat the per-step route (N = 200, H = 15: 1024 rollouts 203 against 253 us, 4096
-    // rollouts in six launches 608 against 722 us; cart-pole N = 150: 832 rollouts 304 against 411 us) -- except where
-    // the per-step route still has its one-launch posterior (T <= SR_FUSED_T) and three launches are needed (cart-pole,
-    // 960 rollouts: 454 against 413 us).
-    // (one or two steps: a second launch costs what the per-step route's two launches per step cost -- N = 200, H = 1,
-    //  960 rollouts: 29 against 24 us)
-    const long chain_max_launches = sr_chain_max_launches(T, H);
-    if (h->chain && h->small_path == 1 && !h->force_stream && !h->general && h->n_xin == 0 &&
-        chain_launches <= chain_max_launches &&
-        sr_chain_supported(h->Np, h->D, n_s, n_u, H)) {
-        // the kernel must be able to run at all: at least one workgroup per CU (registers, static + dynamic LDS)
-        const int occ_key = ((h->Np * 8 + n_s) * 8 + n_u) * 128 + std::min(H, 127);      // (H sizes the dynamic LDS; sr_chain_supported bounds it at 96)
-        if (h->chain_occ_key != occ_key) {
-            h->chain_occ_blocks = 0;
-            SR_TRY(sr_chain_blocks_per_cu(h->Np, n_s, n_u, H, &h->chain_occ_blocks));
-            h->chain_occ_key = occ_key;
-        }
-        if (h->chain_occ_blocks < 1) return SR_OK;                       // per-step launches
-        if (!h->chain_xch) {
-            // all or nothing: the pointers are committed to the handle only once every allocation and memset is in place
-            // (a launch with one of them missing would run on NULL epoch / alive / done words)
-            int* st_host = h->chain_status_host; int* st_dev = h->chain_status_dev;
-            sr_xel* xch = nullptr; unsigned long long* tickets = nullptr; unsigned* done = nullptr;
-            int rc = SR_OK;
-            hipError_t he = hipSuccess;
-            if (!st_host) {
-                he = hipHostMalloc((void**)&st_host, sizeof(int), hipHostMallocMapped);
-                if (he == hipSuccess) { *st_host = 0; he = hipHostGetDevicePointer((void**)&st_dev, st_host, 0); }
-            }
-            if (he == hipSuccess) rc = dev_alloc(&xch, (size_t)SR_CHAIN_XELS);
-            if (he == hipSuccess && rc == SR_OK) rc = dev_alloc(&tickets, (size_t)2 * SR_CHAIN_GROUPS);
-            if (he == hipSuccess && rc == SR_OK) rc = dev_alloc(&done, (size_t)SR_CHAIN_GROUPS);
-            // ON THE CALLER'S STREAM: a memset on the null stream is not ordered with a launch on a non-blocking stream --
-            // it wiped tags the first launch had already written (41 MB take 20 us) and that launch timed out
-            if (he == hipSuccess && rc == SR_OK) he = hipMemsetAsync(xch, 0, sizeof(sr_xel) * (size_t)SR_CHAIN_XELS, s);     // tag 0 = never written
-            if (he == hipSuccess && rc == SR_OK) he = hipMemsetAsync(tickets, 0, sizeof(unsigned long long) * 2 * SR_CHAIN_GROUPS, s);
-            if (he == hipSuccess && rc == SR_OK) he = hipMemsetAsync(done, 0, sizeof(unsigned) * SR_CHAIN_GROUPS, s);
-            if (he != hipSuccess || rc != SR_OK) {
-                if (he != hipSuccess) {
-                    (void)hipStreamSynchronize(s);
-                    sr_set_error("persistent chain: setting up the exchange buffers -> %s", hipGetErrorString(he));
-                    (void)hipGetLastError();
-                    rc = SR_EHIP;
-                }
-                dev_free(xch); dev_free(tickets); dev_free(done);
-                if (st_host && !h->chain_status_host) (void)hipHostFree(st_host);
-                return rc;
-            }
-            h->chain_status_host = st_host; h->chain_status_dev = st_dev;
-            h->chain_xch = xch; h->chain_tickets = tickets; h->chain_done = done;
-        }
-        // every workgroup of a chain launch must be resident at once: resident single-query servers (up to n_out Np / 64 CUs
-        // each) leave the device first; they come back with their next query
-        servers_quiesce_device(h->device);
-        sr_prof_scope ps(&h->prof, SR_K_SMALL, s);
-        for (long t0 = 0; t0 < T; t0 += (long)gmax * SR_SMALL_T) {
-            const long Tc = std::min((long)gmax * SR_SMALL_T, T - t0);
-            const int groups = (int)((Tc + SR_SMALL_T - 1) / SR_SMALL_T);
-            sr_chain_args ca{};
-            model_args(ca.k, h);
-            ca.k.na = n_s; ca.k.nb = n_u;
-            ca.Wt = h->Wt; ca.T = Tc; ca.H = H; ca.mode = mode;
-            ca.p0 = p0 + t0 * n_s; ca.q0 = q0 ? q0 + t0 * nss : nullptr; ca.k_fb0 = k_fb0 ? k_fb0 + t0 * nus : nullptr;
-            ca.k_ff = k_ff + t0 * H * n_u; ca.k_fb = k_fb ? k_fb + t0 * (H - 1) * nus : nullptr;
-            ca.a = a; ca.b = b; ca.l_mu = l_mu; ca.l_sigma = l_sigma; ca.c_safety = c_safety;
-            ca.p_all = p_all + t0 * H * n_s; ca.q_all = q_all + t0 * H * nss;
-            ca.gp_var_all = gp_var_all ? gp_var_all + t0 * H * n_s : nullptr;
-            ca.n_bad = n_bad; ca.xch = h->chain_xch;
-            ca.epoch = h->chain_tickets; ca.alive = h->chain_tickets + SR_CHAIN_GROUPS; ca.done = h->chain_done;
-            ca.status = h->chain_status_dev;
-            ca.test_drop = h->chain_test_drop;
-            sr_chain_turn turn(h->device, s);
-            SR_TRY(turn.enter());
-            SR_TRY(sr_launch_chain(ca, s));
-            SR_TRY(turn.leave());
-            (void)groups;
-        }
-        h->last_chain = 1;
-        *taken = true;
-        return SR_OK;
-    }
-    return SR_OK;
 }
 
 // shared H-step chain: mode 0 = robust ellipsoids (gp_reachability.py:159-212),
@@ -316,8 +169,7 @@ extern "C" int sr_multistep_reach(sr_gp_t h, long T, int H, const double* p0, co
                                   const double* a, const double* b, const double* l_mu,
                                   const double* l_sigma, double c_safety, double* p_all,
                                   double* q_all, int* n_bad, void* stream) {
-    SR_CHECK(h != nullptr, SR_EINVAL, "sr_multistep_reach: NULL handle");
-    SR_CHECK(h->factorized, SR_ESTATE, "sr_multistep_reach: model not factorized");
+    SR_TRY(handle_ready(h, "sr_multistep_reach"));
     SR_CHECK(T >= 0 && H >= 1, SR_EINVAL, "sr_multistep_reach: T=%ld H=%d", T, H);
     if (T == 0) return SR_OK;
     SR_CHECK(p0 && k_ff && a && b && l_mu && l_sigma && p_all && q_all, SR_EINVAL,
@@ -331,204 +183,14 @@ extern "C" int sr_multistep_reach(sr_gp_t h, long T, int H, const double* p0, co
 extern "C" int sr_multistep_moments(sr_gp_t h, long T, int H, int mode, const double* mu0, const double* k_ff,
                                     const double* k_fb, const double* a, const double* b, double* mu_all,
                                     double* sigma_all, double* gp_var_all, void* stream) {
-    SR_CHECK(h != nullptr, SR_EINVAL, "sr_multistep_moments: NULL handle");
-    SR_CHECK(h->factorized, SR_ESTATE, "sr_multistep_moments: model not factorized");
+    SR_TRY(handle_ready(h, "sr_multistep_moments"));
     SR_CHECK(T >= 0 && H >= 1 && (mode == 1 || mode == 2), SR_EINVAL, "sr_multistep_moments: T=%ld H=%d mode=%d",
              T, H, mode);
     if (T == 0) return SR_OK;
     SR_CHECK(mu0 && k_ff && a && b && mu_all && sigma_all, SR_EINVAL, "sr_multistep_moments: NULL argument");
     SR_CHECK(H == 1 || k_fb != nullptr, SR_EINVAL, "sr_multistep_moments: k_fb required for H > 1");
-    // l_mu / l_sigma are unused by the moment modes: any valid device pointer will do
-    return multistep_impl(h, T, H, mode, mu0, nullptr, nullptr, k_ff, k_fb, a, b, a, a, 1.0, mu_all, sigma_all,
+    return multistep_impl(h, T, H, mode, mu0, nullptr, nullptr, k_ff, k_fb, a, b, nullptr, nullptr, 1.0, mu_all, sigma_all,
                           gp_var_all, nullptr, (hipStream_t)stream);
-}
-
-// the general family with the RBF radial part (sr_moment_match_gen.hip): the scratch holds the per-call block (Kinv Z,
-// Z^T Kinv Z, Z^T alpha of every output) in front of the chunk's records
-static int moment_match_general(sr_gp_t h, const double* m, const double* S, long T, const double* inv_k, double* mu,
-                                double* cov, double* V, hipStream_t s) {
-    const long per = sr_mmx_ws_per_query(h->N, h->D, h->n_out), head = sr_mmx_call_ws(h->N, h->D, h->n_out);
-    const long chunk = std::max(1L, std::min({h->chunk, sr_mmx_max_queries(h->N, h->n_out), ((long)1 << 28) / per}));
-    const long DD = (long)h->D * h->D, nn = (long)h->n_out * h->n_out;
-    SR_TRY(h->mm_ws.grow((size_t)(head + std::min(chunk, T) * per), wait::stream(s)));
-    double* call = h->mm_ws.get();
-    SR_TRY(sr_launch_moment_match_gen_call(h->Z, h->alpha, h->kp, h->N, h->Np, h->D, h->n_out, inv_k, call, s));
-    for (long t0 = 0; t0 < T; t0 += chunk) {
-        const long Tc = std::min(chunk, T - t0);
-        SR_TRY(sr_launch_moment_match_gen(h->Z, h->alpha, h->kp, h->N, h->Np, h->D, h->n_out, m + t0 * h->D,
-                                          S ? S + t0 * DD : nullptr, Tc, inv_k, mu + t0 * h->n_out, cov + t0 * nn,
-                                          V ? V + t0 * h->n_out * h->D : nullptr, call, call + head, s));
-    }
-    return SR_OK;
-}
-
-// exact moment matching (sr_moment_match.hip; sr_moment_match_gen.hip for a general-family handle whose outputs all have the
-// RBF radial part).  Reads the model where the handle holds it (alpha may be a slid view: single
-// doubles are loaded, no unslide()); writes nothing into the handle but the grow-only scratch.
-extern "C" int sr_gp_moment_match(sr_gp_t h, const double* m, const double* S, long T, const double* inv_k, double* mu,
-                                  double* cov, double* V, void* stream) {
-    SR_CHECK(h != nullptr, SR_EINVAL, "sr_gp_moment_match: NULL handle");
-    SR_CHECK(h->factorized, SR_ESTATE, "sr_gp_moment_match: model not factorized");
-    hipStream_t s = (hipStream_t)stream;
-    if (h->general) {
-        SR_DEVICE(h->device);
-        SR_TRY(general_info(h, s));
-        if (!h->gen_rbf) {
-            sr_set_error("sr_gp_moment_match: the closed form is for ARD-RBF models and the general family with the RBF "
-                         "radial part only (a Matern output has none)");
-            return SR_EUNSUPPORTED;
-        }
-    }
-    SR_CHECK(T >= 0, SR_EINVAL, "sr_gp_moment_match: T=%ld", T);
-    if (T == 0) return SR_OK;
-    SR_CHECK(m && inv_k && mu && cov, SR_EINVAL, "sr_gp_moment_match: NULL argument");
-    SR_DEVICE(h->device);
-    if (h->general) return moment_match_general(h, m, S, T, inv_k, mu, cov, V, s);
-    const long per = sr_mm_ws_per_query(h->N, h->D, h->n_out);
-    // a chunk: the handle's, what the launch grid takes, and at most 2^28 doubles (2 GB) of scratch
-    const long chunk = std::max(1L, std::min({h->chunk, sr_mm_max_queries(h->N, h->n_out), ((long)1 << 28) / per}));
-    const long DD = (long)h->D * h->D, nn = (long)h->n_out * h->n_out;
-    SR_TRY(h->mm_ws.grow((size_t)(std::min(chunk, T) * per), wait::stream(s)));
-    for (long t0 = 0; t0 < T; t0 += chunk) {
-        const long Tc = std::min(chunk, T - t0);
-        SR_TRY(sr_launch_moment_match(h->Z, h->alpha, h->ls, h->sf2, h->N, h->Np, h->D, h->n_out, m + t0 * h->D,
-                                      S ? S + t0 * DD : nullptr, Tc, inv_k, mu + t0 * h->n_out, cov + t0 * nn,
-                                      V ? V + t0 * h->n_out * h->D : nullptr, h->mm_ws.get(), s));
-    }
-    return SR_OK;
-}
-
-// the reverse pass of sr_gp_moment_match: the same refusals in the same order, the same scratch (its own per-query size)
-extern "C" int sr_gp_moment_match_vjp(sr_gp_t h, const double* m, const double* S, long T, const double* inv_k,
-                                      const double* mu_bar, const double* cov_bar, const double* V_bar, double* m_bar,
-                                      double* S_bar, void* stream) {
-    SR_CHECK(h != nullptr, SR_EINVAL, "sr_gp_moment_match_vjp: NULL handle");
-    SR_CHECK(h->factorized, SR_ESTATE, "sr_gp_moment_match_vjp: model not factorized");
-    if (h->general) {
-        sr_set_error("sr_gp_moment_match_vjp: the reverse pass is for ARD-RBF models only (data set with sr_gp_set_data)");
-        return SR_EUNSUPPORTED;
-    }
-    SR_CHECK(T >= 0, SR_EINVAL, "sr_gp_moment_match_vjp: T=%ld", T);
-    if (T == 0) return SR_OK;
-    SR_CHECK(m && inv_k && (m_bar || S_bar), SR_EINVAL, "sr_gp_moment_match_vjp: NULL argument");
-    hipStream_t s = (hipStream_t)stream;
-    SR_DEVICE(h->device);
-    const long per = sr_mmg_ws_per_query(h->N, h->D, h->n_out);
-    const long chunk = std::max(1L, std::min({h->chunk, sr_mmg_max_queries(h->N, h->n_out), ((long)1 << 28) / per}));
-    const long Dl = h->D, DD = Dl * Dl, n = h->n_out;
-    SR_TRY(h->mm_ws.grow((size_t)(std::min(chunk, T) * per), wait::stream(s)));
-    for (long t0 = 0; t0 < T; t0 += chunk) {
-        const long Tc = std::min(chunk, T - t0);
-        SR_TRY(sr_launch_moment_match_vjp(h->Z, h->alpha, h->ls, h->sf2, h->N, h->Np, h->D, h->n_out, m + t0 * Dl,
-                                          S ? S + t0 * DD : nullptr, Tc, inv_k, mu_bar ? mu_bar + t0 * n : nullptr,
-                                          cov_bar ? cov_bar + t0 * n * n : nullptr, V_bar ? V_bar + t0 * n * Dl : nullptr,
-                                          m_bar ? m_bar + t0 * Dl : nullptr, S_bar ? S_bar + t0 * DD : nullptr,
-                                          h->mm_ws.get(), s));
-    }
-    return SR_OK;
-}
-
-// T trajectories through H closed-loop steps of exact moment matching in one launch per chunk (sr_moment_match_rollout.hip).
-// Every refusal comes before the first launch; the scratch holds one step's records per trajectory of a chunk.  A workgroup
-// owns a trajectory, so the chunk decides nothing but the size of the scratch.
-extern "C" int sr_gp_moment_match_rollout(sr_gp_t h, long T, int H, int n_x_in, int gains_per_traj, const double* mu0,
-                                          const double* sigma0, const double* k_ff, const double* k_fb, const double* a,
-                                          const double* b, const double* tz, const double* inv_k, double* mu_all,
-                                          double* sigma_all, double* cov_all, void* stream) {
-    const char* who = "sr_gp_moment_match_rollout";
-    SR_CHECK(h != nullptr, SR_EINVAL, "%s: NULL handle", who);
-    SR_CHECK(h->factorized, SR_ESTATE, "%s: model not factorized", who);
-    SR_CHECK(!h->general, SR_EUNSUPPORTED, "%s: ARD-RBF models only (data set with sr_gp_set_data): use the per-step route", who);
-    SR_CHECK(h->N <= 1024, SR_EUNSUPPORTED, "%s: N=%d > 1024: use the per-step route", who, h->N);
-    SR_CHECK(h->D <= 12, SR_EUNSUPPORTED, "%s: D=%d > 12: use the per-step route", who, h->D);
-    SR_CHECK(T >= 0 && H >= 1 && (gains_per_traj == 0 || gains_per_traj == 1), SR_EINVAL, "%s: T=%ld H=%d gains_per_traj=%d",
-             who, T, H, gains_per_traj);
-    SR_CHECK(n_x_in >= 1 && n_x_in <= h->D - 1, SR_EINVAL, "%s: n_x_in=%d outside 1 .. D - 1 (D=%d)", who, n_x_in, h->D);
-    SR_CHECK(tz != nullptr || n_x_in == h->n_out, SR_EINVAL, "%s: tz NULL needs n_x_in == n_out (%d, %d)", who, n_x_in,
-             h->n_out);
-    if (T == 0) return SR_OK;
-    SR_CHECK(mu0 && k_ff && a && b && inv_k && mu_all && sigma_all && (k_fb || H == 1), SR_EINVAL, "%s: NULL argument", who);
-    hipStream_t s = (hipStream_t)stream;
-    SR_DEVICE(h->device);
-    const long per = sr_mmr_ws_per_traj(h->D, h->n_out);
-    const long chunk = std::max(1L, std::min({h->chunk, 0x7fffffffL, ((long)1 << 28) / per}));
-    SR_TRY(h->mm_ws.grow((size_t)(std::min(chunk, T) * per), wait::stream(s)));
-    const long n = h->n_out, n_u = h->D - n_x_in;
-    sr_mmr_args r;
-    r.Z = h->Z; r.alpha = h->alpha; r.ls = h->ls; r.sf2 = h->sf2; r.inv_k = inv_k; r.a = a; r.b = b; r.tz = tz;
-    r.ws = h->mm_ws.get();
-    r.N = h->N; r.Np = h->Np; r.D = h->D; r.n_out = h->n_out; r.n_x_in = n_x_in; r.H = H; r.gains_per_traj = gains_per_traj;
-    for (long t0 = 0; t0 < T; t0 += chunk) {
-        r.T = std::min(chunk, T - t0);
-        r.mu0 = mu0 + t0 * n;
-        r.sigma0 = sigma0 ? sigma0 + t0 * n * n : nullptr;
-        r.k_ff = k_ff + (gains_per_traj ? t0 * H * n_u : 0);
-        r.k_fb = k_fb ? k_fb + (gains_per_traj ? t0 * (H - 1) * n_u * n : 0) : nullptr;
-        r.mu_all = mu_all + t0 * H * n;
-        r.sigma_all = sigma_all + t0 * H * n * n;
-        r.cov_all = cov_all ? cov_all + t0 * H * n * n : nullptr;
-        SR_TRY(sr_launch_moment_match_rollout(r, s));
-    }
-    return SR_OK;
-}
-
-// The reverse pass of that roll-out (sr_moment_match_rollout_vjp.hip) at the states a forward stored.  Its domain is that of
-// sr_gp_moment_match_vjp (any N), not of the fused forward.  Every refusal comes before the first launch.  Trajectories go in
-// groups of max(1, min(chunk, sr_mmg_max_queries) / H): a trajectory's results depend on nothing but its own rows, so the
-// group size decides the size of the scratch and how full the one-off pass runs, not a bit of the results.
-extern "C" int sr_gp_moment_match_rollout_vjp(sr_gp_t h, long T, int H, int n_x_in, int gains_per_traj, const double* mu0,
-                                              const double* sigma0, const double* k_ff, const double* k_fb, const double* a,
-                                              const double* b, const double* tz, const double* inv_k, const double* mu_all,
-                                              const double* sigma_all, const double* mu_all_bar, const double* sigma_all_bar,
-                                              const double* cov_all_bar, double* mu0_bar, double* sigma0_bar, double* kff_bar,
-                                              double* kfb_bar, void* stream) {
-    const char* who = "sr_gp_moment_match_rollout_vjp";
-    SR_CHECK(h != nullptr, SR_EINVAL, "%s: NULL handle", who);
-    SR_CHECK(h->factorized, SR_ESTATE, "%s: model not factorized", who);
-    SR_CHECK(!h->general, SR_EUNSUPPORTED, "%s: the reverse pass is for ARD-RBF models only (data set with sr_gp_set_data)", who);
-    SR_CHECK(h->D <= SR_MAX_D, SR_EUNSUPPORTED, "%s: D=%d > %d", who, h->D, SR_MAX_D);
-    SR_CHECK(h->n_out <= SR_MMRV_MAX_NS, SR_EUNSUPPORTED, "%s: n_s=%d > %d (the sweep kernel's matrices in LDS)", who, h->n_out,
-             SR_MMRV_MAX_NS);
-    SR_CHECK(T >= 0 && H >= 1 && (gains_per_traj == 0 || gains_per_traj == 1), SR_EINVAL, "%s: T=%ld H=%d gains_per_traj=%d",
-             who, T, H, gains_per_traj);
-    SR_CHECK(n_x_in >= 1 && n_x_in <= h->D - 1, SR_EINVAL, "%s: n_x_in=%d outside 1 .. D - 1 (D=%d)", who, n_x_in, h->D);
-    SR_CHECK(tz != nullptr || n_x_in == h->n_out, SR_EINVAL, "%s: tz NULL needs n_x_in == n_out (%d, %d)", who, n_x_in,
-             h->n_out);
-    SR_CHECK(H <= sr_mmg_max_queries(h->N, h->n_out), SR_EUNSUPPORTED, "%s: H=%d steps of N=%d, n_out=%d outside the launch grid",
-             who, H, h->N, h->n_out);
-    if (T == 0) return SR_OK;
-    SR_CHECK(mu0 && k_ff && a && b && inv_k && mu_all && sigma_all && mu0_bar && kff_bar && (H == 1 || (k_fb && kfb_bar)),
-             SR_EINVAL, "%s: NULL argument", who);
-    SR_CHECK(sigma0 == nullptr || sigma0_bar != nullptr, SR_EINVAL, "%s: sigma0 without sigma0_bar", who);
-    SR_CHECK(mu_all_bar || sigma_all_bar || cov_all_bar, SR_EINVAL, "%s: all seeds NULL", who);
-    hipStream_t s = (hipStream_t)stream;
-    SR_DEVICE(h->device);
-    const long per = sr_mmrv_ws_per_traj(h->N, h->D, h->n_out, H);
-    const long queries = std::max(1L, std::min(h->chunk, sr_mmg_max_queries(h->N, h->n_out)));
-    const long group = std::max(1L, std::min(queries / H, ((long)1 << 28) / per));
-    SR_TRY(h->mm_ws.grow((size_t)(std::min(group, T) * per), wait::stream(s)));
-    const long n = h->n_out, n_u = h->D - n_x_in;
-    sr_mmrv_args r{};
-    r.Z = h->Z; r.alpha = h->alpha; r.ls = h->ls; r.sf2 = h->sf2; r.inv_k = inv_k; r.a = a; r.b = b; r.tz = tz;
-    r.N = h->N; r.Np = h->Np; r.D = h->D; r.n_s = h->n_out; r.n_x_in = n_x_in; r.H = H; r.gains_per_traj = gains_per_traj;
-    for (long t0 = 0; t0 < T; t0 += group) {
-        r.Tg = std::min(group, T - t0);
-        r.mu0 = mu0 + t0 * n;
-        r.sigma0 = sigma0 ? sigma0 + t0 * n * n : nullptr;
-        r.k_ff = k_ff + (gains_per_traj ? t0 * H * n_u : 0);
-        r.k_fb = k_fb ? k_fb + (gains_per_traj ? t0 * (H - 1) * n_u * n : 0) : nullptr;
-        r.mu_all = mu_all + t0 * H * n;
-        r.sigma_all = sigma_all + t0 * H * n * n;
-        r.mu_all_bar = mu_all_bar ? mu_all_bar + t0 * H * n : nullptr;
-        r.sigma_all_bar = sigma_all_bar ? sigma_all_bar + t0 * H * n * n : nullptr;
-        r.cov_all_bar = cov_all_bar ? cov_all_bar + t0 * H * n * n : nullptr;
-        r.mu0_bar = mu0_bar + t0 * n;
-        r.sigma0_bar = sigma0 ? sigma0_bar + t0 * n * n : nullptr;
-        r.kff_bar = kff_bar + t0 * H * n_u;
-        r.kfb_bar = H > 1 ? kfb_bar + t0 * (H - 1) * n_u * n : nullptr;
-        SR_TRY(sr_launch_moment_match_rollout_vjp(r, h->mm_ws.get(), s));
-    }
-    return SR_OK;
 }
 
 extern "C" int sr_moment_step(int device, long T, int n_s, int n_u, int mode, const double* mu_x,
@@ -589,11 +251,6 @@ extern "C" int sr_ellipsoid_step_vjp(int device, long T, int n_s, int n_u, const
     return sr_launch_reach_vjp(ea, n_s, n_u, (hipStream_t)stream);
 }
 
-// doubles of reach_ws per query: z | mu, var | jac_mu, jac_var | hess_mu | mu_bar, var_bar | jac_bar, jac_s | jz
-static long sr_reach_vjp_ws_per_query(int n_s, int n_u, int D) {
-    return D + 4L * n_s + 3L * n_s * D + (long)n_s * D * D + 2L * n_s * (n_s + n_u);
-}
-
 // The reverse pass of one step with the GP inside, behind the argument checks of sr_onestep_reach_vjp (mode 0; gpvar_bar NULL)
 // and sr_onestep_moments_vjp (mode 1 / 2; l_mu, l_sigma unread).  Per pass: z = [Tz p; k_ff], the GP at z with its first
 // derivatives -- and the Hessian of the mean (sr_gp_linearize_batch) only where jac_bar is not zero: modes 0 and 1 from an
@@ -604,51 +261,38 @@ static int onestep_vjp_impl(sr_gp* h, const char* who, long T, int mode, const d
                             double* p_bar, double* q_bar, double* kff_bar, double* kfb_bar, void* stream) {
     int n_s, n_u;
     SR_TRY(check_reach_dims(h, &n_s, &n_u));
-    if (h->D > 8) {                                   // the widths sr_gp_linearize_batch is compiled for
-        sr_set_error("%s: D=%d > 8 (the batched linearisation behind it)", who, h->D);
-        return SR_EUNSUPPORTED;
-    }
+    SR_TRY(check_linearize_width(h, who));
     hipStream_t s = (hipStream_t)stream;
     SR_DEVICE(h->device);
     const int D = h->D, n_xin = h->n_xin ? h->n_xin : n_s;
     const double* Tz = h->n_xin ? h->Tz : nullptr;
     const bool second = mode != 2 && q != nullptr;
-    const long per = sr_reach_vjp_ws_per_query(n_s, n_u, D);
+    const sr_reach_ws_use use{n_s, n_u, D, false, mode, second};
+    const long per = sr_reach_ws_carve(use, 0, nullptr).per;
     // a pass: the handle's chunk, at most 2^28 doubles (2 GB) of scratch, and never wider than the batch at which both GP calls
     // still split their sums as the model size alone sets it (sr_common.h): the same bits for any chunk size
-    const long chunk = std::max(1L, std::min({h->chunk, sr_stable_pass_max(h->N, h->Np, h->n_out), ((long)1 << 28) / per}));
-    const long nss = (long)n_s * n_s, nus = (long)n_u * n_s, nd = (long)n_s * D, nds = (long)n_s * (n_s + n_u);
+    const long chunk = std::max(1L, std::min({h->chunk, sr_stable_pass_max(h->N, h->Np, h->n_out), SR_REACH_WS_MAX_DOUBLES / per}));
+    const long nss = (long)n_s * n_s, nus = (long)n_u * n_s;
     const long Tw = std::min(chunk, T);
     SR_TRY(h->reach_ws.grow((size_t)(Tw * per), wait::stream(s)));
-    double* w = h->reach_ws.get();                   // (the order of sr_reach_vjp_ws_per_query)
-    double* z = w; w += Tw * D;
-    double* mu = w; w += Tw * n_s;
-    double* var = w; w += Tw * n_s;
-    double* jm = w; w += Tw * nd;
-    double* jv = w; w += Tw * nd;
-    double* hm = w; w += Tw * nd * D;
-    double* mu_bar = w; w += Tw * n_s;
-    double* var_bar = w; w += Tw * n_s;
-    double* jac_bar = w; w += Tw * nds;
-    double* jac_s = w; w += Tw * nds;
-    double* jz = w;
+    const sr_reach_ws w = sr_reach_ws_carve(use, Tw, h->reach_ws.get());
     for (long t0 = 0; t0 < T; t0 += chunk) {
         const long Tc = std::min(chunk, T - t0);
-        SR_TRY(sr_launch_reach_z(Tc, n_s, n_u, n_xin, p + t0 * n_s, k_ff + t0 * n_u, Tz, z, s));
-        if (second) SR_TRY(sr_gp_linearize_batch(h, z, Tc, mu, var, jm, jv, hm, stream));
-        else SR_TRY(sr_gp_predict_grad(h, z, Tc, mu, var, jm, jv, stream));
+        SR_TRY(sr_launch_reach_z(Tc, n_s, n_u, n_xin, p + t0 * n_s, k_ff + t0 * n_u, Tz, w.z, s));
+        if (second) SR_TRY(sr_gp_linearize_batch(h, w.z, Tc, w.mu, w.var, w.jac_mu, w.jac_var, w.hess_mu, stream));
+        else SR_TRY(sr_gp_predict_grad(h, w.z, Tc, w.mu, w.var, w.jac_mu, w.jac_var, stream));
         sr_momvjp_args ma{};
         sr_ellvjp_args& ea = ma.e;
         ea.T = Tc; ea.q = q ? q + t0 * nss : nullptr; ea.k_fb = k_fb ? k_fb + t0 * nus : nullptr;
-        ea.var = var; ea.jac = jm;                    // (identity transform: the GP's Jacobian is the state-space one)
+        ea.var = w.var; ea.jac = w.jac_mu;            // (identity transform: the GP's Jacobian is the state-space one)
         ea.a = a; ea.b = b; ea.l_mu = l_mu; ea.l_sigma = l_sigma; ea.c_safety = c_safety;
         ea.p1_bar = p1_bar ? p1_bar + t0 * n_s : nullptr; ea.q1_bar = q1_bar ? q1_bar + t0 * nss : nullptr;
         ea.p_bar = p_bar + t0 * n_s; ea.q_bar = q_bar ? q_bar + t0 * nss : nullptr;
         ea.kff_bar = kff_bar + t0 * n_u; ea.kfb_bar = kfb_bar ? kfb_bar + t0 * nus : nullptr;
-        ea.mu_bar = mu_bar; ea.var_bar = var_bar;
-        ea.jac_bar = (second || mode == 0) ? jac_bar : nullptr;      // (the ellipsoid kernel writes its zeros from a point too)
-        ea.jac_mu = jm; ea.jac_var = jv; ea.hess_mu = second ? hm : nullptr; ea.Tz = Tz; ea.D = D; ea.n_xin = n_xin;
-        ea.jac_s = jac_s; ea.jz = jz;
+        ea.mu_bar = w.mu_bar; ea.var_bar = w.var_bar;
+        ea.jac_bar = (second || mode == 0) ? w.jac_bar : nullptr;    // (the ellipsoid kernel writes its zeros from a point too)
+        ea.jac_mu = w.jac_mu; ea.jac_var = w.jac_var; ea.hess_mu = second ? w.hess_mu : nullptr; ea.Tz = Tz; ea.D = D; ea.n_xin = n_xin;
+        ea.jac_s = w.jac_s; ea.jz = w.jz;
         ma.gpvar_bar = gpvar_bar ? gpvar_bar + t0 * n_s : nullptr; ma.mode = mode;
         sr_prof_scope ps(&h->prof, SR_K_REACH_VJP, s);
         SR_TRY(mode == 0 ? sr_launch_reach_vjp(ea, n_s, n_u, s) : sr_launch_moments_vjp(ma, n_s, n_u, s));
@@ -660,8 +304,7 @@ extern "C" int sr_onestep_reach_vjp(sr_gp_t h, long T, const double* p, const do
                                     const double* k_fb, const double* a, const double* b, const double* l_mu,
                                     const double* l_sigma, double c_safety, const double* p1_bar, const double* q1_bar,
                                     double* p_bar, double* q_bar, double* kff_bar, double* kfb_bar, void* stream) {
-    SR_CHECK(h != nullptr, SR_EINVAL, "sr_onestep_reach_vjp: NULL handle");
-    SR_CHECK(h->factorized, SR_ESTATE, "sr_onestep_reach_vjp: model not factorized");
+    SR_TRY(handle_ready(h, "sr_onestep_reach_vjp"));
     SR_CHECK(T >= 0, SR_EINVAL, "sr_onestep_reach_vjp: T=%ld", T);
     if (T == 0) return SR_OK;
     SR_CHECK(p && k_ff && a && b && l_mu && l_sigma && p_bar && kff_bar, SR_EINVAL, "sr_onestep_reach_vjp: NULL argument");
@@ -671,183 +314,11 @@ extern "C" int sr_onestep_reach_vjp(sr_gp_t h, long T, const double* p, const do
                             nullptr, p_bar, q_bar, kff_bar, kfb_bar, stream);
 }
 
-// doubles of reach_ws per (trajectory, step) pair of sr_multistep_reach_vjp: those of one step's reverse pass, and
-// q_in, kfb_in | p_seed, q_seed | p_bar, q_bar, kff_bar, kfb_bar | eig
-static long sr_reach_rollout_vjp_ws_per_query(int n_s, int n_u, int D) {
-    return sr_reach_vjp_ws_per_query(n_s, n_u, D) + 2L * n_s + 3L * n_s * n_s + 2L * n_u * n_s + n_u + (1L + 2L * n_s + n_u);
-}
-
-// The reverse pass of sr_multistep_reach (sr_reach_rollout_vjp.hip).  Per group of max(1, chunk / H) trajectories: the inputs of all
-// their steps (one launch), sr_gp_linearize_batch over them in passes bounded as onestep_vjp_impl bounds them, then the sweep, one
-// thread per trajectory.  A thread owns its trajectory: the grouping decides nothing but the size of the scratch.
-extern "C" int sr_multistep_reach_vjp(sr_gp_t h, long T, int H, const double* p0, const double* q0, const double* k_fb0,
-                                      const double* k_ff, const double* k_fb, const double* a, const double* b,
-                                      const double* l_mu, const double* l_sigma, double c_safety, const double* p_all,
-                                      const double* q_all, const double* p_all_bar, const double* q_all_bar, double* p0_bar,
-                                      double* q0_bar, double* kfb0_bar, double* kff_bar, double* kfb_bar, void* stream) {
-    const char* who = "sr_multistep_reach_vjp";
-    SR_CHECK(h != nullptr, SR_EINVAL, "%s: NULL handle", who);
-    SR_CHECK(h->factorized, SR_ESTATE, "%s: model not factorized", who);
-    SR_CHECK(T >= 0 && H >= 1, SR_EINVAL, "%s: T=%ld H=%d", who, T, H);
-    int n_s, n_u;
-    SR_TRY(check_reach_dims(h, &n_s, &n_u));
-    if (h->D > 8) {                                   // the widths sr_gp_linearize_batch is compiled for
-        sr_set_error("%s: D=%d > 8 (the batched linearisation behind it)", who, h->D);
-        return SR_EUNSUPPORTED;
-    }
-    if (T == 0) return SR_OK;
-    SR_CHECK(p0 && k_ff && a && b && l_mu && l_sigma && p_all && q_all && p0_bar && kff_bar, SR_EINVAL, "%s: NULL argument", who);
-    SR_CHECK(H == 1 || (k_fb && kfb_bar), SR_EINVAL, "%s: k_fb and kfb_bar required for H > 1", who);
-    SR_CHECK(q0 == nullptr || (k_fb0 && q0_bar && kfb0_bar), SR_EINVAL, "%s: k_fb0, q0_bar and kfb0_bar required with q0", who);
-    SR_CHECK(p_all_bar || q_all_bar, SR_EINVAL, "%s: both seeds NULL", who);
-    hipStream_t s = (hipStream_t)stream;
-    SR_DEVICE(h->device);
-    const int D = h->D, n_xin = h->n_xin ? h->n_xin : n_s;
-    const long per = sr_reach_rollout_vjp_ws_per_query(n_s, n_u, D);
-    const long nss = (long)n_s * n_s, nus = (long)n_u * n_s, nd = (long)n_s * D, nds = (long)n_s * (n_s + n_u);
-    // a group: chunk / H trajectories and at most 2^28 doubles (2 GB) of scratch; a linearisation pass: as in onestep_vjp_impl
-    const long group = std::max(1L, std::min(h->chunk / H, ((long)1 << 28) / (per * H)));
-    const long pass = std::max(1L, std::min(h->chunk, sr_stable_pass_max(h->N, h->Np, h->n_out)));
-    const long Qw = std::min(group, T) * H;
-    SR_TRY(h->reach_ws.grow((size_t)(Qw * per), wait::stream(s)));
-    double* w = h->reach_ws.get();
-    auto take = [&](long each) { double* x = w; w += Qw * each; return x; };
-    sr_rrv_args r{};
-    sr_ellvjp_args& ea = r.e;
-    r.z = take(D);
-    double* mu = take(n_s);
-    double* var = take(n_s);
-    double* jm = take(nd);
-    double* jv = take(nd);
-    double* hm = take(nd * D);
-    ea.mu_bar = take(n_s); ea.var_bar = take(n_s); ea.jac_bar = take(nds); ea.jac_s = take(nds); ea.jz = take(nd);
-    r.q_in = take(nss); r.kfb_in = take(nus); r.p_seed = take(n_s); r.q_seed = take(nss);
-    ea.p_bar = take(n_s); ea.q_bar = take(nss); ea.kff_bar = take(n_u); ea.kfb_bar = take(nus);
-    r.eig = take(1 + 2 * n_s + n_u);
-    ea.q = r.q_in; ea.k_fb = r.kfb_in; ea.var = var; ea.jac = jm;
-    ea.a = a; ea.b = b; ea.l_mu = l_mu; ea.l_sigma = l_sigma; ea.c_safety = c_safety;
-    ea.p1_bar = r.p_seed; ea.q1_bar = r.q_seed;
-    ea.jac_mu = jm; ea.jac_var = jv; ea.hess_mu = hm; ea.Tz = h->n_xin ? h->Tz : nullptr; ea.D = D; ea.n_xin = n_xin;
-    r.H = H; r.n_s = n_s; r.n_u = n_u;
-    for (long t0 = 0; t0 < T; t0 += group) {
-        const long Tg = std::min(group, T - t0), Q = Tg * H;
-        ea.T = Tg;
-        r.p0 = p0 + t0 * n_s; r.q0 = q0 ? q0 + t0 * nss : nullptr; r.k_fb0 = q0 ? k_fb0 + t0 * nus : nullptr;
-        r.k_ff = k_ff + t0 * H * n_u; r.k_fb = k_fb ? k_fb + t0 * (H - 1) * nus : nullptr;
-        r.p_all = p_all + t0 * H * n_s; r.q_all = q_all + t0 * H * nss;
-        r.p_all_bar = p_all_bar ? p_all_bar + t0 * H * n_s : nullptr; r.q_all_bar = q_all_bar ? q_all_bar + t0 * H * nss : nullptr;
-        r.p0_bar = p0_bar + t0 * n_s; r.q0_bar = q0_bar ? q0_bar + t0 * nss : nullptr;
-        r.kfb0_bar = kfb0_bar ? kfb0_bar + t0 * nus : nullptr; r.kfb_bar = kfb_bar ? kfb_bar + t0 * (H - 1) * nus : nullptr;
-        r.kff_bar = kff_bar + t0 * H * n_u;
-        SR_TRY(sr_launch_reach_rollout_prep(r, s));
-        SR_TRY(sr_launch_reach_rollout_eig(r, s));
-        for (long q1 = 0; q1 < Q; q1 += pass) {
-            const long Qc = std::min(pass, Q - q1);
-            SR_TRY(sr_gp_linearize_batch(h, r.z + q1 * D, Qc, mu + q1 * n_s, var + q1 * n_s, jm + q1 * nd, jv + q1 * nd,
-                                         hm + q1 * nd * D, stream));
-        }
-        sr_prof_scope ps(&h->prof, SR_K_REACH_VJP, s);
-        SR_TRY(sr_launch_reach_rollout_vjp(r, s));
-    }
-    return SR_OK;
-}
-
-// doubles of reach_ws per (trajectory, step) pair of sr_multistep_moments_vjp: z | mu, var | jac_mu, jac_var | hess_mu (where it is
-// read) | mu_bar, var_bar | jac_bar, jac_s, jz (mode 1) | q_in, kfb_in | p_seed, q_seed | p_bar, q_bar, kff_bar, kfb_bar
-static long sr_moments_rollout_vjp_ws_per_query(int n_s, int n_u, int D, int mode, bool second) {
-    return D + 4L * n_s + 2L * n_s * D + (second ? (long)n_s * D * D : 0) + (mode == 1 ? 2L * n_s * (n_s + n_u) + (long)n_s * D : 0) +
-           2L * n_s + 3L * n_s * n_s + 2L * n_u * n_s + n_u;
-}
-
-// The reverse pass of sr_multistep_moments, and of H rounds of sr_onestep_moments from N(mu0, sigma0) (sr_moments_rollout_vjp.hip).
-// Per group of max(1, chunk / H) trajectories: the inputs of all their steps (the launch of sr_multistep_reach_vjp), the GP derivatives
-// at them in passes bounded as onestep_vjp_impl bounds them -- sr_gp_linearize_batch in mode 1, where a step from a Gaussian reads
-// the Hessian of the mean, sr_gp_predict_grad in mode 2 and for one step from a point --, then the sweep, one thread per trajectory.
-// A thread owns its trajectory: the grouping decides nothing but the size of the scratch.
-extern "C" int sr_multistep_moments_vjp(sr_gp_t h, long T, int H, int mode, const double* mu0, const double* sigma0,
-                                        const double* k_ff, const double* k_fb, const double* a, const double* b,
-                                        const double* mu_all, const double* sigma_all, const double* mu_all_bar,
-                                        const double* sigma_all_bar, const double* gpvar_all_bar, double* mu0_bar,
-                                        double* sigma0_bar, double* kff_bar, double* kfb_bar, void* stream) {
-    const char* who = "sr_multistep_moments_vjp";
-    SR_CHECK(h != nullptr, SR_EINVAL, "%s: NULL handle", who);
-    SR_CHECK(h->factorized, SR_ESTATE, "%s: model not factorized", who);
-    SR_CHECK(T >= 0 && H >= 1 && (mode == 1 || mode == 2), SR_EINVAL, "%s: T=%ld H=%d mode=%d", who, T, H, mode);
-    int n_s, n_u;
-    SR_TRY(check_reach_dims(h, &n_s, &n_u));
-    if (h->D > 8) {                                   // the widths sr_gp_linearize_batch is compiled for
-        sr_set_error("%s: D=%d > 8 (the batched linearisation behind it)", who, h->D);
-        return SR_EUNSUPPORTED;
-    }
-    if (T == 0) return SR_OK;
-    SR_CHECK(mu0 && k_ff && a && b && mu_all && sigma_all && mu0_bar && kff_bar, SR_EINVAL, "%s: NULL argument", who);
-    SR_CHECK(H == 1 || (k_fb && kfb_bar), SR_EINVAL, "%s: k_fb and kfb_bar required for H > 1", who);
-    SR_CHECK(sigma0 == nullptr || sigma0_bar != nullptr, SR_EINVAL, "%s: sigma0 without sigma0_bar", who);
-    SR_CHECK(mu_all_bar || sigma_all_bar || gpvar_all_bar, SR_EINVAL, "%s: every seed NULL", who);
-    hipStream_t s = (hipStream_t)stream;
-    SR_DEVICE(h->device);
-    const int D = h->D, n_xin = h->n_xin ? h->n_xin : n_s;
-    const bool second = mode == 1 && (H > 1 || sigma0 != nullptr);
-    const long per = sr_moments_rollout_vjp_ws_per_query(n_s, n_u, D, mode, second);
-    const long nss = (long)n_s * n_s, nus = (long)n_u * n_s, nd = (long)n_s * D, nds = (long)n_s * (n_s + n_u);
-    // a group: chunk / H trajectories and at most 2^28 doubles (2 GB) of scratch; a pass of GP derivatives: as in onestep_vjp_impl
-    const long group = std::max(1L, std::min(h->chunk / H, ((long)1 << 28) / (per * H)));
-    const long pass = std::max(1L, std::min(h->chunk, sr_stable_pass_max(h->N, h->Np, h->n_out)));
-    const long Qw = std::min(group, T) * H;
-    SR_TRY(h->reach_ws.grow((size_t)(Qw * per), wait::stream(s)));
-    double* w = h->reach_ws.get();
-    auto take = [&](long each) { double* x = w; w += Qw * each; return x; };
-    sr_mrv_args m{};
-    sr_rrv_args& r = m.r;
-    sr_ellvjp_args& ea = r.e;
-    r.z = take(D);
-    double* mu = take(n_s);
-    double* var = take(n_s);
-    double* jm = take(nd);
-    double* jv = take(nd);
-    double* hm = second ? take(nd * D) : nullptr;
-    ea.mu_bar = take(n_s); ea.var_bar = take(n_s);
-    if (mode == 1) { ea.jac_bar = take(nds); ea.jac_s = take(nds); ea.jz = take(nd); }
-    r.q_in = take(nss); r.kfb_in = take(nus); r.p_seed = take(n_s); r.q_seed = take(nss);
-    ea.p_bar = take(n_s); ea.q_bar = take(nss); ea.kff_bar = take(n_u); ea.kfb_bar = take(nus);
-    ea.q = r.q_in; ea.k_fb = r.kfb_in; ea.var = var; ea.jac = jm;
-    ea.a = a; ea.b = b; ea.c_safety = 1.0;
-    ea.p1_bar = r.p_seed; ea.q1_bar = r.q_seed;
-    ea.jac_mu = jm; ea.jac_var = jv; ea.hess_mu = hm; ea.Tz = h->n_xin ? h->Tz : nullptr; ea.D = D; ea.n_xin = n_xin;
-    r.H = H; r.n_s = n_s; r.n_u = n_u;
-    m.mode = mode;
-    for (long t0 = 0; t0 < T; t0 += group) {
-        const long Tg = std::min(group, T - t0), Q = Tg * H;
-        ea.T = Tg;
-        r.p0 = mu0 + t0 * n_s; r.q0 = sigma0 ? sigma0 + t0 * nss : nullptr;
-        r.k_ff = k_ff + t0 * H * n_u; r.k_fb = k_fb ? k_fb + t0 * (H - 1) * nus : nullptr;
-        r.p_all = mu_all + t0 * H * n_s; r.q_all = sigma_all + t0 * H * nss;
-        r.p_all_bar = mu_all_bar ? mu_all_bar + t0 * H * n_s : nullptr;
-        r.q_all_bar = sigma_all_bar ? sigma_all_bar + t0 * H * nss : nullptr;
-        m.gpvar_all_bar = gpvar_all_bar ? gpvar_all_bar + t0 * H * n_s : nullptr;
-        r.p0_bar = mu0_bar + t0 * n_s; r.q0_bar = sigma0 ? sigma0_bar + t0 * nss : nullptr;
-        r.kff_bar = kff_bar + t0 * H * n_u; r.kfb_bar = H > 1 ? kfb_bar + t0 * (H - 1) * nus : nullptr;
-        SR_TRY(sr_launch_reach_rollout_prep(r, s));
-        for (long q1 = 0; q1 < Q; q1 += pass) {
-            const long Qc = std::min(pass, Q - q1);
-            if (second)
-                SR_TRY(sr_gp_linearize_batch(h, r.z + q1 * D, Qc, mu + q1 * n_s, var + q1 * n_s, jm + q1 * nd, jv + q1 * nd,
-                                             hm + q1 * nd * D, stream));
-            else
-                SR_TRY(sr_gp_predict_grad(h, r.z + q1 * D, Qc, mu + q1 * n_s, var + q1 * n_s, jm + q1 * nd, jv + q1 * nd, stream));
-        }
-        sr_prof_scope ps(&h->prof, SR_K_REACH_VJP, s);
-        SR_TRY(sr_launch_moments_rollout_vjp(m, s));
-    }
-    return SR_OK;
-}
-
 extern "C" int sr_onestep_moments_vjp(sr_gp_t h, long T, int mode, const double* mu_x, const double* sigma_x, const double* k_ff,
                                       const double* k_fb, const double* a, const double* b, const double* mu1_bar,
                                       const double* sigma1_bar, const double* gpvar_bar, double* mux_bar, double* sigma_bar,
                                       double* kff_bar, double* kfb_bar, void* stream) {
-    SR_CHECK(h != nullptr, SR_EINVAL, "sr_onestep_moments_vjp: NULL handle");
-    SR_CHECK(h->factorized, SR_ESTATE, "sr_onestep_moments_vjp: model not factorized");
+    SR_TRY(handle_ready(h, "sr_onestep_moments_vjp"));
     SR_CHECK(T >= 0 && (mode == 1 || mode == 2), SR_EINVAL, "sr_onestep_moments_vjp: T=%ld mode=%d", T, mode);
     if (T == 0) return SR_OK;
     SR_CHECK(mu_x && k_ff && a && b && mux_bar && kff_bar, SR_EINVAL, "sr_onestep_moments_vjp: NULL argument");
@@ -856,6 +327,114 @@ extern "C" int sr_onestep_moments_vjp(sr_gp_t h, long T, int mode, const double*
     SR_CHECK(mu1_bar || sigma1_bar || gpvar_bar, SR_EINVAL, "sr_onestep_moments_vjp: every seed NULL");
     return onestep_vjp_impl(h, "sr_onestep_moments_vjp", T, mode, mu_x, sigma_x, k_ff, k_fb, a, b, nullptr, nullptr, 1.0,
                             mu1_bar, sigma1_bar, gpvar_bar, mux_bar, sigma_bar, kff_bar, kfb_bar, stream);
+}
+
+// The reverse pass of a whole roll-out, behind the argument checks of sr_multistep_reach_vjp (mode 0: sr_reach_rollout_vjp.hip;
+// gpvar_all_bar NULL) and sr_multistep_moments_vjp (mode 1 / 2: sr_moments_rollout_vjp.hip; k_fb0, kfb0_bar, l_mu, l_sigma NULL;
+// also H rounds of sr_onestep_moments from N(mu0, sigma0)).  Per group of max(1, chunk / H) trajectories: the inputs of all their
+// steps (one launch), in mode 0 the eigenpairs of their ellipsoids, the GP derivatives at them in passes bounded as
+// onestep_vjp_impl bounds them -- sr_gp_linearize_batch where a step reads the Hessian of the mean (mode 0; mode 1 but for one step
+// from a point), else sr_gp_predict_grad --, then the sweep, one thread per trajectory.  A thread owns its trajectory: the grouping
+// decides nothing but the size of the scratch.
+static int rollout_vjp_impl(sr_gp* h, int n_s, int n_u, long T, int H, int mode, const double* p0, const double* q0,
+                            const double* k_fb0, const double* k_ff, const double* k_fb, const double* a, const double* b,
+                            const double* l_mu, const double* l_sigma, double c_safety, const double* p_all, const double* q_all,
+                            const double* p_all_bar, const double* q_all_bar, const double* gpvar_all_bar, double* p0_bar,
+                            double* q0_bar, double* kfb0_bar, double* kff_bar, double* kfb_bar, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    SR_DEVICE(h->device);
+    const int D = h->D, n_xin = h->n_xin ? h->n_xin : n_s;
+    const bool second = mode == 0 || (mode == 1 && (H > 1 || q0 != nullptr));
+    const sr_reach_ws_use use{n_s, n_u, D, true, mode, second};
+    const long per = sr_reach_ws_carve(use, 0, nullptr).per;
+    const long nss = (long)n_s * n_s, nus = (long)n_u * n_s, nd = (long)n_s * D;
+    // a group: chunk / H trajectories and at most 2^28 doubles (2 GB) of scratch; a pass of GP derivatives: as in onestep_vjp_impl
+    const long group = std::max(1L, std::min(h->chunk / H, SR_REACH_WS_MAX_DOUBLES / (per * H)));
+    const long pass = std::max(1L, std::min(h->chunk, sr_stable_pass_max(h->N, h->Np, h->n_out)));
+    const long Qw = std::min(group, T) * H;
+    SR_TRY(h->reach_ws.grow((size_t)(Qw * per), wait::stream(s)));
+    const sr_reach_ws w = sr_reach_ws_carve(use, Qw, h->reach_ws.get());
+    sr_mrv_args m{};
+    sr_rrv_args& r = m.r;
+    sr_ellvjp_args& ea = r.e;
+    r.z = w.z; r.q_in = w.q_in; r.kfb_in = w.kfb_in; r.p_seed = w.p_seed; r.q_seed = w.q_seed; r.eig = w.eig;
+    ea.q = w.q_in; ea.k_fb = w.kfb_in; ea.var = w.var; ea.jac = w.jac_mu;
+    ea.a = a; ea.b = b; ea.l_mu = l_mu; ea.l_sigma = l_sigma; ea.c_safety = c_safety;
+    ea.p1_bar = w.p_seed; ea.q1_bar = w.q_seed;
+    ea.p_bar = w.p_bar; ea.q_bar = w.q_bar; ea.kff_bar = w.kff_bar; ea.kfb_bar = w.kfb_bar;
+    ea.mu_bar = w.mu_bar; ea.var_bar = w.var_bar; ea.jac_bar = w.jac_bar;
+    ea.jac_mu = w.jac_mu; ea.jac_var = w.jac_var; ea.hess_mu = w.hess_mu; ea.Tz = h->n_xin ? h->Tz : nullptr; ea.D = D; ea.n_xin = n_xin;
+    ea.jac_s = w.jac_s; ea.jz = w.jz;
+    r.H = H; r.n_s = n_s; r.n_u = n_u;
+    m.mode = mode;
+    for (long t0 = 0; t0 < T; t0 += group) {
+        const long Tg = std::min(group, T - t0), Q = Tg * H;
+        ea.T = Tg;
+        r.p0 = p0 + t0 * n_s; r.q0 = q0 ? q0 + t0 * nss : nullptr; r.k_fb0 = q0 && k_fb0 ? k_fb0 + t0 * nus : nullptr;
+        r.k_ff = k_ff + t0 * H * n_u; r.k_fb = k_fb ? k_fb + t0 * (H - 1) * nus : nullptr;
+        r.p_all = p_all + t0 * H * n_s; r.q_all = q_all + t0 * H * nss;
+        r.p_all_bar = p_all_bar ? p_all_bar + t0 * H * n_s : nullptr; r.q_all_bar = q_all_bar ? q_all_bar + t0 * H * nss : nullptr;
+        m.gpvar_all_bar = gpvar_all_bar ? gpvar_all_bar + t0 * H * n_s : nullptr;
+        r.p0_bar = p0_bar + t0 * n_s; r.q0_bar = q0_bar ? q0_bar + t0 * nss : nullptr;
+        r.kfb0_bar = kfb0_bar ? kfb0_bar + t0 * nus : nullptr; r.kfb_bar = kfb_bar ? kfb_bar + t0 * (H - 1) * nus : nullptr;
+        r.kff_bar = kff_bar + t0 * H * n_u;
+        SR_TRY(sr_launch_reach_rollout_prep(r, s));
+        if (mode == 0) SR_TRY(sr_launch_reach_rollout_eig(r, s));
+        for (long q1 = 0; q1 < Q; q1 += pass) {
+            const long Qc = std::min(pass, Q - q1);
+            if (second)
+                SR_TRY(sr_gp_linearize_batch(h, w.z + q1 * D, Qc, w.mu + q1 * n_s, w.var + q1 * n_s, w.jac_mu + q1 * nd,
+                                             w.jac_var + q1 * nd, w.hess_mu + q1 * nd * D, stream));
+            else
+                SR_TRY(sr_gp_predict_grad(h, w.z + q1 * D, Qc, w.mu + q1 * n_s, w.var + q1 * n_s, w.jac_mu + q1 * nd,
+                                          w.jac_var + q1 * nd, stream));
+        }
+        sr_prof_scope ps(&h->prof, SR_K_REACH_VJP, s);
+        SR_TRY(mode == 0 ? sr_launch_reach_rollout_vjp(r, s) : sr_launch_moments_rollout_vjp(m, s));
+    }
+    return SR_OK;
+}
+
+extern "C" int sr_multistep_reach_vjp(sr_gp_t h, long T, int H, const double* p0, const double* q0, const double* k_fb0,
+                                      const double* k_ff, const double* k_fb, const double* a, const double* b,
+                                      const double* l_mu, const double* l_sigma, double c_safety, const double* p_all,
+                                      const double* q_all, const double* p_all_bar, const double* q_all_bar, double* p0_bar,
+                                      double* q0_bar, double* kfb0_bar, double* kff_bar, double* kfb_bar, void* stream) {
+    const char* who = "sr_multistep_reach_vjp";
+    SR_TRY(handle_ready(h, who));
+    SR_CHECK(T >= 0 && H >= 1, SR_EINVAL, "%s: T=%ld H=%d", who, T, H);
+    int n_s, n_u;
+    SR_TRY(check_reach_dims(h, &n_s, &n_u));
+    SR_TRY(check_linearize_width(h, who));
+    if (T == 0) return SR_OK;
+    SR_CHECK(p0 && k_ff && a && b && l_mu && l_sigma && p_all && q_all && p0_bar && kff_bar, SR_EINVAL, "%s: NULL argument", who);
+    SR_CHECK(H == 1 || (k_fb && kfb_bar), SR_EINVAL, "%s: k_fb and kfb_bar required for H > 1", who);
+    SR_CHECK(q0 == nullptr || (k_fb0 && q0_bar && kfb0_bar), SR_EINVAL, "%s: k_fb0, q0_bar and kfb0_bar required with q0", who);
+    SR_CHECK(p_all_bar || q_all_bar, SR_EINVAL, "%s: both seeds NULL", who);
+    return rollout_vjp_impl(h, n_s, n_u, T, H, 0, p0, q0, k_fb0, k_ff, k_fb, a, b, l_mu, l_sigma, c_safety, p_all, q_all, p_all_bar,
+                            q_all_bar, nullptr, p0_bar, q0_bar, kfb0_bar, kff_bar, kfb_bar, stream);
+}
+
+extern "C" int sr_multistep_moments_vjp(sr_gp_t h, long T, int H, int mode, const double* mu0, const double* sigma0,
+                                        const double* k_ff, const double* k_fb, const double* a, const double* b,
+                                        const double* mu_all, const double* sigma_all, const double* mu_all_bar,
+                                        const double* sigma_all_bar, const double* gpvar_all_bar, double* mu0_bar,
+                                        double* sigma0_bar, double* kff_bar, double* kfb_bar, void* stream) {
+    const char* who = "sr_multistep_moments_vjp";
+    SR_TRY(handle_ready(h, who));
+    SR_CHECK(T >= 0 && H >= 1 && (mode == 1 || mode == 2), SR_EINVAL, "%s: T=%ld H=%d mode=%d", who, T, H, mode);
+    int n_s, n_u;
+    SR_TRY(check_reach_dims(h, &n_s, &n_u));
+    SR_TRY(check_linearize_width(h, who));
+    if (T == 0) return SR_OK;
+    SR_CHECK(mu0 && k_ff && a && b && mu_all && sigma_all && mu0_bar && kff_bar, SR_EINVAL, "%s: NULL argument", who);
+    SR_CHECK(H == 1 || (k_fb && kfb_bar), SR_EINVAL, "%s: k_fb and kfb_bar required for H > 1", who);
+    SR_CHECK(sigma0 == nullptr || sigma0_bar != nullptr, SR_EINVAL, "%s: sigma0 without sigma0_bar", who);
+    SR_CHECK(mu_all_bar || sigma_all_bar || gpvar_all_bar, SR_EINVAL, "%s: every seed NULL", who);
+    // (sigma0_bar of a point start is not written)
+    return rollout_vjp_impl(h, n_s, n_u, T, H, mode, mu0, sigma0, nullptr, k_ff, k_fb, a, b, nullptr, nullptr, 1.0, mu_all, sigma_all,
+                            mu_all_bar, sigma_all_bar, gpvar_all_bar, mu0_bar, sigma0 ? sigma0_bar : nullptr, nullptr, kff_bar,
+                            kfb_bar, stream);
 }
 
 extern "C" int sr_moment_step_vjp(int device, long T, int n_s, int n_u, int mode, const double* mu_x, const double* sigma_x,
@@ -970,26 +549,7 @@ extern "C" int sr_gp_sample(int device, long T, int size, int n_out, int n_u, co
     return sr_launch_sample(T, size, n_out, n_u, mu, var, eps, S, k_fb, k_ff, z_next, (hipStream_t)stream);
 }
 
-extern "C" int sr_gp_set_chain(sr_gp_t h, int on) {
-    SR_CHECK(h != nullptr, SR_EINVAL, "sr_gp_set_chain: NULL handle");
-    h->chain = on != 0;
-    return SR_OK;
-}
-
-extern "C" int sr_gp_last_chain(sr_gp_t h) { return h ? h->last_chain : 0; }
-
-extern "C" int sr_gp_chain_status(sr_gp_t h, int* timed_out) {
-    SR_CHECK(h != nullptr && timed_out != nullptr, SR_EINVAL, "sr_gp_chain_status: NULL argument");
-    *timed_out = 0;
-    if (h->chain_status_host && *(volatile int*)h->chain_status_host != 0) {
-        *timed_out = 1;
-        *(volatile int*)h->chain_status_host = 0;
-        h->chain = 0;                        // per-step launches from here on (sr_gp_set_chain re-arms)
-    }
-    return SR_OK;
-}
-
-// tests (host only): the two split rules of sr_common.h and the pass bound the reverse driver takes from them
+// tests (host only): the two split rules of sr_common.h and the pass bound the reverse drivers take from them
 extern "C" int sr_test_split_plan(int N, int Np, int n_out, long Tp, int* out) {
     SR_CHECK(N >= 1 && Np >= N && Np % SR_NB == 0 && n_out >= 1 && Tp >= 1 && out, SR_EINVAL, "sr_test_split_plan: bad argument");
     out[0] = sr_kstar_nsplit(Np, n_out, Tp);
@@ -998,22 +558,3 @@ extern "C" int sr_test_split_plan(int N, int Np, int n_out, long Tp, int* out) {
     out[3] = SR_FINAL_WAVE_T;
     return SR_OK;
 }
-
-// tests: the next persistent multi-step launches are short of `drop` workgroups, i.e. the last group waits for partners
-// that never come -- the deterministic way to reach the time-out path (a CU mask of one or two bits does not do it: the
-// driver widens such masks, the chain completed on "1 CU")
-extern "C" int sr_test_chain_drop(sr_gp_t h, int drop) {
-    SR_CHECK(h != nullptr && drop >= 0, SR_EINVAL, "sr_test_chain_drop: bad argument");
-    h->chain_test_drop = drop;
-    if (drop == 0 && h->chain_tickets) {
-        // a launch that was short of a workgroup leaves its group's counters in a state no real launch can produce
-        // (in the field every workgroup runs, however late, and the last one to leave resynchronises the group)
-        SR_DEVICE(h->device);
-        SR_HIP(device_sync());
-        SR_TRY(dev_zero(h->chain_xch, sizeof(sr_xel) * (size_t)SR_CHAIN_XELS));
-        SR_TRY(dev_zero(h->chain_tickets, sizeof(unsigned long long) * 2 * SR_CHAIN_GROUPS));
-        SR_TRY(dev_zero(h->chain_done, sizeof(unsigned) * SR_CHAIN_GROUPS));
-    }
-    return SR_OK;
-}
-

@@ -419,7 +419,7 @@ int sr_launch_var_bal(const double* Wt, const double* Ks, double* Vt, double* pa
 //  reverse pass of one step                  passes of at most sr_stable_pass_max(N, Np, n_out) queries: the widest batch at which
 //   (sr_capi_reach.hip: onestep_vjp_impl)    sr_kstar_nsplit and sr_hess_nsplit still give the counts of one 256-query block, SR_FINAL_WAVE_T
 //                                            at most (the same bits for any chunk size; N = 2000, two outputs: 768)
-//  multi-step chains (sr_capi_reach.hip)     persistent kernel K0c up to SR_CHAIN_GROUPS workgroups (device CUs - 16 at most),
+//  multi-step chains (sr_capi_chain.hip)     persistent kernel K0c up to SR_CHAIN_GROUPS workgroups (device CUs - 16 at most),
 //                                            1 launch for H <= 2, <= 2 launches for T <= 1024, <= 6 beyond (N = 200 H = 15: 1024
 //                                            rollouts 203 against 253 us, 4096 in six launches 608 / 722, r03_chain_bench); one-step
 //                                            through it for n_s <= 2 (24.5 -> 21.5 us; n_s >= 3: 25 -> 35 us)

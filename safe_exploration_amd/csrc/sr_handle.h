@@ -7,7 +7,10 @@
 //   sr_capi_remove.hip     retiring training points (sr_gp_remove), leave-one-out posterior (sr_gp_loo)
 //   sr_capi_posterior.hip  workspace, dispatch of the posterior pass (sr_gp_predict, sr_gp_linearize, sr_gp_call1),
 //                          input transform, completion mailbox
-//   sr_capi_reach.hip      reachability / moment / sampling entry points and the persistent-chain dispatch
+//   sr_capi_reach.hip      reachability / moment propagation with the GP inside, forward and reverse (scratch: sr_reach_ws.h);
+//                          the stateless steps, roll-out cost, distances, sampling
+//   sr_capi_chain.hip      dispatch of the persistent chain kernel (try_chain), its launch gate and switches
+//   sr_capi_moment_match.hip  exact moment matching: per query, whole roll-outs, and their reverse passes
 //   sr_capi_server.hip     resident single-query server: start / stop / blocking call
 //   sr_capi_paths.hip      posterior function samples by pathwise conditioning (sr_gp_paths_draw / _count / _weight_count /
 //                          _eval / _step ...)
@@ -147,8 +150,8 @@ struct sr_gp {
     // sr_gp_moment_match_rollout_vjp: per trajectory of a group the reverse pass's scratch of its H queries, their inputs, one
     // step's seeds and results, and the carried adjoint (sr_mmrv_ws_per_traj doubles each)
     srh::scratch<double> mm_ws;
-    // sr_onestep_reach_vjp, sr_onestep_moments_vjp: per query of a chunk z, the outputs of sr_gp_linearize_batch at z, the seeds on (mu, var, jac) and the
-    // two transformed Jacobians (sr_reach_vjp_ws_per_query doubles each)
+    // the reverse passes with the GP inside, of one step and of a whole roll-out (sr_capi_reach.hip): per query of a pass, or per
+    // (trajectory, step) pair of a group, the blocks that sr_reach_ws.h lays out
     srh::scratch<double> reach_ws;
     // sr_gp_remove: per output the coefficient tables of the retired row (3 Np + 4), then the input rows behind it
     srh::scratch<double> rm_ws;
@@ -300,6 +303,20 @@ int gp_pass(sr_gp* h, long Tc, const double* xa, long lda, int na, const double*
 int tile_route_alignment(sr_gp* h);
 int gp_pass_states(sr_gp* h, long Tc, const double* p, long ldp, int n_s, const double* kff, long ldkff, int n_u,
                    double* mu, double* var, const double** jac_out, hipStream_t s);
+// the persistent chain kernel for a chain of H >= 1 steps, where it applies; *taken says whether it ran (sr_capi_chain.hip;
+// hidden: the library's dynamic symbols stay those it had while this was a static function)
+__attribute__((visibility("hidden")))
+int try_chain(sr_gp* h, long T, int H, int mode, const double* p0, const double* q0, const double* k_fb0,
+              const double* k_ff, const double* k_fb, const double* a, const double* b, const double* l_mu,
+              const double* l_sigma, double c_safety, double* p_all, double* q_all, double* gp_var_all,
+              int* n_bad, int n_s, int n_u, hipStream_t s, bool* taken);
+
+// what every entry point that reads the fitted model checks first, under its own name
+static inline int handle_ready(const sr_gp* h, const char* who) {
+    SR_CHECK(h != nullptr, SR_EINVAL, "%s: NULL handle", who);
+    SR_CHECK(h->factorized, SR_ESTATE, "%s: model not factorized", who);
+    return SR_OK;
+}
 
 // ---- the model as a launch reads it --------------------------------------------------------------------------------
 // the fields every argument struct of the posterior kernels shares (sr_kstar_args, sr_lin_args)

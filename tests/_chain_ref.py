@@ -62,7 +62,7 @@ CHAIN_GROUPS, CHAIN_XELS, FUSED_T = 240, 240 * 112 * 96, 1024
 NOMINAL_CUS = 256                      # MI355X; the GPU test asks the device
 
 
-# ---- the launch arithmetic of try_chain (csrc/sr_capi_reach.hip), restated from its documentation ---------------------------------
+# ---- the launch arithmetic of try_chain (csrc/sr_capi_chain.hip), restated from its documentation ---------------------------------
 def padded(N):
     return -(-N // 128) * 128
 

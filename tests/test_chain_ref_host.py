@@ -86,7 +86,7 @@ def test_fp64_twin_of_the_reference_modules_is_fp64_and_the_default_is_unchanged
 
 
 def test_launch_arithmetic_matches_the_documented_examples():
-    """csrc/sr_capi_reach.hip: 768 roll-outs of a pendulum model with N <= 256 and 416 of a cart-pole model (N <= 256) in one
+    """csrc/sr_capi_chain.hip: 768 roll-outs of a pendulum model with N <= 256 and 416 of a cart-pole model (N <= 256) in one
     launch on a device that leaves 240 workgroups; H_max of the LDS control block"""
     assert 16 * C.gmax(256, 2, 1, 15) == 768 and 16 * C.gmax(256, 4, 1, 6) == 416
     assert C.h_max(3, 2) == 24 and C.h_max(4, 1) == 38
