@@ -569,6 +569,64 @@ int sr_rollout_cost_vjp(int device, long T, int H, int n_s, int n_u, int idx_ang
                         const double* mu, const double* sigma, const double* u, const double* cost_bar,
                         double* mu_bar, double* sigma_bar, double* u_bar, void* stream);
 
+/* replaces: SimpleSafeMPC.generate_safety_constraints / _generate_control_constraint  safempc_simple.py:317-392, 488-532 (batched;
+ * the constraint vector of the SafeMPC problem, every row a lin_ellipsoid_safety_distance)
+ * sr_rollout_constraints: the constraint rows of T stored roll-outs of H ellipsoids in ONE launch.  p_all T x H x n_s, q_all
+ * T x H x n_s x n_s are what sr_multistep_reach returned, k_ff T x H x n_u, k_fb T x (H - 1) x n_u x n_s (may be NULL when H == 1
+ * or without bounds) what it was given, q0 T x n_s x n_s with k_fb0 T x n_u x n_s its ellipsoid start (both NULL: point start).
+ * q_all and q0 are read as their symmetric parts (q + q^T) / 2.  Every row is satisfied iff g <= 0; per trajectory
+ * n_g = (bounds ? 2 n_u H : 0) + m_obs (H - 1) + m_safe rows in this order:
+ *   control    (u_min, u_max given, n_u each; both NULL: no such rows) for the steps i = 0 .. H - 1, 2 n_u rows each:
+ *              [k_ff[i] + r_i - u_max ; u_min - k_ff[i] + r_i],  r_i[j] = c_safety sqrt(K_i[j, :] Q_i K_i[j, :]^T) with
+ *              (Q_0, K_0) = (q0, k_fb0) -- a point start has r_0 = 0: the two-sided bound on u_0 -- and (Q_i, K_i) =
+ *              (q_all[i - 1], k_fb[i - 1]) for i >= 1, the indices of sr_multistep_reach (step i applies k_fb[i - 1] at
+ *              p_all[i - 1]); the reference's h_mat = [I; -I], h_vec = [u_max; -u_min] on the ellipsoid (k_ff, K Q K^T)
+ *   obstacle   (h_obs_mat m_obs x n_s, h_obs m_obs; m_obs == 0: both NULL) for the states i = 0 .. H - 2, m_obs rows each:
+ *              h . p_all[i] + c_safety sqrt(h q_all[i] h^T) - h_obs
+ *   terminal   (h_safe_mat m_safe x n_s, h_safe m_safe; m_safe == 0: both NULL) m_safe rows of that form on the last state
+ * c_safety scales every square root, the control rows' included (the control set is the image of the same ellipsoid; the
+ * reference passes its default 1 everywhere).  The obstacle and terminal rows are the bits of sr_safety_distance on the same
+ * ellipsoids at a symmetric q.  A negative radicand gives NaN in its row, as there.  g T x n_g; g_max (T, may be NULL) the
+ * largest row of each trajectory, NaN if any of its rows is NaN: g_max[t] <= 0 iff candidate t is feasible.  The rows work on
+ * mu_all / sigma_all of the moment roll-outs as they are (the chance constraints of CautiousMPC).  The same bits on every call, with
+ * and without g_max, and whatever other trajectories are in the batch.  No model handle, no scratch.  Asynchronous on `stream`.
+ * Errors, before any launch: SR_EINVAL NULL where required (p_all, q_all, g; k_ff with bounds; k_fb with bounds and H > 1), q0
+ * without k_fb0 or the reverse, u_min without u_max or the reverse, m_obs < 0 or m_safe < 0, m > 0 with a NULL matrix or vector,
+ * n_g == 0, T < 0, H < 1, n_s < 1, n_u < 1 with bounds; SR_EUNSUPPORTED n_s > 12 or n_u > 12; T == 0 is a no-op. */
+int sr_rollout_constraints(int device, long T, int H, int n_s, int n_u,
+                           const double* p_all, const double* q_all, const double* k_ff, const double* k_fb,
+                           const double* q0, const double* k_fb0 /* both NULL: point start */,
+                           const double* u_min, const double* u_max /* both NULL: no control rows */,
+                           int m_obs, const double* h_obs_mat, const double* h_obs,
+                           int m_safe, const double* h_safe_mat, const double* h_safe,
+                           double c_safety, double* g /* T x n_g */, double* g_max /* T | NULL */, void* stream);
+/* Its reverse pass in ONE launch: for the seed g_bar (T x n_g) the gradient of sum(g_bar * g) in the inputs:  p_all_bar
+ * T x H x n_s ; q_all_bar T x H x n_s x n_s, exactly symmetric ; kff_bar T x H x n_u ; kfb_bar T x (H - 1) x n_u x n_s ; with
+ * q0 also q0_bar T x n_s x n_s, exactly symmetric, and kfb0_bar T x n_u x n_s (both required iff q0 is given, else unread).
+ * Overwritten, not accumulated (zero where no row reads the input); each of the four main outputs may be NULL, not all four.
+ * p_all_bar / q_all_bar are shaped like, and are, the seeds of sr_multistep_reach_vjp: the gradient of a Lagrangian or penalty of
+ * the SafeMPC problem in k_ff, k_fb is a roll-out, this call and the roll-out's reverse pass, plus kff_bar / kfb_bar of this call
+ * (the rows read the gains directly as well).
+ * Closed form, with s = sqrt(h Q_s h^T), Q_s the symmetric part:  state rows  d / d p = g_bar h,  d / d Q = c g_bar h^T h / (2 s);
+ * control output j with g+ = g_bar_upper + g_bar_lower, k = K[j, :]:  d / d k_ff[j] = g_bar_upper - g_bar_lower,
+ * d / d k = c g+ Q_s k^T / s_j,  d / d Q = c g+ k^T k / (2 s_j).
+ * A radicand that is exactly zero -- a k_fb row of zeros, the usual initial guess, or q = 0 -- contributes ZERO through its
+ * square root: in k this is an element of the subdifferential of the norm k -> sqrt(k Q k^T) at its kink, in Q it truncates an
+ * infinite one-sided slope.  This deliberately differs from var_bar = +-inf of sr_ellipsoid_step_vjp: a zero gain must not poison
+ * a whole gradient with 0 * inf.  A negative radicand gives NaN in exactly the outputs of its (trajectory, state) that the row
+ * touches (q_all_bar[t, i], kfb_bar[t, i]; p_all_bar stays finite) and nothing else.
+ * One writer per output element, no atomics, sums in a fixed order: the same bits on every call and whatever other trajectories
+ * are in the batch.  Inputs and refusals as sr_rollout_constraints; SR_EINVAL also for g_bar NULL, every main output NULL, q0
+ * without q0_bar or kfb0_bar.  Asynchronous on `stream`. */
+int sr_rollout_constraints_vjp(int device, long T, int H, int n_s, int n_u,
+                               const double* p_all, const double* q_all, const double* k_ff, const double* k_fb,
+                               const double* q0, const double* k_fb0, const double* u_min, const double* u_max,
+                               int m_obs, const double* h_obs_mat, const double* h_obs,
+                               int m_safe, const double* h_safe_mat, const double* h_safe,
+                               double c_safety, const double* g_bar /* T x n_g */,
+                               double* p_all_bar, double* q_all_bar, double* kff_bar, double* kfb_bar,
+                               double* q0_bar, double* kfb0_bar /* required iff q0 is given */, void* stream);
+
 /* replaces: utils_ellipsoid.distance_to_center / sample_inside_ellipsoid  utils_ellipsoid.py:16-60 (batched;
  * the Monte-Carlo verification of sampling_models.py / gp_reachability.py:323-356 evaluates it per step)
  * T ellipsoids (p T x n_s, q T x n_s x n_s) against K samples: samples K x n_s shared by all ellipsoids

@@ -89,6 +89,8 @@ SIGNATURES = {
     "sr_safety_distance": (_I, [_I, _L, _I, _I, _P, _P, _P, _P, _D, _P, _P]),
     "sr_rollout_cost": (_I, [_I, _L, _I, _I, _I, _I, _D, _I, _I, _P, _P, _D, _D] + [_P] * 7),
     "sr_rollout_cost_vjp": (_I, [_I, _L, _I, _I, _I, _I, _D, _I, _I, _P, _P, _D, _D] + [_P] * 9),
+    "sr_rollout_constraints": (_I, [_I, _L, _I, _I, _I] + [_P] * 8 + [_I, _P, _P, _I, _P, _P, _D] + [_P] * 3),
+    "sr_rollout_constraints_vjp": (_I, [_I, _L, _I, _I, _I] + [_P] * 8 + [_I, _P, _P, _I, _P, _P, _D] + [_P] * 8),
     "sr_distance_to_center": (_I, [_I, _L, _I, _I, _P, _I, _P, _P, _P, _P]),
     "sr_gp_mll": (_I, [_H, _P, _P, _P]),
     "sr_gp_logdet": (_I, [_H, _P, _P]),

@@ -5,7 +5,7 @@
 // Reverse, with the GP inside: one step through onestep_vjp_impl, a whole roll-out through rollout_vjp_impl, in all three
 // modes.  Their scratch is the handle's reach_ws, laid out by sr_reach_ws.h.
 // Stateless, per query: the ellipsoid and moment steps and their reverse passes, the remainder, the safety distance, the
-// roll-out cost and its reverse pass, the distance to the centre, and sampling.
+// roll-out cost and the roll-out constraints with their reverse passes, the distance to the centre, and sampling.
 #include "sr_handle.h"
 #include "sr_reach_ws.h"
 using namespace srh;
@@ -526,6 +526,67 @@ extern "C" int sr_rollout_cost_vjp(int device, long T, int H, int n_s, int n_u, 
     SR_DEVICE(device);
     c.cost_bar = cost_bar; c.mu_bar = mu_bar; c.sigma_bar = sigma_bar; c.u_bar = u_bar;
     return sr_launch_rollout_cost(c, true, (hipStream_t)stream);
+}
+
+// the arguments sr_rollout_constraints and sr_rollout_constraints_vjp share: checked, then packed; before any launch
+static int rollout_constraints_args(const char* who, long T, int H, int n_s, int n_u, const double* p_all, const double* q_all,
+                                    const double* k_ff, const double* k_fb, const double* q0, const double* k_fb0, const double* u_min,
+                                    const double* u_max, int m_obs, const double* h_obs_mat, const double* h_obs, int m_safe,
+                                    const double* h_safe_mat, const double* h_safe, double c_safety, sr_rcn_args& c) {
+    SR_CHECK(T >= 0 && H >= 1 && n_s >= 1 && n_u >= 0, SR_EINVAL, "%s: T=%ld H=%d n_s=%d n_u=%d", who, T, H, n_s, n_u);
+    SR_CHECK(m_obs >= 0 && m_safe >= 0, SR_EINVAL, "%s: m_obs=%d m_safe=%d", who, m_obs, m_safe);
+    SR_CHECK(p_all && q_all, SR_EINVAL, "%s: NULL argument", who);
+    SR_CHECK(!q0 == !k_fb0, SR_EINVAL, "%s: q0 and k_fb0 go together", who);
+    SR_CHECK(!u_min == !u_max, SR_EINVAL, "%s: u_min and u_max go together", who);
+    const bool bounds = u_min != nullptr;
+    SR_CHECK(!bounds || n_u >= 1, SR_EINVAL, "%s: control bounds with n_u=%d", who, n_u);
+    SR_CHECK(!bounds || k_ff, SR_EINVAL, "%s: control bounds without k_ff", who);
+    SR_CHECK(!bounds || H == 1 || k_fb, SR_EINVAL, "%s: control bounds without k_fb (H=%d)", who, H);
+    SR_CHECK(m_obs == 0 || (h_obs_mat && h_obs), SR_EINVAL, "%s: m_obs=%d without h_obs_mat, h_obs", who, m_obs);
+    SR_CHECK(m_safe == 0 || (h_safe_mat && h_safe), SR_EINVAL, "%s: m_safe=%d without h_safe_mat, h_safe", who, m_safe);
+    const long n_g = (bounds ? 2L * n_u * H : 0L) + (long)m_obs * (H - 1) + m_safe;
+    SR_CHECK(n_g > 0, SR_EINVAL, "%s: no constraint rows (no bounds, m_obs (H - 1) = 0, m_safe = 0)", who);
+    SR_CHECK(n_s <= 12 && n_u <= 12, SR_EUNSUPPORTED, "%s: n_s=%d n_u=%d beyond 12", who, n_s, n_u);
+    SR_CHECK(n_g <= 2147483647L, SR_EUNSUPPORTED, "%s: %ld rows per trajectory", who, n_g);
+    c = sr_rcn_args{};
+    c.T = T; c.H = H; c.n_s = n_s; c.n_u = n_u; c.m_obs = m_obs; c.m_safe = m_safe; c.n_g = (int)n_g; c.bounds = bounds; c.c = c_safety;
+    c.p_all = p_all; c.q_all = q_all; c.k_ff = k_ff; c.k_fb = k_fb; c.q0 = q0; c.kfb0 = k_fb0; c.u_min = u_min; c.u_max = u_max;
+    c.h_obs_mat = h_obs_mat; c.h_obs = h_obs; c.h_safe_mat = h_safe_mat; c.h_safe = h_safe;
+    return SR_OK;
+}
+
+extern "C" int sr_rollout_constraints(int device, long T, int H, int n_s, int n_u, const double* p_all, const double* q_all,
+                                      const double* k_ff, const double* k_fb, const double* q0, const double* k_fb0,
+                                      const double* u_min, const double* u_max, int m_obs, const double* h_obs_mat,
+                                      const double* h_obs, int m_safe, const double* h_safe_mat, const double* h_safe,
+                                      double c_safety, double* g, double* g_max, void* stream) {
+    sr_rcn_args c;
+    SR_TRY(rollout_constraints_args("sr_rollout_constraints", T, H, n_s, n_u, p_all, q_all, k_ff, k_fb, q0, k_fb0, u_min, u_max, m_obs,
+                                    h_obs_mat, h_obs, m_safe, h_safe_mat, h_safe, c_safety, c));
+    SR_CHECK(g != nullptr, SR_EINVAL, "sr_rollout_constraints: NULL argument");
+    if (T == 0) return SR_OK;
+    SR_DEVICE(device);
+    c.g = g; c.g_max = g_max;
+    return sr_launch_rollout_constraints(c, false, (hipStream_t)stream);
+}
+
+extern "C" int sr_rollout_constraints_vjp(int device, long T, int H, int n_s, int n_u, const double* p_all, const double* q_all,
+                                          const double* k_ff, const double* k_fb, const double* q0, const double* k_fb0,
+                                          const double* u_min, const double* u_max, int m_obs, const double* h_obs_mat,
+                                          const double* h_obs, int m_safe, const double* h_safe_mat, const double* h_safe,
+                                          double c_safety, const double* g_bar, double* p_all_bar, double* q_all_bar, double* kff_bar,
+                                          double* kfb_bar, double* q0_bar, double* kfb0_bar, void* stream) {
+    sr_rcn_args c;
+    SR_TRY(rollout_constraints_args("sr_rollout_constraints_vjp", T, H, n_s, n_u, p_all, q_all, k_ff, k_fb, q0, k_fb0, u_min, u_max,
+                                    m_obs, h_obs_mat, h_obs, m_safe, h_safe_mat, h_safe, c_safety, c));
+    SR_CHECK(g_bar != nullptr, SR_EINVAL, "sr_rollout_constraints_vjp: NULL argument");
+    SR_CHECK(p_all_bar || q_all_bar || kff_bar || kfb_bar, SR_EINVAL, "sr_rollout_constraints_vjp: every output NULL");
+    SR_CHECK(!q0 || (q0_bar && kfb0_bar), SR_EINVAL, "sr_rollout_constraints_vjp: q0 without q0_bar, kfb0_bar");
+    if (T == 0) return SR_OK;
+    SR_DEVICE(device);
+    c.g_bar = g_bar; c.p_all_bar = p_all_bar; c.q_all_bar = q_all_bar; c.kff_bar = kff_bar; c.kfb_bar = kfb_bar;
+    c.q0_bar = q0_bar; c.kfb0_bar = kfb0_bar;
+    return sr_launch_rollout_constraints(c, true, (hipStream_t)stream);
 }
 
 extern "C" int sr_distance_to_center(int device, long T, int K, int n_s, const double* samples, int per_t,

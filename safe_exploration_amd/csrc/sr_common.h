@@ -789,6 +789,16 @@ struct sr_cost_args {
     double *cost, *cost_steps, *mu_bar, *sigma_bar, *u_bar;
 };
 int sr_launch_rollout_cost(sr_cost_args a, bool reverse, hipStream_t s);
+// the SafeMPC constraint rows over a stored roll-out and their reverse pass (sr_rollout_constraints.hip): the arguments of
+// sr_rollout_constraints / sr_rollout_constraints_vjp; bounds: control rows present, n_g the rows per trajectory, G the
+// trajectories per workgroup of the forward (set by the launch)
+struct sr_rcn_args {
+    long T; int H, n_s, n_u, m_obs, m_safe, n_g, bounds, G;
+    double c;
+    const double *p_all, *q_all, *k_ff, *k_fb, *q0, *kfb0, *u_min, *u_max, *h_obs_mat, *h_obs, *h_safe_mat, *h_safe, *g_bar;
+    double *g, *g_max, *p_all_bar, *q_all_bar, *kff_bar, *kfb_bar, *q0_bar, *kfb0_bar;
+};
+int sr_launch_rollout_constraints(sr_rcn_args a, bool reverse, hipStream_t s);
 
 // ---- fused small-batch posterior (sr_stream.hip) ------------------------------------------------------
 struct sr_lin_args;

@@ -58,15 +58,8 @@ __global__ __launch_bounds__(256) void sr_safety_kernel(long T, int n_s, int m,
     const double* pt = p + t * n_s;
     const double* qt = q + t * n_s * n_s;
     for (int r = 0; r < m; ++r) {
-        const double* h = h_mat + r * n_s;
-        double dc = 0.0, quad = 0.0;
-        for (int i = 0; i < n_s; ++i) {
-            dc = fma(h[i], pt[i], dc);
-            double s = 0.0;
-            for (int j = 0; j < n_s; ++j) s = fma(qt[i * n_s + j], h[j], s);
-            quad = fma(s, h[i], quad);
-        }
-        d[t * m + r] = dc + c * sqrt(quad) - h_vec[r];
+        double quad;
+        d[t * m + r] = sr_safety_row(h_mat + r * n_s, pt, [&](int i, int j) { return qt[i * n_s + j]; }, n_s, c, h_vec[r], quad);
     }
 }
 

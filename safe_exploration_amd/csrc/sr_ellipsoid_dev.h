@@ -9,6 +9,23 @@
 #pragma once
 #include "sr_common.h"
 
+// One row of lin_ellipsoid_safety_distance (gp_reachability.py:245-248): h . p + c sqrt(h Q h^T) - h_vec, the radicand left in
+// `quad`.  q(i, j) is the caller's view of the shape matrix (sr_safety_kernel: as stored; sr_rollout_constraints: its symmetric
+// part, the same bits at a symmetric Q).  The order of the fma chains is the contract: both kernels return the same bits.
+template <class QF>
+__device__ __forceinline__ double sr_safety_row(const double* __restrict__ h, const double* __restrict__ pt, QF q, int n_s, double c,
+                                                double h_vec, double& quad) {
+    double dc = 0.0;
+    quad = 0.0;
+    for (int i = 0; i < n_s; ++i) {
+        dc = fma(h[i], pt[i], dc);
+        double s = 0.0;
+        for (int j = 0; j < n_s; ++j) s = fma(q(i, j), h[j], s);
+        quad = fma(s, h[i], quad);
+    }
+    return dc + c * sqrt(quad) - h_vec;
+}
+
 // largest eigenvalue of Q * B, Q symmetric PSD, B = I + K^T K SPD.
 // eig(Q B) == eig(L^T Q L) with B = L L^T (similarity by L^T); the latter is symmetric, so a cyclic
 // Jacobi iteration gives all eigenvalues to full fp64 accuracy.  The reference calls

@@ -645,6 +645,237 @@ def lin_ellipsoid_safety_distance(p_center, q_shape, h_mat, h_vec, c_safety=1.0)
 
 
 # ------------------------------------------------------------------------------------------------
+# the constraint vector of SimpleSafeMPC.generate_safety_constraints over stored roll-outs (safempc_simple.py:317-392, 488-532)
+# ------------------------------------------------------------------------------------------------
+def rollout_constraint_layout(H, n_u, m_obs, m_safe, has_bounds):
+    """Host only: where the rows of ``rollout_constraints_batch`` sit.  Returns (blocks, names): blocks = dict(control=slice,
+    obstacle=slice, terminal=slice) into the n_g = (2 n_u H if has_bounds) + m_obs (H - 1) + m_safe rows of a trajectory, names
+    one string per row -- the reference's g_name strings: "u_0_ctrl_constraint" for the 2 n_u rows of step 0,
+    "ellipsoid_ctrl_constraint_{i}" for those of step i + 1 (the reference counts from its k_fb[i]),
+    "obstacle_avoidance_constraint{i}" for state i, "terminal constraint"."""
+    H, n_u, m_obs, m_safe = int(H), int(n_u), int(m_obs), int(m_safe)
+    if H < 1 or n_u < 0 or m_obs < 0 or m_safe < 0 or (has_bounds and n_u < 1):
+        raise ValueError("need H >= 1, m_obs >= 0, m_safe >= 0 and n_u >= 1 with bounds")
+    n_ctrl = 2 * n_u * H if has_bounds else 0
+    n_obs = m_obs * (H - 1)
+    blocks = dict(control=slice(0, n_ctrl), obstacle=slice(n_ctrl, n_ctrl + n_obs), terminal=slice(n_ctrl + n_obs, n_ctrl + n_obs + m_safe))
+    names = []
+    if has_bounds:
+        names += ["u_0_ctrl_constraint"] * (2 * n_u)
+        for i in range(H - 1):
+            names += ["ellipsoid_ctrl_constraint_{}".format(i)] * (2 * n_u)
+    for i in range(H - 1):
+        names += ["obstacle_avoidance_constraint{}".format(i)] * m_obs
+    names += ["terminal constraint"] * m_safe
+    return blocks, names
+
+
+def _constraints_prepare(p_all, q_all, k_ff, k_fb, ctrl_bounds, h_mat_obs, h_obs, h_mat_safe, h_safe, q_0, k_fb_0, c_safety, device):
+    """Shapes checked (ValueError, before anything touches the device), then everything on the device: the arguments both entry
+    points share, in the order of the C ABI after `device`."""
+    as_t = B.is_tensor(p_all)
+    shp = tuple(np.shape(p_all))
+    if len(shp) != 3 or shp[1] < 1 or shp[2] < 1:
+        raise ValueError("p_all must be (T, H, n_s) with H >= 1")
+    T, H, n_s = shp
+    if tuple(np.shape(q_all)) != (T, H, n_s, n_s):
+        raise ValueError("q_all must be {}".format((T, H, n_s, n_s)))
+    has_bounds = ctrl_bounds is not None
+    n_u = 0
+    if k_ff is not None:
+        ushp = tuple(np.shape(k_ff))
+        if len(ushp) != 3 or ushp[:2] != (T, H):
+            raise ValueError("k_ff must be (T, H, n_u)")
+        n_u = ushp[2]
+    if has_bounds:
+        if k_ff is None or n_u < 1:
+            raise ValueError("ctrl_bounds needs k_ff (T, H, n_u) with n_u >= 1")
+        cb = np.asarray(B.to_numpy(ctrl_bounds) if B.is_tensor(ctrl_bounds) else ctrl_bounds, dtype=np.float64)
+        if cb.shape != (n_u, 2):
+            raise ValueError("ctrl_bounds must be ({}, 2)".format(n_u))
+        if H > 1 and k_fb is None:
+            raise ValueError("ctrl_bounds needs k_fb for H > 1")
+    if k_fb is not None and H > 1 and int(np.prod(np.shape(k_fb))) != T * (H - 1) * n_u * n_s:
+        raise ValueError("k_fb must be {}".format((T, H - 1, n_u, n_s)))
+    if (q_0 is None) != (k_fb_0 is None):
+        raise ValueError("q_0 and k_fb_0 go together")
+    if q_0 is not None:
+        if tuple(np.shape(q_0)) != (T, n_s, n_s):
+            raise ValueError("q_0 must be {}".format((T, n_s, n_s)))
+        if k_ff is None or tuple(np.shape(k_fb_0)) != (T, n_u, n_s):
+            raise ValueError("k_fb_0 must be (T, n_u, n_s), with k_ff given")
+    hs = []
+    for hm, hv, what in ((h_mat_obs, h_obs, "obs"), (h_mat_safe, h_safe, "safe")):
+        if (hm is None) != (hv is None):
+            raise ValueError("h_mat_{0} and h_{0} go together".format(what))
+        if hm is None:
+            hs.append((0, None, None))
+            continue
+        hm = np.asarray(B.to_numpy(hm) if B.is_tensor(hm) else hm, dtype=np.float64)
+        hv = np.asarray(B.to_numpy(hv) if B.is_tensor(hv) else hv, dtype=np.float64).reshape(-1)
+        if hm.ndim != 2 or hm.shape[0] < 1 or hm.shape[1] != n_s or hv.size != hm.shape[0]:
+            raise ValueError("h_mat_{0} must be (m, {1}) and h_{0} hold m entries".format(what, n_s))
+        hs.append((hm.shape[0], hm, hv))
+    (m_obs, hmo, hvo), (m_safe, hms, hvs) = hs
+    n_g = (2 * n_u * H if has_bounds else 0) + m_obs * (H - 1) + m_safe
+    if n_g == 0:
+        raise ValueError("no constraint rows: give ctrl_bounds, obstacles (H > 1) or a terminal set")
+    if n_s > 12 or n_u > 12:
+        raise NotImplementedError("rollout constraints: n_s and n_u up to 12")
+    dev = B.resolve_device(p_all.device if as_t else device)
+    pa, qa, kff = B.as_dev(p_all, dev), B.as_dev(q_all, dev), B.as_dev(k_ff, dev)
+    kfb = B.as_dev(k_fb, dev, (T, H - 1, n_u, n_s)) if (k_fb is not None and H > 1) else None
+    q0, kfb0 = B.as_dev(q_0, dev), B.as_dev(k_fb_0, dev)
+    umin = B.const_dev(cb[:, 0], dev, (n_u,)) if has_bounds else None
+    umax = B.const_dev(cb[:, 1], dev, (n_u,)) if has_bounds else None
+    dho = [None if x is None else B.const_dev(x, dev, x.shape) for x in (hmo, hvo, hms, hvs)]
+    head = (dev.index, T, H, n_s, n_u, B.ptr(pa), B.ptr(qa), B.ptr(kff), B.ptr(kfb), B.ptr(q0), B.ptr(kfb0), B.ptr(umin), B.ptr(umax),
+            m_obs, B.ptr(dho[0]), B.ptr(dho[1]), m_safe, B.ptr(dho[2]), B.ptr(dho[3]), float(c_safety))
+    return as_t, dev, (T, H, n_s, n_u, n_g), head, (pa, qa, kff, kfb, q0, kfb0, umin, umax, dho)
+
+
+def rollout_constraints_batch(p_all, q_all, k_ff, k_fb, ctrl_bounds=None, h_mat_obs=None, h_obs=None, h_mat_safe=None, h_safe=None,
+                              q_0=None, k_fb_0=None, c_safety=1.0, return_max=False, differentiable=False, device=None):
+    """The SafeMPC constraint rows of T roll-outs in one launch (``sr_rollout_constraints``; the reference's
+    ``SimpleSafeMPC.generate_safety_constraints``).
+
+    p_all (T,H,n_s), q_all (T,H,n_s,n_s): what ``multistep_reachability_batch`` returned; k_ff (T,H,n_u), k_fb (T,H-1,n_u,n_s):
+    what it was given (both may be None without ctrl_bounds; k_fb None for H == 1); q_0 (T,n_s,n_s) with k_fb_0 (T,n_u,n_s) its
+    ellipsoid start.  ctrl_bounds (n_u,2) = [u_min, u_max] as in the reference; (h_mat_obs (m_obs,n_s), h_obs) the obstacle
+    half-spaces on the states 0 .. H-2, (h_mat_safe, h_safe) the terminal set on the last one.  Returns g (T,n_g), every row
+    satisfied iff g <= 0, in the order of ``rollout_constraint_layout``; with return_max (g, g_max (T)): the largest row per
+    trajectory (NaN if any row is NaN), g_max <= 0 iff the candidate is feasible.  c_safety scales every square root.  The rows work
+    on mu_all / sigma_all of the moment roll-outs as they are (the chance constraints of CautiousMPC).  differentiable (tensors
+    only): the same bits, with an autograd graph to p_all, q_all, k_ff, k_fb, q_0 and k_fb_0 whose backward is one
+    ``rollout_constraints_vjp_batch`` call (once differentiable; g_max carries no gradient).  numpy in -> numpy out, tensors in ->
+    tensors out."""
+    if differentiable:
+        if not B.is_tensor(p_all):
+            raise TypeError("differentiable=True needs tensors")
+        cfg = (ctrl_bounds, h_mat_obs, h_obs, h_mat_safe, h_safe, c_safety)
+        out = _RolloutConstraintsFn.apply(cfg, p_all, q_all, k_ff, k_fb, q_0, k_fb_0)
+        return out if return_max else out[0]
+    as_t, dev, (T, H, n_s, n_u, n_g), head, keep = _constraints_prepare(p_all, q_all, k_ff, k_fb, ctrl_bounds, h_mat_obs, h_obs,
+                                                                       h_mat_safe, h_safe, q_0, k_fb_0, c_safety, device)
+    g = B.empty((T, n_g), dev)
+    g_max = B.empty((T,), dev) if return_max else None
+    check(lib.sr_rollout_constraints(*head, B.ptr(g), B.ptr(g_max), B.stream_ptr(dev)))
+    outs = (g, g_max) if return_max else (g,)
+    if not as_t:
+        outs = tuple(B.to_numpy(o) for o in outs)
+    return outs if return_max else outs[0]
+
+
+def rollout_constraints_vjp_batch(p_all, q_all, k_ff, k_fb, ctrl_bounds=None, h_mat_obs=None, h_obs=None, h_mat_safe=None,
+                                  h_safe=None, q_0=None, k_fb_0=None, c_safety=1.0, g_bar=None, device=None):
+    """Reverse pass of ``rollout_constraints_batch`` in one launch (``sr_rollout_constraints_vjp``): for the seed g_bar (T,n_g) the
+    gradients of sum(g_bar * g): (p_all_bar, q_all_bar, kff_bar, kfb_bar, q0_bar, kfb0_bar), shaped like p_all, q_all, k_ff, k_fb,
+    q_0, k_fb_0 (None where the input is None or empty).  q_all_bar and q0_bar are exactly symmetric.  p_all_bar / q_all_bar are the
+    seeds of ``multistep_reachability_vjp_batch``; kff_bar / kfb_bar are added to what that call returns for k_ff / k_fb.  A radicand
+    that is exactly zero (a zero k_fb row, q = 0) contributes zero through its square root; a negative one NaN in q_all_bar, kfb_bar
+    of its own state only."""
+    as_t, dev, (T, H, n_s, n_u, n_g), head, keep = _constraints_prepare(p_all, q_all, k_ff, k_fb, ctrl_bounds, h_mat_obs, h_obs,
+                                                                       h_mat_safe, h_safe, q_0, k_fb_0, c_safety, device)
+    if g_bar is None or tuple(np.shape(g_bar)) != (T, n_g):
+        raise ValueError("g_bar must be {}".format((T, n_g)))
+    gb = B.as_dev(g_bar, dev)
+    kfb, q0 = keep[3], keep[4]
+    outs = [B.empty((T, H, n_s), dev), B.empty((T, H, n_s, n_s), dev),
+            B.empty((T, H, n_u), dev) if (k_ff is not None and n_u) else None,
+            B.empty((T, H - 1, n_u, n_s), dev) if kfb is not None else None,
+            B.empty((T, n_s, n_s), dev) if q0 is not None else None, B.empty((T, n_u, n_s), dev) if q0 is not None else None]
+    check(lib.sr_rollout_constraints_vjp(*head, B.ptr(gb), *[B.ptr(o) for o in outs], B.stream_ptr(dev)))
+    return tuple(outs) if as_t else tuple(None if o is None else B.to_numpy(o) for o in outs)
+
+
+class _RolloutConstraintsFn(torch.autograd.Function):
+    """``rollout_constraints_batch(differentiable=True)``: the forward is the plain call, the backward one
+    ``rollout_constraints_vjp_batch``."""
+
+    @staticmethod
+    def forward(ctx, cfg, p_all, q_all, k_ff, k_fb, q_0, k_fb_0):
+        ctrl_bounds, h_mat_obs, h_obs, h_mat_safe, h_safe, c_safety = cfg
+        g, g_max = rollout_constraints_batch(p_all, q_all, k_ff, k_fb, ctrl_bounds, h_mat_obs, h_obs, h_mat_safe, h_safe, q_0, k_fb_0,
+                                             c_safety, True)
+        ctx.cfg = cfg
+        ctx.save_for_backward(p_all, q_all, k_ff, k_fb, q_0, k_fb_0)
+        ctx.mark_non_differentiable(g_max)
+        ctx.set_materialize_grads(False)
+        return g, g_max
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_bar, _g_max_bar):
+        p_all, q_all, k_ff, k_fb, q_0, k_fb_0 = ctx.saved_tensors
+        ctrl_bounds, h_mat_obs, h_obs, h_mat_safe, h_safe, c_safety = ctx.cfg
+        if g_bar is None:
+            return (None,) * 7
+        out = rollout_constraints_vjp_batch(p_all, q_all, k_ff, k_fb, ctrl_bounds, h_mat_obs, h_obs, h_mat_safe, h_safe, q_0, k_fb_0,
+                                            c_safety, g_bar)
+        ins = (p_all, q_all, k_ff, k_fb, q_0, k_fb_0)
+        return (None,) + tuple(None if (x is None or o is None) else o.reshape(x.shape) for x, o in zip(ins, out))
+
+
+def safety_constraints(p_all, q_all, u_0, k_fb, k_ff_all, ctrl_bounds=None, h_mat_obs=None, h_obs=None, h_mat_safe=None, h_safe=None,
+                       q_0=None, k_fb_0=None, c_safety=1.0):
+    """Host twin (NumPy, no device) of ``SimpleSafeMPC.generate_safety_constraints`` for ONE trajectory (safempc_simple.py:317-392),
+    with the reference's argument split: p_all (H,n_s), q_all (H,n_s,n_s) or (H,n_s*n_s), u_0 (n_u) the first control, k_fb
+    (H-1,n_u,n_s) or (H-1,n_u*n_s), k_ff_all (H-1,n_u) the feed-forward terms of the steps 1 .. H-1.  Returns (g, lbg, ubg, g_name)
+    in the reference's own order, lbg <= g <= ubg: the u_0 rows as the reference emits them -- for a point start plain u_0 with the
+    bounds u_min / u_max, with (q_0, k_fb_0) the 2 n_u ellipsoid rows with (-inf, 0) --, then the control rows of the steps
+    1 .. H-1, the obstacle rows and the terminal rows, each with (-inf, 0).  g_name holds one string per row.  Behind the u_0 rows
+    this is a trajectory's row of ``rollout_constraints_batch`` (k_ff = [u_0; k_ff_all]), to rounding."""
+    p = np.asarray(p_all, dtype=np.float64)
+    if p.ndim != 2 or p.shape[0] < 1:
+        raise ValueError("p_all must be (H, n_s)")
+    H, n_s = p.shape
+    q = np.asarray(q_all, dtype=np.float64).reshape(H, n_s, n_s)
+    q = 0.5 * (q + q.transpose(0, 2, 1))
+    if (q_0 is None) != (k_fb_0 is None):
+        raise ValueError("q_0 and k_fb_0 go together")
+
+    def dist(pc, qs, h_mat, h_vec):
+        h_mat = np.asarray(h_mat, dtype=np.float64)
+        return h_mat.dot(pc) + c_safety * np.sqrt(np.sum(qs.dot(h_mat.T) * h_mat.T, axis=0)) - np.asarray(h_vec, dtype=np.float64).reshape(-1)
+
+    g, lbg, ubg, names = [], [], [], []
+    if ctrl_bounds is not None:
+        cb = np.asarray(ctrl_bounds, dtype=np.float64)
+        n_u = cb.shape[0]
+        if cb.shape != (n_u, 2) or u_0 is None:
+            raise ValueError("ctrl_bounds must be (n_u, 2), with u_0 given")
+        u0 = np.asarray(u_0, dtype=np.float64).reshape(n_u)
+        kff = np.asarray(k_ff_all, dtype=np.float64).reshape(H - 1, n_u) if H > 1 else np.zeros((0, n_u))
+        kfb = np.asarray(k_fb, dtype=np.float64).reshape(H - 1, n_u, n_s) if H > 1 else np.zeros((0, n_u, n_s))
+        h_u, v_u = np.vstack((np.eye(n_u), -np.eye(n_u))), np.concatenate((cb[:, 1], -cb[:, 0]))
+        if q_0 is None:
+            g.append(u0)
+            lbg += cb[:, 0].tolist()
+            ubg += cb[:, 1].tolist()
+            names += ["u_0_ctrl_constraint"] * n_u
+        else:
+            q0, k0 = np.asarray(q_0, dtype=np.float64).reshape(n_s, n_s), np.asarray(k_fb_0, dtype=np.float64).reshape(n_u, n_s)
+            g.append(dist(u0, k0.dot(0.5 * (q0 + q0.T)).dot(k0.T), h_u, v_u))
+            names += ["u_0_ctrl_constraint"] * (2 * n_u)
+        for i in range(H - 1):
+            g.append(dist(kff[i], kfb[i].dot(q[i]).dot(kfb[i].T), h_u, v_u))
+            names += ["ellipsoid_ctrl_constraint_{}".format(i)] * (2 * n_u)
+    if h_mat_obs is not None:
+        for i in range(H - 1):
+            g.append(dist(p[i], q[i], h_mat_obs, h_obs))
+            names += ["obstacle_avoidance_constraint{}".format(i)] * np.shape(h_mat_obs)[0]
+    if h_mat_safe is not None:
+        g.append(dist(p[-1], q[-1], h_mat_safe, h_safe))
+        names += ["terminal constraint"] * np.shape(h_mat_safe)[0]
+    if not g:
+        raise ValueError("no constraint rows: give ctrl_bounds, obstacles (H > 1) or a terminal set")
+    g = np.concatenate(g)
+    lbg += [-np.inf] * (g.size - len(lbg))
+    ubg += [0.0] * (g.size - len(ubg))
+    return g, lbg, ubg, names
+
+
+# ------------------------------------------------------------------------------------------------
 # closed-loop roll-outs of the TRUE system against the predicted ellipsoids (gp_reachability.py:253-356).
 # `env` is the caller's environment object (duck-typed: ``simulate_onestep(state, action) -> (state, ...)``,
 # attributes n_s / n_u); these are host-side bookkeeping around the batched containment kernels.
