@@ -343,6 +343,29 @@ int sr_multistep_reach_vjp(sr_gp_t h, long T, int H, const double* p0, const dou
                            const double* l_sigma, double c_safety, const double* p_all, const double* q_all,
                            const double* p_all_bar, const double* q_all_bar, double* p0_bar, double* q0_bar, double* kfb0_bar,
                            double* kff_bar, double* kfb_bar, void* stream);
+/* ---- the GP variances of a reachability roll-out (the reference's third output, gp_pred_sigma_all) and their seed ----------------
+ * sr_multistep_reach_var: sr_multistep_reach with one more output, gp_var_all T x H x n_s (or NULL): gp_var_all[t][i] is the
+ * predictive variance step i used, at z_i = [Tz p_{i-1}; k_ff_i], clipped at 1e-15 as everywhere.  The same driver and the same
+ * routes (the persistent chain where it applies, else per-step launches): p_all, q_all and n_bad are the bits of sr_multistep_reach
+ * on whichever route the call takes, with and without gp_var_all.  Refusals as sr_multistep_reach. */
+int sr_multistep_reach_var(sr_gp_t h, long T, int H, const double* p0, const double* q0, const double* k_fb0, const double* k_ff,
+                           const double* k_fb, const double* a, const double* b, const double* l_mu, const double* l_sigma,
+                           double c_safety, double* p_all, double* q_all, double* gp_var_all, int* n_bad, void* stream);
+/* sr_multistep_reach_var_vjp: sr_multistep_reach_vjp with a third seed, gpvar_all_bar T x H x n_s on the variances above:
+ *   L = sum p_all_bar . p_all + sum q_all_bar . q_all + sum gpvar_all_bar . gp_var_all.
+ * Any seed NULL = zero; all three NULL is SR_EINVAL.  In the sweep gpvar_all_bar[t][i] is added to the var_bar of step i after the
+ * step's reverse algebra has written it and before the GP link reads it (z_bar += jac_var^T gpvar_all_bar[t][i]); the clip of the
+ * variance is ignored, as in every reverse pass here.  A step that is a bound violation has a NaN var_bar, which stays NaN: under a
+ * seed on the variances alone the NaN reaches exactly what it reaches under any seed -- kff_bar[t][:i+1], kfb_bar[t][:i], p0_bar[t],
+ * q0_bar[t], kfb0_bar[t] -- and nothing else.  Everything else is the contract of sr_multistep_reach_vjp: outputs, symmetry
+ * conventions, grouping, pass width, the same bits on every call and for any chunk size, D <= 8, n_s <= 8, n_u <= 4.  With
+ * gpvar_all_bar == NULL the add is not executed at all and the outputs are the bits of sr_multistep_reach_vjp, which itself keeps
+ * returning the bits it returned before this entry point existed. */
+int sr_multistep_reach_var_vjp(sr_gp_t h, long T, int H, const double* p0, const double* q0, const double* k_fb0,
+                               const double* k_ff, const double* k_fb, const double* a, const double* b, const double* l_mu,
+                               const double* l_sigma, double c_safety, const double* p_all, const double* q_all,
+                               const double* p_all_bar, const double* q_all_bar, const double* gpvar_all_bar, double* p0_bar,
+                               double* q0_bar, double* kfb0_bar, double* kff_bar, double* kfb_bar, void* stream);
 
 /* ---- Gaussian moment propagation (the CautiousMPC baseline), batched -----------------------------
  * replaces: uncertainty_propagation_casadi.one_step_taylor / multi_step_taylor_symbolic (mode 1)
@@ -626,6 +649,45 @@ int sr_rollout_constraints_vjp(int device, long T, int H, int n_s, int n_u,
                                double c_safety, const double* g_bar /* T x n_g */,
                                double* p_all_bar, double* q_all_bar, double* kff_bar, double* kfb_bar,
                                double* q0_bar, double* kfb0_bar /* required iff q0 is given */, void* stream);
+
+/* ---- the exploration objective over the stored GP variances of roll-outs ------------------------------------------------------
+ * replaces: the default cost of SimpleSafeMPC.generate_cost_function  safempc_simple.py:286-315  (kind 1; with the deviation term
+ *           its n_perf > 1 branch) and of StaticSafeMPCExploration.init_solver  safempc_exploration.py:104  (kind 0)
+ * sr_rollout_explore: the objective of T roll-outs in ONE launch; no model handle, no scratch.  gp_var T x H_v x n_s are GP variances
+ * of a roll-out (gp_var_all of sr_multistep_reach_var or of sr_multistep_moments).  Per trajectory t, with v = gp_var[t]:
+ *   kind 0   info_i = -r_i,        r_i = (v[i][0] + v[i][1]) + ... + v[i][n_s-1]
+ *   kind 1   info_i = -sqrt(r_i),  r_i = ((v[i][0] + v[i][1]) + ... + v[i][n_s-1]) + eps
+ *            (the reference adds eps_noise to every element: eps = n_s eps_noise)
+ *   n_dev >= 2:  dev_i = d^T W d for 1 <= i < n_dev, d = mu[t][i] - p[t][i]; row 0 is skipped as in the reference.  p T x H_p x n_s
+ *            is the safe trajectory, mu T x H_m x n_s the performance trajectory, W n_s x n_s need not be symmetric (the caller
+ *            passes 0.1 wx_cost).  s_a = fma(W[a][n_s-1], d_{n_s-1}, ... fma(W[a][0], d_0, 0)), dev_i = fma(d_{n_s-1}, s_{n_s-1}, ...
+ *            fma(d_0, s_0, 0)).
+ *   cost[t] = ((info_0 + info_1) + ... + info_{H_v-1}) + ((dev_1 + dev_2) + ... + dev_{n_dev-1})   (the second bracket only with n_dev >= 2)
+ * cost_steps T x H_v (or NULL) receives the information terms info_i.  Every sum runs in the order written here, one writer per
+ * output element, no atomics: the same bits on every call and whatever else is in the batch, with and without cost_steps.
+ * r_i < 0 (kind 1) gives NaN in cost[t] and cost_steps[t][i] only.
+ * Before any launch: SR_EINVAL for NULL where required (gp_var, cost), kind outside {0, 1}, T < 0, H_v < 1, n_s < 1, n_dev < 0 or
+ * n_dev == 1, n_dev > min(H_p, H_m), n_dev >= 2 without p, mu or W, eps < 0; SR_EUNSUPPORTED for n_s > 12; T == 0 is a no-op.
+ * p and mu may be NULL with n_dev == 0 (H_p, H_m are then ignored).  Asynchronous on `stream`. */
+int sr_rollout_explore(int device, long T, int kind /* 0 sum, 1 sqrt */, int n_s, int H_v, const double* gp_var /* T x H_v x n_s */,
+                       double eps, int n_dev /* 0: no deviation term */, int H_p, const double* p /* T x H_p x n_s | NULL */,
+                       int H_m, const double* mu /* T x H_m x n_s | NULL */, const double* W /* n_s x n_s | NULL */,
+                       double* cost /* T */, double* cost_steps /* T x H_v | NULL */, void* stream);
+/* Its reverse pass in ONE launch, in closed form: for the seed cost_bar (T; NULL = ones, the same bits) the gradient of
+ * sum(cost_bar * cost):  gpvar_bar[t][i][:] = -cost_bar[t] (kind 0) or -cost_bar[t] / (2 sqrt(r_i)) (kind 1);
+ * mu_bar[t][i][a] = cost_bar[t] fma-sum_{b = 0 ..} (W[a][b] + W[b][a]) d_b and p_bar[t][i] = -mu_bar[t][i] for 1 <= i < n_dev; every
+ * other row of p_bar (T x H_p x n_s) and mu_bar (T x H_m x n_s) is exactly zero.  Overwritten, not accumulated.  gpvar_bar is shaped
+ * like, and is, the seed gpvar_all_bar of sr_multistep_reach_var_vjp (or of sr_multistep_moments_vjp); p_bar is added to the seed on
+ * p_all, mu_bar is the seed on the means of the performance roll-out: the gradient of the exploration problem is a roll-out, this
+ * call and the roll-out's reverse pass.
+ * r_i == 0 contributes exactly ZERO (the convention of sr_rollout_constraints_vjp for a zero radicand: the infinite one-sided
+ * slope is truncated, not +-inf); r_i < 0 gives NaN in gpvar_bar[t][i][:] only.
+ * Each output may be NULL, not all three; p_bar needs p and mu_bar needs mu (SR_EINVAL).  Inputs, determinism and the other refusals
+ * as sr_rollout_explore.  Asynchronous on `stream`. */
+int sr_rollout_explore_vjp(int device, long T, int kind, int n_s, int H_v, const double* gp_var, double eps, int n_dev, int H_p,
+                           const double* p, int H_m, const double* mu, const double* W, const double* cost_bar /* T | NULL = ones */,
+                           double* gpvar_bar /* T x H_v x n_s */, double* p_bar /* T x H_p x n_s */, double* mu_bar /* T x H_m x n_s */,
+                           void* stream);
 
 /* replaces: utils_ellipsoid.distance_to_center / sample_inside_ellipsoid  utils_ellipsoid.py:16-60 (batched;
  * the Monte-Carlo verification of sampling_models.py / gp_reachability.py:323-356 evaluates it per step)

@@ -81,6 +81,8 @@ SIGNATURES = {
     "sr_ellipsoid_step_vjp": (_I, [_I, _L, _I, _I] + [_P] * 11 + [_D] + [_P] * 10),
     "sr_onestep_reach_vjp": (_I, [_H, _L] + [_P] * 8 + [_D] + [_P] * 7),
     "sr_multistep_reach_vjp": (_I, [_H, _L, _I] + [_P] * 9 + [_D] + [_P] * 10),
+    "sr_multistep_reach_var": (_I, [_H, _L, _I] + [_P] * 9 + [_D] + [_P] * 5),
+    "sr_multistep_reach_var_vjp": (_I, [_H, _L, _I] + [_P] * 9 + [_D] + [_P] * 11),
     "sr_moment_step_vjp": (_I, [_I, _L, _I, _I, _I] + [_P] * 19),
     "sr_onestep_moments": (_I, [_H, _L, _I] + [_P] * 10),
     "sr_onestep_moments_vjp": (_I, [_H, _L, _I] + [_P] * 14),
@@ -91,6 +93,8 @@ SIGNATURES = {
     "sr_rollout_cost_vjp": (_I, [_I, _L, _I, _I, _I, _I, _D, _I, _I, _P, _P, _D, _D] + [_P] * 9),
     "sr_rollout_constraints": (_I, [_I, _L, _I, _I, _I] + [_P] * 8 + [_I, _P, _P, _I, _P, _P, _D] + [_P] * 3),
     "sr_rollout_constraints_vjp": (_I, [_I, _L, _I, _I, _I] + [_P] * 8 + [_I, _P, _P, _I, _P, _P, _D] + [_P] * 8),
+    "sr_rollout_explore": (_I, [_I, _L, _I, _I, _I, _P, _D, _I, _I, _P, _I, _P, _P] + [_P] * 3),
+    "sr_rollout_explore_vjp": (_I, [_I, _L, _I, _I, _I, _P, _D, _I, _I, _P, _I, _P, _P] + [_P] * 5),
     "sr_distance_to_center": (_I, [_I, _L, _I, _I, _P, _I, _P, _P, _P, _P]),
     "sr_gp_mll": (_I, [_H, _P, _P, _P]),
     "sr_gp_logdet": (_I, [_H, _P, _P]),

@@ -5,7 +5,8 @@
 // Reverse, with the GP inside: one step through onestep_vjp_impl, a whole roll-out through rollout_vjp_impl, in all three
 // modes.  Their scratch is the handle's reach_ws, laid out by sr_reach_ws.h.
 // Stateless, per query: the ellipsoid and moment steps and their reverse passes, the remainder, the safety distance, the
-// roll-out cost and the roll-out constraints with their reverse passes, the distance to the centre, and sampling.
+// roll-out cost, the roll-out constraints and the exploration objective with their reverse passes, the distance to the centre, and
+// sampling.
 #include "sr_handle.h"
 #include "sr_reach_ws.h"
 using namespace srh;
@@ -180,6 +181,21 @@ extern "C" int sr_multistep_reach(sr_gp_t h, long T, int H, const double* p0, co
                           nullptr, n_bad, (hipStream_t)stream);
 }
 
+// sr_multistep_reach with the GP variances of every step beside its outputs: the same driver, the same routes, the same bits
+extern "C" int sr_multistep_reach_var(sr_gp_t h, long T, int H, const double* p0, const double* q0, const double* k_fb0,
+                                      const double* k_ff, const double* k_fb, const double* a, const double* b, const double* l_mu,
+                                      const double* l_sigma, double c_safety, double* p_all, double* q_all, double* gp_var_all,
+                                      int* n_bad, void* stream) {
+    SR_TRY(handle_ready(h, "sr_multistep_reach_var"));
+    SR_CHECK(T >= 0 && H >= 1, SR_EINVAL, "sr_multistep_reach_var: T=%ld H=%d", T, H);
+    if (T == 0) return SR_OK;
+    SR_CHECK(p0 && k_ff && a && b && l_mu && l_sigma && p_all && q_all, SR_EINVAL, "sr_multistep_reach_var: NULL argument");
+    SR_CHECK(H == 1 || k_fb != nullptr, SR_EINVAL, "sr_multistep_reach_var: k_fb required for H > 1");
+    SR_CHECK(q0 == nullptr || k_fb0 != nullptr, SR_EINVAL, "sr_multistep_reach_var: k_fb0 required with q0");
+    return multistep_impl(h, T, H, 0, p0, q0, k_fb0, k_ff, k_fb, a, b, l_mu, l_sigma, c_safety, p_all, q_all, gp_var_all, n_bad,
+                          (hipStream_t)stream);
+}
+
 extern "C" int sr_multistep_moments(sr_gp_t h, long T, int H, int mode, const double* mu0, const double* k_ff,
                                     const double* k_fb, const double* a, const double* b, double* mu_all,
                                     double* sigma_all, double* gp_var_all, void* stream) {
@@ -330,7 +346,7 @@ extern "C" int sr_onestep_moments_vjp(sr_gp_t h, long T, int mode, const double*
 }
 
 // The reverse pass of a whole roll-out, behind the argument checks of sr_multistep_reach_vjp (mode 0: sr_reach_rollout_vjp.hip;
-// gpvar_all_bar NULL) and sr_multistep_moments_vjp (mode 1 / 2: sr_moments_rollout_vjp.hip; k_fb0, kfb0_bar, l_mu, l_sigma NULL;
+// gpvar_all_bar NULL), sr_multistep_reach_var_vjp (mode 0 with the seed on the GP variances) and sr_multistep_moments_vjp (mode 1 / 2: sr_moments_rollout_vjp.hip; k_fb0, kfb0_bar, l_mu, l_sigma NULL;
 // also H rounds of sr_onestep_moments from N(mu0, sigma0)).  Per group of max(1, chunk / H) trajectories: the inputs of all their
 // steps (one launch), in mode 0 the eigenpairs of their ellipsoids, the GP derivatives at them in passes bounded as
 // onestep_vjp_impl bounds them -- sr_gp_linearize_batch where a step reads the Hessian of the mean (mode 0; mode 1 but for one step
@@ -374,7 +390,7 @@ static int rollout_vjp_impl(sr_gp* h, int n_s, int n_u, long T, int H, int mode,
         r.k_ff = k_ff + t0 * H * n_u; r.k_fb = k_fb ? k_fb + t0 * (H - 1) * nus : nullptr;
         r.p_all = p_all + t0 * H * n_s; r.q_all = q_all + t0 * H * nss;
         r.p_all_bar = p_all_bar ? p_all_bar + t0 * H * n_s : nullptr; r.q_all_bar = q_all_bar ? q_all_bar + t0 * H * nss : nullptr;
-        m.gpvar_all_bar = gpvar_all_bar ? gpvar_all_bar + t0 * H * n_s : nullptr;
+        r.gpvar_all_bar = gpvar_all_bar ? gpvar_all_bar + t0 * H * n_s : nullptr;
         r.p0_bar = p0_bar + t0 * n_s; r.q0_bar = q0_bar ? q0_bar + t0 * nss : nullptr;
         r.kfb0_bar = kfb0_bar ? kfb0_bar + t0 * nus : nullptr; r.kfb_bar = kfb_bar ? kfb_bar + t0 * (H - 1) * nus : nullptr;
         r.kff_bar = kff_bar + t0 * H * n_u;
@@ -395,12 +411,13 @@ static int rollout_vjp_impl(sr_gp* h, int n_s, int n_u, long T, int H, int mode,
     return SR_OK;
 }
 
-extern "C" int sr_multistep_reach_vjp(sr_gp_t h, long T, int H, const double* p0, const double* q0, const double* k_fb0,
-                                      const double* k_ff, const double* k_fb, const double* a, const double* b,
-                                      const double* l_mu, const double* l_sigma, double c_safety, const double* p_all,
-                                      const double* q_all, const double* p_all_bar, const double* q_all_bar, double* p0_bar,
-                                      double* q0_bar, double* kfb0_bar, double* kff_bar, double* kfb_bar, void* stream) {
-    const char* who = "sr_multistep_reach_vjp";
+// sr_multistep_reach_vjp (gpvar_all_bar NULL) and sr_multistep_reach_var_vjp behind their shared argument checks
+static int multistep_reach_vjp_checked(const char* who, sr_gp_t h, long T, int H, const double* p0, const double* q0,
+                                       const double* k_fb0, const double* k_ff, const double* k_fb, const double* a, const double* b,
+                                       const double* l_mu, const double* l_sigma, double c_safety, const double* p_all,
+                                       const double* q_all, const double* p_all_bar, const double* q_all_bar,
+                                       const double* gpvar_all_bar, double* p0_bar, double* q0_bar, double* kfb0_bar, double* kff_bar,
+                                       double* kfb_bar, void* stream) {
     SR_TRY(handle_ready(h, who));
     SR_CHECK(T >= 0 && H >= 1, SR_EINVAL, "%s: T=%ld H=%d", who, T, H);
     int n_s, n_u;
@@ -410,9 +427,29 @@ extern "C" int sr_multistep_reach_vjp(sr_gp_t h, long T, int H, const double* p0
     SR_CHECK(p0 && k_ff && a && b && l_mu && l_sigma && p_all && q_all && p0_bar && kff_bar, SR_EINVAL, "%s: NULL argument", who);
     SR_CHECK(H == 1 || (k_fb && kfb_bar), SR_EINVAL, "%s: k_fb and kfb_bar required for H > 1", who);
     SR_CHECK(q0 == nullptr || (k_fb0 && q0_bar && kfb0_bar), SR_EINVAL, "%s: k_fb0, q0_bar and kfb0_bar required with q0", who);
-    SR_CHECK(p_all_bar || q_all_bar, SR_EINVAL, "%s: both seeds NULL", who);
+    SR_CHECK(p_all_bar || q_all_bar || gpvar_all_bar, SR_EINVAL, "%s: every seed NULL", who);
     return rollout_vjp_impl(h, n_s, n_u, T, H, 0, p0, q0, k_fb0, k_ff, k_fb, a, b, l_mu, l_sigma, c_safety, p_all, q_all, p_all_bar,
-                            q_all_bar, nullptr, p0_bar, q0_bar, kfb0_bar, kff_bar, kfb_bar, stream);
+                            q_all_bar, gpvar_all_bar, p0_bar, q0_bar, kfb0_bar, kff_bar, kfb_bar, stream);
+}
+
+extern "C" int sr_multistep_reach_vjp(sr_gp_t h, long T, int H, const double* p0, const double* q0, const double* k_fb0,
+                                      const double* k_ff, const double* k_fb, const double* a, const double* b,
+                                      const double* l_mu, const double* l_sigma, double c_safety, const double* p_all,
+                                      const double* q_all, const double* p_all_bar, const double* q_all_bar, double* p0_bar,
+                                      double* q0_bar, double* kfb0_bar, double* kff_bar, double* kfb_bar, void* stream) {
+    return multistep_reach_vjp_checked("sr_multistep_reach_vjp", h, T, H, p0, q0, k_fb0, k_ff, k_fb, a, b, l_mu, l_sigma, c_safety,
+                                       p_all, q_all, p_all_bar, q_all_bar, nullptr, p0_bar, q0_bar, kfb0_bar, kff_bar, kfb_bar, stream);
+}
+
+extern "C" int sr_multistep_reach_var_vjp(sr_gp_t h, long T, int H, const double* p0, const double* q0, const double* k_fb0,
+                                          const double* k_ff, const double* k_fb, const double* a, const double* b,
+                                          const double* l_mu, const double* l_sigma, double c_safety, const double* p_all,
+                                          const double* q_all, const double* p_all_bar, const double* q_all_bar,
+                                          const double* gpvar_all_bar, double* p0_bar, double* q0_bar, double* kfb0_bar,
+                                          double* kff_bar, double* kfb_bar, void* stream) {
+    return multistep_reach_vjp_checked("sr_multistep_reach_var_vjp", h, T, H, p0, q0, k_fb0, k_ff, k_fb, a, b, l_mu, l_sigma,
+                                       c_safety, p_all, q_all, p_all_bar, q_all_bar, gpvar_all_bar, p0_bar, q0_bar, kfb0_bar, kff_bar,
+                                       kfb_bar, stream);
 }
 
 extern "C" int sr_multistep_moments_vjp(sr_gp_t h, long T, int H, int mode, const double* mu0, const double* sigma0,
@@ -587,6 +624,49 @@ extern "C" int sr_rollout_constraints_vjp(int device, long T, int H, int n_s, in
     c.g_bar = g_bar; c.p_all_bar = p_all_bar; c.q_all_bar = q_all_bar; c.kff_bar = kff_bar; c.kfb_bar = kfb_bar;
     c.q0_bar = q0_bar; c.kfb0_bar = kfb0_bar;
     return sr_launch_rollout_constraints(c, true, (hipStream_t)stream);
+}
+
+// the arguments sr_rollout_explore and sr_rollout_explore_vjp share: checked, then packed; before any launch
+static int rollout_explore_args(const char* who, long T, int kind, int n_s, int H_v, const double* gp_var, double eps, int n_dev,
+                                int H_p, const double* p, int H_m, const double* mu, const double* W, sr_xpl_args& c) {
+    SR_CHECK(T >= 0 && H_v >= 1 && n_s >= 1, SR_EINVAL, "%s: T=%ld H_v=%d n_s=%d", who, T, H_v, n_s);
+    SR_CHECK(kind == 0 || kind == 1, SR_EINVAL, "%s: kind=%d (0 sum, 1 sqrt)", who, kind);
+    SR_CHECK(gp_var != nullptr, SR_EINVAL, "%s: NULL argument", who);
+    SR_CHECK(eps >= 0.0, SR_EINVAL, "%s: eps=%g", who, eps);                 // (a NaN eps fails it too)
+    SR_CHECK(n_dev >= 0 && n_dev != 1, SR_EINVAL, "%s: n_dev=%d (0: no deviation term, else >= 2)", who, n_dev);
+    SR_CHECK(n_dev == 0 || (p && mu && W), SR_EINVAL, "%s: n_dev=%d without p, mu or W", who, n_dev);
+    SR_CHECK(n_dev == 0 || (n_dev <= H_p && n_dev <= H_m), SR_EINVAL, "%s: n_dev=%d beyond H_p=%d or H_m=%d", who, n_dev, H_p, H_m);
+    SR_CHECK((!p || H_p >= 1) && (!mu || H_m >= 1), SR_EINVAL, "%s: H_p=%d H_m=%d", who, H_p, H_m);
+    SR_CHECK(n_s <= 12, SR_EUNSUPPORTED, "%s: n_s=%d beyond 12", who, n_s);
+    c = sr_xpl_args{};
+    c.T = T; c.kind = kind; c.n_s = n_s; c.H_v = H_v; c.n_dev = n_dev; c.H_p = p ? H_p : 0; c.H_m = mu ? H_m : 0; c.eps = eps;
+    c.gp_var = gp_var; c.p = p; c.mu = mu; c.W = W;
+    return SR_OK;
+}
+
+extern "C" int sr_rollout_explore(int device, long T, int kind, int n_s, int H_v, const double* gp_var, double eps, int n_dev, int H_p,
+                                  const double* p, int H_m, const double* mu, const double* W, double* cost, double* cost_steps,
+                                  void* stream) {
+    sr_xpl_args c;
+    SR_TRY(rollout_explore_args("sr_rollout_explore", T, kind, n_s, H_v, gp_var, eps, n_dev, H_p, p, H_m, mu, W, c));
+    SR_CHECK(cost != nullptr, SR_EINVAL, "sr_rollout_explore: NULL argument");
+    if (T == 0) return SR_OK;
+    SR_DEVICE(device);
+    c.cost = cost; c.cost_steps = cost_steps;
+    return sr_launch_rollout_explore(c, false, (hipStream_t)stream);
+}
+
+extern "C" int sr_rollout_explore_vjp(int device, long T, int kind, int n_s, int H_v, const double* gp_var, double eps, int n_dev,
+                                      int H_p, const double* p, int H_m, const double* mu, const double* W, const double* cost_bar,
+                                      double* gpvar_bar, double* p_bar, double* mu_bar, void* stream) {
+    sr_xpl_args c;
+    SR_TRY(rollout_explore_args("sr_rollout_explore_vjp", T, kind, n_s, H_v, gp_var, eps, n_dev, H_p, p, H_m, mu, W, c));
+    SR_CHECK(gpvar_bar || p_bar || mu_bar, SR_EINVAL, "sr_rollout_explore_vjp: every output NULL");
+    SR_CHECK((!p_bar || p) && (!mu_bar || mu), SR_EINVAL, "sr_rollout_explore_vjp: p_bar without p, or mu_bar without mu");
+    if (T == 0) return SR_OK;
+    SR_DEVICE(device);
+    c.cost_bar = cost_bar; c.gpvar_bar = gpvar_bar; c.p_bar = p_bar; c.mu_bar = mu_bar;
+    return sr_launch_rollout_explore(c, true, (hipStream_t)stream);
 }
 
 extern "C" int sr_distance_to_center(int device, long T, int K, int n_s, const double* samples, int per_t,

@@ -752,6 +752,9 @@ struct sr_rrv_args {
     const double* p0; const double* q0; const double* k_fb0; const double* k_ff; const double* k_fb;
     const double* p_all; const double* q_all; const double* p_all_bar; const double* q_all_bar;
     double* p0_bar; double* q0_bar; double* kfb0_bar; double* kff_bar; double* kfb_bar;   // q0_bar, kfb0_bar may be NULL in a point start
+    // seed on the GP variances the roll-out returns beside its outputs (T x H x n_s) or NULL: added to the step's var_bar in mode 0
+    // (sr_multistep_reach_var_vjp), read by sr_moments_vjp_one in modes 1 / 2
+    const double* gpvar_all_bar;
     // per-query scratch: z (n_xin + n_u), q_in / q_seed (n_s^2), kfb_in (n_u n_s), p_seed (n_s), eig (1 + 2 n_s + n_u: r^2, w, v, K v)
     double* z; double* q_in; double* kfb_in; double* p_seed; double* q_seed; double* eig;
 };
@@ -764,8 +767,7 @@ int sr_launch_reach_rollout_vjp(const sr_rrv_args& r, hipStream_t s);
 // mode 2, hess_mu set in mode 1 only (the sweep drops it at step 0 of a point start).  sr_launch_reach_rollout_prep(m.r) fills z, q_in
 // and kfb_in.
 struct sr_mrv_args {
-    sr_rrv_args r;
-    const double* gpvar_all_bar;      // seed on the GP variances (T x H x n_s) or NULL
+    sr_rrv_args r;                    // (r.gpvar_all_bar: the seed on the GP variances)
     int mode;                         // 1 Taylor, 2 mean-equivalent
 };
 int sr_launch_moments_rollout_vjp(const sr_mrv_args& m, hipStream_t s);
@@ -799,6 +801,15 @@ struct sr_rcn_args {
     double *g, *g_max, *p_all_bar, *q_all_bar, *kff_bar, *kfb_bar, *q0_bar, *kfb0_bar;
 };
 int sr_launch_rollout_constraints(sr_rcn_args a, bool reverse, hipStream_t s);
+// the exploration objective over stored GP variances and its reverse pass (sr_rollout_explore.hip): the arguments of
+// sr_rollout_explore / sr_rollout_explore_vjp; G the trajectories per workgroup of the forward (set by the launch)
+struct sr_xpl_args {
+    long T; int kind, n_s, H_v, n_dev, H_p, H_m, G;
+    double eps;
+    const double *gp_var, *p, *mu, *W, *cost_bar;
+    double *cost, *cost_steps, *gpvar_bar, *p_bar, *mu_bar;
+};
+int sr_launch_rollout_explore(sr_xpl_args a, bool reverse, hipStream_t s);
 
 // ---- fused small-batch posterior (sr_stream.hip) ------------------------------------------------------
 struct sr_lin_args;

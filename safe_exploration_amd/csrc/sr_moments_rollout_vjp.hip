@@ -41,7 +41,7 @@ __global__ __launch_bounds__(SR_MRV_THREADS) void sr_moments_rollout_vjp_kernel(
     const int H = r.H;
     const bool point = r.q0 == nullptr;
     sr_momvjp_args m;
-    m.e = r.e; m.gpvar_bar = mr.gpvar_all_bar; m.mode = MODE;
+    m.e = r.e; m.gpvar_bar = r.gpvar_all_bar; m.mode = MODE;
     sr_ellvjp_args& a = m.e;
     double* p_seed = r.p_seed;
     double* q_seed = r.q_seed;

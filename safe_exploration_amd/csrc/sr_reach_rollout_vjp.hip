@@ -10,7 +10,8 @@
 //   sr_reach_rollout_vjp_kernel    one thread per trajectory, i = H - 1 .. 0: seed of step i = the caller's seed on (p_all, q_all)[t][i]
 //                                  plus the (p_bar, q_bar) step i + 1 left; then the three stages of sr_reach_vjp_kernel at query n
 //                                  (sr_reach_gp_jac_one, sr_ellipsoid_vjp_one, sr_reach_gp_vjp_one: sr_ellipsoid_vjp_dev.h, nothing
-//                                  is derived here a second time); then k_fb_bar of the step to where the caller wants it.
+//                                  is derived here a second time; between the last two the caller's seed on the step's GP variances,
+//                                  where there is one, is added to var_bar); then k_fb_bar of the step to where the caller wants it.
 // Everything a thread reads back it wrote itself: no barrier, no atomics, no waiting between workgroups, sums in a fixed order --
 // the same bits on every call and for any grouping of the trajectories.
 // The caller's q seed is symmetrised BEFORE the carried q_bar (exactly symmetric) is added, and the sum is stored in both halves:
@@ -154,6 +155,11 @@ __global__ __launch_bounds__(SR_RRV_THREADS) void sr_reach_rollout_vjp_kernel(sr
             a.jac = a.jac_s;
         }
         sr_ellipsoid_vjp_one<NS, NU, true>(a, n, lds + threadIdx.x, BT, r.eig, ts);
+        // the caller's seed on this step's GP variances (sr_multistep_reach_var_vjp), between the stage that writes var_bar and the
+        // one that reads it.  Behind a branch: x + 0.0 is not x for x = -0.0; a NaN var_bar of a bound violation stays NaN
+        if (r.gpvar_all_bar)
+#pragma unroll
+            for (int k = 0; k < NS; ++k) a.var_bar[ts * NS + k] += r.gpvar_all_bar[n * NS + k];
         sr_reach_gp_vjp_one(a, n, NS, NU, ts);
         // the gradients of the controls: to the caller's kff_bar[t][i] and k_fb_bar[t][i - 1], or kfb0_bar[t]
 #pragma unroll

@@ -17,6 +17,10 @@ torch autograd.  Gradients reach the centres, shape matrices and controls (and m
 the model.  Mode 0 here (the moment modes: uncertainty_propagation_casadi); D <= 8.  A whole roll-out is differentiated in one
 call by ``multistep_reachability_vjp_batch`` / ``sr_multistep_reach_vjp`` (one linearisation pass over all T*H steps, then a
 sweep); ``multistep_reachability_diff_batch`` is the autograd surface over it, its forward the plain one-launch roll-out.
+The exploration objective (the reference's default MPC cost, a function of the GP variances of a roll-out): the variances come
+back with ``return_gp_var=True``, take a seed of their own in the reverse pass (``gpvar_all_bar``), and the objective with its
+closed-form gradient is ``exploration_cost_batch`` / ``exploration_cost_vjp_batch`` (``sr_rollout_explore``, one launch each);
+``safempc_default_cost`` is the reference's expression on the host.
 """
 import ctypes
 
@@ -385,11 +389,15 @@ def onestep_reachability(p_center, ssm, k_ff, l_mu, l_sigma, q_shape=None, k_fb=
 
 
 def multistep_reachability_batch(p_0, gp, k_fb, k_ff, L_mu, L_sigm, q_0=None, c_safety=1., a=None,
-                                 b=None, k_fb_init=None, check_bounds=False, t_z_gp=None, differentiable=False):
+                                 b=None, k_fb_init=None, check_bounds=False, t_z_gp=None, differentiable=False,
+                                 return_gp_var=False):
     """Batched ``multistep_reachability``: T independent trajectories, H sequential steps each.
 
     p_0 (T,n_s); k_fb (T,H-1,n_u,n_s); k_ff (T,H,n_u); q_0 (T,n_s,n_s) or None;
     k_fb_init (T,n_u,n_s) (needed iff q_0 is given).  Returns p_all (T,H,n_s), q_all (T,H,n_s,n_s).
+    return_gp_var: also gp_var_all (T,H,n_s), the GP's predictive variances at the linearisation point of every step (the
+    reference's third output, gp_pred_sigma_all), through ``sr_multistep_reach_var``: p_all and q_all keep their bits.  With
+    differentiable=True: NotImplementedError (``multistep_reachability_diff_batch(return_gp_var=True)`` is the surface for it).
     differentiable (tensors only): H differentiable one-step calls chained in torch (step 0 from the point, or from
     (q_0, k_fb_init), exactly as the forward), stacked into p_all, q_all with an autograd graph to p_0, q_0, k_fb_init, k_ff and
     k_fb.  Every step is one ``sr_onestep_reach`` call, so the values are those of the forward's per-step-launch route
@@ -402,6 +410,8 @@ def multistep_reachability_batch(p_0, gp, k_fb, k_ff, L_mu, L_sigm, q_0=None, c_
     if not isinstance(gp, SimpleGPModel):
         raise TypeError("multistep_reachability_batch needs the HIP SimpleGPModel")
     gp._need_trained()
+    if differentiable and return_gp_var:
+        raise NotImplementedError("return_gp_var with differentiable=True: use multistep_reachability_diff_batch(return_gp_var=True)")
     if differentiable:
         if not B.is_tensor(p_0):
             raise TypeError("differentiable=True needs tensors")
@@ -439,8 +449,11 @@ def multistep_reachability_batch(p_0, gp, k_fb, k_ff, L_mu, L_sigm, q_0=None, c_
         st = getattr(hd, "_staging", None)
         if st is None:
             st = hd._staging = B.Staging(dev)
-        (p0, kff, kfb, q0, kfb0), (p_all, q_all, bad_slot) = st.stage(
-            [np_p0.reshape(T, n_s), np_kff, np_kfb, np_q0, np_kfb0], [(T, H, n_s), (T, H, n_s, n_s), (1,)], zero_copy=True)
+        (p0, kff, kfb, q0, kfb0), outs_d = st.stage(
+            [np_p0.reshape(T, n_s), np_kff, np_kfb, np_q0, np_kfb0],
+            [(T, H, n_s), (T, H, n_s, n_s), (1,)] + ([(T, H, n_s)] if return_gp_var else []), zero_copy=True)
+        p_all, q_all, bad_slot = outs_d[:3]
+        gp_var = outs_d[3] if return_gp_var else None
     else:
         p0 = B.as_dev(p_0, dev)
         T = p0.shape[0]
@@ -453,6 +466,7 @@ def multistep_reachability_batch(p_0, gp, k_fb, k_ff, L_mu, L_sigm, q_0=None, c_
         kfb0 = B.as_dev(k_fb_init, dev, (T, n_u, n_s)) if q0 is not None else None
         p_all = B.empty((T, H, n_s), dev)
         q_all = B.empty((T, H, n_s, n_s), dev)
+        gp_var = B.empty((T, H, n_s), dev) if return_gp_var else None
     a, b = _lin_model(a, b, n_s, n_u)
     ta, tb = B.const_dev(a, dev, (n_s, n_s)), B.const_dev(b, dev, (n_s, n_u))
     tlm, tls = B.const_dev(L_mu, dev, (n_s,)), B.const_dev(L_sigm, dev, (n_s,))
@@ -463,28 +477,34 @@ def multistep_reachability_batch(p_0, gp, k_fb, k_ff, L_mu, L_sigm, q_0=None, c_
     else:
         n_bad = B.zeros_i32(1, dev) if check_bounds else None
     with _input_transform(gp, t_z_gp):
-        check(lib.sr_multistep_reach(hd.h, T, H, B.ptr(p0), B.ptr(q0), B.ptr(kfb0), B.ptr(kff), B.ptr(kfb),
-                                     B.ptr(ta), B.ptr(tb), B.ptr(tlm), B.ptr(tls), float(c_safety),
-                                     B.ptr(p_all), B.ptr(q_all), B.ptr(n_bad), B.stream_ptr(dev)))
+        head = (hd.h, T, H, B.ptr(p0), B.ptr(q0), B.ptr(kfb0), B.ptr(kff), B.ptr(kfb), B.ptr(ta), B.ptr(tb), B.ptr(tlm), B.ptr(tls),
+                float(c_safety), B.ptr(p_all), B.ptr(q_all))
+        if return_gp_var:
+            check(lib.sr_multistep_reach_var(*head, B.ptr(gp_var), B.ptr(n_bad), B.stream_ptr(dev)))
+        else:
+            check(lib.sr_multistep_reach(*head, B.ptr(n_bad), B.stream_ptr(dev)))
     if as_t:
         _raise_if_bad(n_bad)
-        return p_all, q_all
+        return (p_all, q_all, gp_var) if return_gp_var else (p_all, q_all)
     if staged:
-        p_np, q_np, bad_np = st.fetch()               # (synchronises the stream)
+        fetched = st.fetch()                          # (synchronises the stream)
+        p_np, q_np, bad_np = fetched[:3]
         if check_bounds:
             n_viol = int(bad_np.view(np.int32)[0])
             if n_viol > 0:
                 raise AssertionError("all elements of u_b need to be greater than zero! "
                                      "({} query state(s) affected)".format(n_viol))
         _raise_if_chain_failed(hd, dev, True)
-        return p_np, q_np
+        return (p_np, q_np, fetched[3]) if return_gp_var else (p_np, q_np)
     _raise_if_bad(n_bad)
     _raise_if_chain_failed(hd, dev, n_bad is not None)
+    if return_gp_var:
+        return B.to_numpy(p_all), B.to_numpy(q_all), B.to_numpy(gp_var)
     return B.to_numpy(p_all), B.to_numpy(q_all)
 
 
 def multistep_reachability_vjp_batch(p_0, gp, k_fb, k_ff, L_mu, L_sigm, p_all, q_all, p_all_bar=None, q_all_bar=None, q_0=None,
-                                     c_safety=1., a=None, b=None, k_fb_init=None, t_z_gp=None):
+                                     c_safety=1., a=None, b=None, k_fb_init=None, t_z_gp=None, gpvar_all_bar=None):
     """Reverse pass of ``multistep_reachability_batch`` in one call (``sr_multistep_reach_vjp``): one batched linearisation at the
     inputs of all T*H steps -- the centres p_all are known --, then a sweep over the steps, one thread per trajectory.
 
@@ -494,7 +514,9 @@ def multistep_reachability_vjp_batch(p_0, gp, k_fb, k_ff, L_mu, L_sigm, p_all, q
     k_fb_init, k_ff and k_fb; q0_bar and kfb_init_bar are None in a point start (q_0 None).  Only the symmetric part of q_all_bar
     counts, q0_bar is exactly symmetric, a step the forward would count as a bound violation turns the gradients that flow
     through it into NaN.  The same bits on every call and for any ``set_chunk``.  Models as ``linearize_device_batch`` takes
-    them (D <= 8: NotImplementedError beyond).  numpy in -> numpy out, tensors in -> tensors out."""
+    them (D <= 8: NotImplementedError beyond).  numpy in -> numpy out, tensors in -> tensors out.
+    gpvar_all_bar (T,H,n_s): a third seed, on the gp_var_all of ``multistep_reachability_batch(return_gp_var=True)``
+    (``sr_multistep_reach_var_vjp``; the clip of the variances is ignored); None: the call and the bits of before."""
     if not isinstance(gp, SimpleGPModel):
         raise TypeError("multistep_reachability_vjp_batch needs the HIP SimpleGPModel")
     as_t = B.is_tensor(p_0)
@@ -504,8 +526,8 @@ def multistep_reachability_vjp_batch(p_0, gp, k_fb, k_ff, L_mu, L_sigm, p_all, q
     n_s, n_u = _reach_dims(hd, t_z_gp)
     if q_0 is not None and k_fb_init is None:
         raise ValueError("k_fb_init is required when q_0 is given")
-    if p_all_bar is None and q_all_bar is None:
-        raise ValueError("at least one of p_all_bar, q_all_bar is needed")
+    if p_all_bar is None and q_all_bar is None and gpvar_all_bar is None:
+        raise ValueError("at least one of p_all_bar, q_all_bar, gpvar_all_bar is needed")
     p0 = B.as_dev(p_0, dev)
     T = p0.shape[0]
     if p0.dim() != 2 or p0.shape[1] != n_s:
@@ -526,6 +548,7 @@ def multistep_reachability_vjp_batch(p_0, gp, k_fb, k_ff, L_mu, L_sigm, p_all, q
     kfb0 = shaped(k_fb_init, (T, n_u, n_s), "k_fb_init") if q0 is not None else None
     pa, qa = shaped(p_all, (T, H, n_s), "p_all"), shaped(q_all, (T, H, n_s, n_s), "q_all")
     pab, qab = shaped(p_all_bar, (T, H, n_s), "p_all_bar"), shaped(q_all_bar, (T, H, n_s, n_s), "q_all_bar")
+    gvb = shaped(gpvar_all_bar, (T, H, n_s), "gpvar_all_bar")
     a, b = _lin_model(a, b, n_s, n_u)
     ta, tb = B.const_dev(a, dev, (n_s, n_s)), B.const_dev(b, dev, (n_s, n_u))
     tlm, tls = B.const_dev(L_mu, dev, (n_s,)), B.const_dev(L_sigm, dev, (n_s,))
@@ -533,10 +556,13 @@ def multistep_reachability_vjp_batch(p_0, gp, k_fb, k_ff, L_mu, L_sigm, p_all, q
     outs = [B.empty((T, n_s), dev), B.empty((T, n_s, n_s), dev) if ell else None, B.empty((T, n_u, n_s), dev) if ell else None,
             B.empty((T, H, n_u), dev), B.empty((T, H - 1, n_u, n_s), dev)]
     with _input_transform(gp, t_z_gp):
-        check(lib.sr_multistep_reach_vjp(hd.h, T, H, B.ptr(p0), B.ptr(q0), B.ptr(kfb0), B.ptr(kff), B.ptr(kfb), B.ptr(ta),
-                                         B.ptr(tb), B.ptr(tlm), B.ptr(tls), float(c_safety), B.ptr(pa), B.ptr(qa), B.ptr(pab),
-                                         B.ptr(qab), *[B.ptr(o) if o is not None and o.numel() else None for o in outs],
-                                         B.stream_ptr(dev)))
+        head = (hd.h, T, H, B.ptr(p0), B.ptr(q0), B.ptr(kfb0), B.ptr(kff), B.ptr(kfb), B.ptr(ta), B.ptr(tb), B.ptr(tlm), B.ptr(tls),
+                float(c_safety), B.ptr(pa), B.ptr(qa), B.ptr(pab), B.ptr(qab))
+        tail = [B.ptr(o) if o is not None and o.numel() else None for o in outs] + [B.stream_ptr(dev)]
+        if gvb is None:
+            check(lib.sr_multistep_reach_vjp(*head, *tail))
+        else:
+            check(lib.sr_multistep_reach_var_vjp(*head, B.ptr(gvb), *tail))
     return tuple(outs) if as_t else tuple(None if o is None else B.to_numpy(o) for o in outs)
 
 
@@ -556,30 +582,48 @@ class _MultistepReachFn(torch.autograd.Function):
 
     @staticmethod
     @torch.autograd.function.once_differentiable
-    def backward(ctx, p_all_bar, q_all_bar):
+    def backward(ctx, p_all_bar, q_all_bar, gpvar_all_bar=None):
         p_0, q_0, k_fb_init, k_ff, k_fb, p_all, q_all = ctx.saved_tensors
         L_mu, L_sigm, c_safety, a, b, _, t_z_gp = ctx.cfg
-        if p_all_bar is None and q_all_bar is None:
+        if p_all_bar is None and q_all_bar is None and gpvar_all_bar is None:
             return (None,) * 7
         g = multistep_reachability_vjp_batch(p_0, ctx.gp, k_fb, k_ff, L_mu, L_sigm, p_all, q_all, p_all_bar, q_all_bar, q_0,
-                                             c_safety, a, b, k_fb_init, t_z_gp)
+                                             c_safety, a, b, k_fb_init, t_z_gp, gpvar_all_bar)
         return None, None, g[0], g[1], g[2], g[3], (g[4].reshape(k_fb.shape) if k_fb is not None else None)
 
 
+class _MultistepReachVarFn(_MultistepReachFn):
+    """``multistep_reachability_diff_batch(return_gp_var=True)``: three outputs (p_all, q_all, gp_var_all); the backward, inherited,
+    is one ``sr_multistep_reach_var_vjp`` call."""
+
+    @staticmethod
+    def forward(ctx, gp, cfg, p_0, q_0, k_fb_init, k_ff, k_fb):
+        L_mu, L_sigm, c_safety, a, b, check_bounds, t_z_gp = cfg
+        p_all, q_all, gp_var = multistep_reachability_batch(p_0, gp, k_fb, k_ff, L_mu, L_sigm, q_0, c_safety, a, b, k_fb_init,
+                                                            check_bounds, t_z_gp, return_gp_var=True)
+        ctx.gp, ctx.cfg = gp, cfg
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(p_0, q_0, k_fb_init, k_ff, k_fb, p_all, q_all)
+        return p_all, q_all, gp_var
+
+
 def multistep_reachability_diff_batch(p_0, gp, k_fb, k_ff, L_mu, L_sigm, q_0=None, c_safety=1., a=None, b=None, k_fb_init=None,
-                                      check_bounds=False, t_z_gp=None):
+                                      check_bounds=False, t_z_gp=None, return_gp_var=False):
     """``multistep_reachability_batch`` (tensors only) with an autograd graph to p_0, q_0, k_fb_init, k_ff and k_fb: the forward IS
     the plain call (the persistent one-launch chain where it applies; the same bits, ``check_bounds`` honoured), the backward is
     ONE ``multistep_reachability_vjp_batch`` call at the saved p_all, q_all (once differentiable; no gradient to the model).
-    ``multistep_reachability_batch(differentiable=True)`` chains H one-step nodes instead and stays as it is."""
+    ``multistep_reachability_batch(differentiable=True)`` chains H one-step nodes instead and stays as it is.
+    return_gp_var: a third output gp_var_all (T,H,n_s) with a gradient of its own (the exploration objectives are functions of it,
+    ``exploration_cost_batch``); the backward is still one call, ``sr_multistep_reach_var_vjp``."""
     if not isinstance(gp, SimpleGPModel):
         raise TypeError("multistep_reachability_diff_batch needs the HIP SimpleGPModel")
     if not B.is_tensor(p_0):
         raise TypeError("multistep_reachability_diff_batch needs tensors")
     if q_0 is not None and k_fb_init is None:
         raise ValueError("k_fb_init is required when q_0 is given")
-    return _MultistepReachFn.apply(gp, (L_mu, L_sigm, c_safety, a, b, check_bounds, t_z_gp), p_0, q_0,
-                                   k_fb_init if q_0 is not None else None, k_ff, k_fb if k_ff.shape[1] > 1 else None)
+    fn = _MultistepReachVarFn if return_gp_var else _MultistepReachFn
+    return fn.apply(gp, (L_mu, L_sigm, c_safety, a, b, check_bounds, t_z_gp), p_0, q_0,
+                    k_fb_init if q_0 is not None else None, k_ff, k_fb if k_ff.shape[1] > 1 else None)
 
 
 def multistep_reachability(p_0, gp, k_fb, k_ff, L_mu, L_sigm, q_0=None, c_safety=1., verbose=1,
@@ -873,6 +917,160 @@ def safety_constraints(p_all, q_all, u_0, k_fb, k_ff_all, ctrl_bounds=None, h_ma
     lbg += [-np.inf] * (g.size - len(lbg))
     ubg += [0.0] * (g.size - len(ubg))
     return g, lbg, ubg, names
+
+
+# ------------------------------------------------------------------------------------------------
+# the exploration objective: the default cost of SimpleSafeMPC.generate_cost_function (safempc_simple.py:286-315) and of
+# StaticSafeMPCExploration.init_solver (safempc_exploration.py:104) over the stored GP variances of roll-outs
+# ------------------------------------------------------------------------------------------------
+def _explore_prepare(gp_var_all, kind, eps, p_all, mu_perf, wx_cost, n_dev, device):
+    """Shapes checked (ValueError, before anything touches the device), then everything on the device: the arguments both entry
+    points share, in the order of the C ABI after `device`."""
+    as_t = B.is_tensor(gp_var_all)
+    if kind not in ("sqrt", "sum"):
+        raise ValueError("kind must be 'sqrt' or 'sum'")
+    shp = tuple(np.shape(gp_var_all))
+    if len(shp) != 3 or shp[1] < 1 or shp[2] < 1:
+        raise ValueError("gp_var_all must be (T, H_v, n_s) with H_v >= 1")
+    T, H_v, n_s = shp
+    if not float(eps) >= 0.0:
+        raise ValueError("eps must be >= 0")
+    if (p_all is None) != (mu_perf is None):
+        raise ValueError("p_all and mu_perf go together")
+    H_p = H_m = 0
+    if p_all is not None:
+        ps, ms = tuple(np.shape(p_all)), tuple(np.shape(mu_perf))
+        if len(ps) != 3 or ps[0] != T or ps[1] < 1 or ps[2] != n_s or len(ms) != 3 or ms[0] != T or ms[1] < 1 or ms[2] != n_s:
+            raise ValueError("p_all must be (T, H_p, {0}) and mu_perf (T, H_m, {0})".format(n_s))
+        H_p, H_m = ps[1], ms[1]
+        n_dev = min(H_p, H_m) if n_dev is None else int(n_dev)
+        if n_dev == 1:
+            n_dev = 0                   # the deviation sum runs over 1 <= i < n_dev: empty
+        if n_dev < 0 or n_dev > min(H_p, H_m):
+            raise ValueError("n_dev must be within 0 .. min(H_p, H_m) = {}".format(min(H_p, H_m)))
+        if n_dev >= 2 and wx_cost is None:
+            raise ValueError("the deviation term needs wx_cost")
+    elif n_dev:
+        raise ValueError("n_dev without p_all, mu_perf")
+    else:
+        n_dev = 0
+    if n_s > 12:
+        raise NotImplementedError("exploration cost: n_s up to 12")
+    w = None
+    if wx_cost is not None and p_all is not None:
+        w = np.asarray(B.to_numpy(wx_cost) if B.is_tensor(wx_cost) else wx_cost, dtype=np.float64)
+        if w.shape != (n_s, n_s):
+            raise ValueError("wx_cost must be ({0}, {0})".format(n_s))
+    dev = B.resolve_device(gp_var_all.device if as_t else device)
+    W = None if w is None else B.const_dev(0.1 * w, dev, (n_s, n_s))      # the reference applies 0.1 wx_cost (safempc_simple.py:300)
+    v, p, m = B.as_dev(gp_var_all, dev), B.as_dev(p_all, dev), B.as_dev(mu_perf, dev)
+    head = (dev.index, T, 1 if kind == "sqrt" else 0, n_s, H_v, B.ptr(v), float(eps), n_dev, H_p, B.ptr(p), H_m, B.ptr(m), B.ptr(W))
+    return as_t, dev, (T, H_v, H_p, H_m, n_s), head, (v, p, m, W)
+
+
+def exploration_cost_batch(gp_var_all, kind="sqrt", eps=0., p_all=None, mu_perf=None, wx_cost=None, n_dev=None, return_steps=False,
+                           differentiable=False, device=None):
+    """The exploration objective of T roll-outs in one launch (``sr_rollout_explore``).
+
+    gp_var_all (T,H_v,n_s): the GP variances of a roll-out (``multistep_reachability_batch(return_gp_var=True)``, or the gp_var_all
+    of the moment roll-outs).  kind "sqrt": cost[t] = -sum_i sqrt(sum_j gp_var_all[t,i,j] + eps), the default objective of the
+    reference's ``SimpleSafeMPC.generate_cost_function``; "sum": -sum_i sum_j gp_var_all[t,i,j], that of
+    ``StaticSafeMPCExploration``.  With p_all (T,H_p,n_s) -- the safe trajectory --, mu_perf (T,H_m,n_s) -- the performance
+    trajectory -- and wx_cost (n_s,n_s): plus sum_{i=1}^{n_dev-1} d_i^T (0.1 wx_cost) d_i, d_i = mu_perf[t,i] - p_all[t,i] (n_dev
+    default min(H_p, H_m); the reference's n_perf > 1 branch with n_dev = min(n_perf, n_safe); n_dev = 0 or 1: an empty sum, no
+    deviation term -- the C ABI takes 0 for that and refuses 1).  Returns cost (T); with return_steps
+    (cost, steps (T,H_v)): the information terms.  differentiable (tensors only): the same bits, with an autograd graph to
+    gp_var_all, p_all and mu_perf whose backward is one ``exploration_cost_vjp_batch`` call (once differentiable; steps carries no
+    gradient).  numpy in -> numpy out, tensors in -> tensors out."""
+    if differentiable:
+        if not B.is_tensor(gp_var_all):
+            raise TypeError("differentiable=True needs tensors")
+        out = _ExploreCostFn.apply((kind, eps, wx_cost, n_dev), gp_var_all, p_all, mu_perf)
+        return out if return_steps else out[0]
+    as_t, dev, (T, H_v, H_p, H_m, n_s), head, keep = _explore_prepare(gp_var_all, kind, eps, p_all, mu_perf, wx_cost, n_dev, device)
+    cost = B.empty((T,), dev)
+    steps = B.empty((T, H_v), dev) if return_steps else None
+    check(lib.sr_rollout_explore(*head, B.ptr(cost), B.ptr(steps), B.stream_ptr(dev)))
+    outs = (cost, steps) if return_steps else (cost,)
+    if not as_t:
+        outs = tuple(B.to_numpy(o) for o in outs)
+    return outs if return_steps else outs[0]
+
+
+def exploration_cost_vjp_batch(gp_var_all, kind="sqrt", eps=0., p_all=None, mu_perf=None, wx_cost=None, n_dev=None, cost_bar=None,
+                               device=None):
+    """Reverse pass of ``exploration_cost_batch`` in one launch (``sr_rollout_explore_vjp``): for the seed cost_bar (T; None = ones)
+    the gradients of sum(cost_bar * cost): (gpvar_bar, p_bar, mu_bar), shaped like gp_var_all, p_all, mu_perf (None where the input
+    is None).  gpvar_bar is the seed gpvar_all_bar of ``multistep_reachability_vjp_batch`` (or of the moment roll-outs' reverse
+    pass), p_bar is added to the seed on p_all, mu_bar is the seed on the performance trajectory's means.  A radicand that is
+    exactly zero contributes zero; a negative one NaN in its own row of gpvar_bar only.  n_dev = 0 or 1: no deviation term, p_bar and
+    mu_bar all zero (as in ``exploration_cost_batch``)."""
+    if cost_bar is not None and tuple(np.shape(cost_bar)) != tuple(np.shape(gp_var_all))[:1]:
+        raise ValueError("cost_bar must be (T,)")
+    as_t, dev, (T, H_v, H_p, H_m, n_s), head, keep = _explore_prepare(gp_var_all, kind, eps, p_all, mu_perf, wx_cost, n_dev, device)
+    cb = B.as_dev(cost_bar, dev)
+    outs = [B.empty((T, H_v, n_s), dev), B.empty((T, H_p, n_s), dev) if p_all is not None else None,
+            B.empty((T, H_m, n_s), dev) if mu_perf is not None else None]
+    check(lib.sr_rollout_explore_vjp(*head, B.ptr(cb), *[B.ptr(o) for o in outs], B.stream_ptr(dev)))
+    return tuple(outs) if as_t else tuple(None if o is None else B.to_numpy(o) for o in outs)
+
+
+class _ExploreCostFn(torch.autograd.Function):
+    """``exploration_cost_batch(differentiable=True)``: the forward is the plain call, the backward one
+    ``exploration_cost_vjp_batch``."""
+
+    @staticmethod
+    def forward(ctx, cfg, gp_var_all, p_all, mu_perf):
+        kind, eps, wx_cost, n_dev = cfg
+        cost, steps = exploration_cost_batch(gp_var_all, kind, eps, p_all, mu_perf, wx_cost, n_dev, True)
+        ctx.cfg = cfg
+        ctx.save_for_backward(gp_var_all, p_all, mu_perf)
+        ctx.mark_non_differentiable(steps)
+        ctx.set_materialize_grads(False)
+        return cost, steps
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, cost_bar, _steps_bar):
+        gp_var_all, p_all, mu_perf = ctx.saved_tensors
+        kind, eps, wx_cost, n_dev = ctx.cfg
+        if cost_bar is None:
+            return (None,) * 4
+        out = exploration_cost_vjp_batch(gp_var_all, kind, eps, p_all, mu_perf, wx_cost, n_dev, cost_bar)
+        return (None,) + tuple(out)
+
+
+def safempc_default_cost(p_all, sigma_safe, mu_perf=None, gp_pred_sigma_perf=None, wx_cost=None, n_safe=None, n_perf=None,
+                         eps_noise=0.):
+    """Host twin (NumPy, no device) of the default branch of ``SimpleSafeMPC.generate_cost_function`` for ONE problem
+    (safempc_simple.py:286-315, no custom cost), under the reference's names: p_all (n_safe,n_s) the safe trajectory's centres,
+    sigma_safe (n_safe,n_s) its GP variances (gp_sigma_pred_safe_all), mu_perf (n_perf,n_s) and gp_pred_sigma_perf (n_perf,n_s) the
+    performance trajectory and its GP variances, wx_cost (n_s,n_s).  n_perf <= 1 (default: 0 without mu_perf, else its rows):
+    cost = -sum_{i < n_safe} sqrt(sum_j (sigma_safe[i,j] + eps_noise)).  n_perf > 1: cost = sum_{i=1}^{min(n_perf,n_safe)-1}
+    (mu_perf[i] - p_all[i]) (0.1 wx_cost) (mu_perf[i] - p_all[i])^T - sum_{i < n_perf} sqrt(sum_j (gp_pred_sigma_perf[i,j] +
+    eps_noise)).  The reference adds eps_noise to every element before it sums: on the device this is
+    ``exploration_cost_batch(..., eps=n_s * eps_noise)``.  Returns a float."""
+    p_all = np.asarray(p_all, dtype=np.float64)
+    sigma_safe = np.asarray(sigma_safe, dtype=np.float64)
+    n_safe = sigma_safe.shape[0] if n_safe is None else int(n_safe)
+    if n_perf is None:
+        n_perf = 0 if mu_perf is None else np.shape(mu_perf)[0]
+    cost = 0.0
+    if n_perf > 1:
+        if mu_perf is None or gp_pred_sigma_perf is None or wx_cost is None:
+            raise ValueError("n_perf > 1 needs mu_perf, gp_pred_sigma_perf and wx_cost")
+        mu_perf = np.asarray(mu_perf, dtype=np.float64)
+        sig = np.asarray(gp_pred_sigma_perf, dtype=np.float64)
+        w = 0.1 * np.asarray(wx_cost, dtype=np.float64)
+        for i in range(1, min(n_perf, n_safe)):
+            d = (mu_perf[i] - p_all[i]).reshape(1, -1)
+            cost += float(d.dot(w).dot(d.T)[0, 0])
+        for i in range(n_perf):
+            cost -= float(np.sqrt(np.sum(sig[i] + eps_noise)))
+    else:
+        for i in range(n_safe):
+            cost -= float(np.sqrt(np.sum(sigma_safe[i] + eps_noise)))
+    return cost
 
 
 # ------------------------------------------------------------------------------------------------
